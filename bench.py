@@ -14,7 +14,15 @@ Inputs are resident in HBM before timing. Weights: the reference's DI seed-0 ini
 (tests/golden/weights/di_seed0_0.npz); dVdx labels come from the DDP backward pass along the
 rollouts (cacto_ddp_backward, every system; the TO NLP solve itself is host-side CasADi, absent).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs: it sets the double integrator up, queues the
+clock-settling rollout batches (--long-steps, untimed) and the W warm-up steps, times the K steps,
+writes the last step's outputs when --dump-outputs is given, and prints the result line (`value`,
+`ms_per_step`, the timed region's segments and the rollout kernel's roofline). Everything else — the
+long region's own rates, the rollout variants, DDP labels, episode -> buffer, the update loops and
+their roofline, the other systems, the one-rank RCCL leg, configs[0] and the CPU baselines — runs
+with --full, which prints the same line with those records added.
 """
 import argparse
 import ctypes
@@ -48,6 +56,13 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=1000)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: the long region's rates, rollout "
+                        "variants, DDP labels, episode -> buffer, the update loops, the other systems, the "
+                        "one-rank RCCL leg, configs[0] and the CPU baselines (the options below trim it)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the last step's rollout outputs (S, A, R, EE, status of "
+                        "rank 0) as DIR/<name>.npy; above 60 MB a fixed, seeded sample of the episodes")
     p.add_argument("--system", default="double_integrator")
     p.add_argument("--rollouts", type=int, default=4096)
     p.add_argument("--update-steps", type=int, default=1000)
@@ -65,7 +80,8 @@ def parse():
     p.add_argument("--no-diagnostics", action="store_true",
                    help="skip the rollout variants (profiling runs: every k_rollout dispatch is a full rollout)")
     p.add_argument("--long-steps", type=int, default=1000,
-                   help="rollout batches of the long robustness region reported beside the K-step value")
+                   help="rollout batches queued before the warm-up so the timed steps run at settled clocks; "
+                        "with --full their rates are reported beside the K-step value (the long region)")
     p.add_argument("--dry-run", action="store_true",
                    help="rank plumbing only: launch / rendezvous (gloo on the CPU) and print each rank's "
                         "RANK / LOCAL_RANK / WORLD_SIZE and the device it would use; no GPU call")
@@ -337,19 +353,22 @@ def rollout_phase(rl, conf, env, R, K, W, world, rank):
     # region of max(K, LONG_STEPS) rollout batches, as 5 consecutive segments, median reported. It runs
     # BEFORE the contract's W warmup + K timed batches, so those are taken at settled GPU clocks (the
     # first ~100 batches of a fresh process ran 5-10 % slower while the clocks ramped, r02 / r03).
+    # A plain run queues the same batches to settle the clocks and takes no rates from them.
     steps_per_call = int(nsteps.sum())
     long_k = max(K, LONG_STEPS) if LONG_STEPS > 0 else 0
     long_region = None
     if long_k >= 5:
-        lev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+        lev = [torch.cuda.Event(enable_timing=True) for _ in range(6)] if FULL else None
         cuts_l = [j * long_k // 5 for j in range(6)]
         barrier(world)
-        lev[0].record()
+        if lev:
+            lev[0].record()
         for j in range(5):
             for _ in range(cuts_l[j + 1] - cuts_l[j]):
                 rl.rollout_batch(None, None, T, inputs=inputs, out=seq)
                 rl.rollout_rewards(out, n_d, T)
-            lev[j + 1].record()
+            if lev:
+                lev[j + 1].record()
     # the W warmup steps follow the long region on the queue with no host synchronisation between
     # them (its rates are read after the timed region), so the GPU does not idle before the timed
     # region's own barrier
@@ -382,7 +401,7 @@ def rollout_phase(rl, conf, env, R, K, W, world, rank):
     t1 = time.perf_counter()
     barrier(world)
     wall = max_over_ranks(t1 - t0, world)
-    if long_k >= 5:
+    if long_k >= 5 and lev:
         rates = [steps_per_call * (cuts_l[j + 1] - cuts_l[j]) / (lev[j].elapsed_time(lev[j + 1]) * 1e-3)
                  for j in range(5)]
         long_region = dict(batches=long_k, seconds=lev[0].elapsed_time(lev[5]) * 1e-3, segment_rates=rates,
@@ -402,7 +421,8 @@ def rollout_phase(rl, conf, env, R, K, W, world, rank):
     return dict(out=out, S0=S0, nsteps=nsteps, T=T, wall=wall, kernel_ms=kern_ms, seq_kernel_ms=seq_ms,
                 seq_kernel_ms_median=float(np.median([e[0].elapsed_time(e[1]) for e in evs])),
                 kernel_ms_samples=len(evs), rewards_kernel_ms=kern_ms - seq_ms, steps_per_call=steps_per_call,
-                total_steps=sum_over_ranks(steps_per_call * K, world), segments=seg, long_region=long_region)
+                total_steps=sum_over_ranks(steps_per_call * K, world), segments=seg, long_region=long_region,
+                settle_batches=long_k if long_k >= 5 else 0)
 
 
 def rollout_diagnostics(rl, conf, roll, K=5):
@@ -881,12 +901,30 @@ def flat_summary(updates, upd_roof, extra, world):
     return out
 
 
+def dump_outputs(path, out, budget=60e6, seed=0):
+    """The arrays the timed path's last step left (what a caller of rollout_batch + rollout_rewards
+    receives) as path/<name>.npy, float32 / float64. Above `budget` bytes a fixed, seeded sample of the
+    episodes is kept (the same rows of every array, in episode order) and episodes.npy lists them."""
+    os.makedirs(path, exist_ok=True)
+    n = out["S"].shape[0]
+    per_episode = sum(v[0].numel() * (v.element_size() if v.is_floating_point() else 8) for v in out.values()) + 8
+    keep = int(min(n, budget // per_episode))
+    idx = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False)) if keep < n else np.arange(n)
+    rows = torch.as_tensor(idx, device=out["S"].device)
+    for name, v in out.items():
+        a = v.index_select(0, rows).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+    np.save(os.path.join(path, "episodes.npy"), idx.astype(np.float64))
+
+
 USE_GRAPH = False
 LONG_STEPS = 1000
+# --full: everything beside the headline figure runs too
+FULL = False
 
 
 def main():
-    global USE_GRAPH, LONG_STEPS
+    global USE_GRAPH, LONG_STEPS, FULL
     args = parse()
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
@@ -898,6 +936,7 @@ def main():
         return dry_run(args)
     USE_GRAPH = args.graph
     LONG_STEPS = args.long_steps
+    FULL = args.full
     world, rank = init_dist()
     torch.backends.cuda.matmul.allow_tf32 = False
     conf, env, rl = make_learner(args.system)
@@ -908,6 +947,71 @@ def main():
     value = roll["total_steps"] / roll["wall"]
     # the dominant kernel is the sequential pass (k_rollout); its own HIP-event time
     achieved = roll["steps_per_call"] * fa_flops(ns, na) / (roll["seq_kernel_ms"] * 1e-3)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, roll["out"])
+    full = full_records(args, conf, env, rl, roll, world, rank) if FULL else None
+    traffic, traffic_src = pmc_traffic()
+    rw_traffic, _ = pmc_traffic("k_rollout_rewards<2>")
+    n_ep = len(roll["nsteps"])
+    roll_bytes = (roll["steps_per_call"] * (8 * ns + 4 * na + 8 + 24) + n_ep * (8 * ns + 24 + 8 * ns + 4)
+                  + 4 * rl.actor_model.P)
+    if rank == 0:
+        line = {
+            "metric": METRIC,
+            "value": value,
+            "unit": "env-steps/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": 1e3 * roll["wall"] / args.steps,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32 (MLP, MFMA) / f64 (dynamics)",
+            "data": "synthetic: Env.reset initial states (random.seed(rank)), reference DI seed-0 weights, "
+                    "dVdx labels from the DDP backward pass along the rollouts (cacto_ddp_backward)",
+            "config": {"workload": "double_integrator, w-S=1e-2, %d rollouts per GPU (BASELINE configs[1])"
+                                   % args.rollouts,
+                       "system": args.system, "rollouts_per_gpu": args.rollouts,
+                       "env_steps_per_rollout_batch": roll["steps_per_call"], "T_max": roll["T"],
+                       "parallelism": "dp%d" % world},
+            "full": FULL,
+            # untimed rollout batches queued before the W warm-up steps (--long-steps: clock settling)
+            "settle_batches": roll["settle_batches"],
+            "segments": roll["segments"],
+            "roofline": {"kernel": "k_rollout (k_rollout_ks<2>: one slot per wave, layer 2 split over K, at this "
+                                   "schedule)",
+                         "bound": "mfma", "achieved": achieved / 1e12,
+                         "peak": FP32_MFMA_PEAK / 1e12, "unit": "TFLOP/s", "frac": achieved / FP32_MFMA_PEAK,
+                         "traffic": traffic, "traffic_unit": "bytes/launch", "traffic_source": traffic_src,
+                         "kernel_ms": roll["seq_kernel_ms"], "kernel_ms_samples": roll["kernel_ms_samples"],
+                         "flop_per_env_step": fa_flops(ns, na),
+                         "rollout_batch_ms": roll["kernel_ms"], "rewards_kernel_ms": roll["rewards_kernel_ms"],
+                         "env_steps_per_launch": roll["steps_per_call"],
+                         # bytes the batch (k_rollout + k_rollout_rewards) must move: per env step
+                         # s_{t+1} (8 ns), a_t (4 na), r_t (8), EE (24) written; per episode s_0 read
+                         # and written, EE_0, the length; the actor weights read once
+                         "batch_algorithmic_bytes": roll_bytes,
+                         "batch_traffic": (traffic + rw_traffic) if traffic and rw_traffic else None,
+                         "batch_traffic_over_algorithmic": ((traffic + rw_traffic) / roll_bytes
+                                                            if traffic and rw_traffic else None)},
+        }
+        if full is not None:
+            line["roofline"].update(full.pop("roofline"))
+            line.update(full)
+        else:
+            line.update(flat_summary(None, None, None, world))      # what the distributed run was
+        print(json.dumps(line))
+    if world > 1 or DP1_GROUP is not None:
+        import torch.distributed as dist
+        dist.destroy_process_group()
+
+
+def full_records(args, conf, env, rl, roll, world, rank):
+    """What --full adds to the result line (rank 0; {} on the other ranks, which run the same
+    phases): the long region, rollout variants, DDP labels, episode -> buffer, the update loops with
+    their roofline, the other systems, configs[0] and the CPU baselines."""
+    ns, na = conf.nb_state, conf.nb_action
     diag = None if args.no_diagnostics else rollout_diagnostics(rl, conf, roll)
     labels, ddp = ddp_labels(rl, conf, env, roll)
     buf = fill_buffer(rl, conf, roll, env, seed=rank, dVdx=labels)
@@ -944,11 +1048,6 @@ def main():
     c0 = None if args.no_config0 else config0(args, rank, max(20, int(args.cpu_seconds * 20)))
     if cpu is not None:
         cpu["host"] = host_info()
-    traffic, traffic_src = pmc_traffic()
-    rw_traffic, _ = pmc_traffic("k_rollout_rewards<2>")
-    n_ep = len(roll["nsteps"])
-    roll_bytes = (roll["steps_per_call"] * (8 * ns + 4 * na + 8 + 24) + n_ep * (8 * ns + 24 + 8 * ns + 4)
-                  + 4 * rl.actor_model.P)
     upd_roof = None
     upd_roofs = {}
     if updates:
@@ -968,63 +1067,26 @@ def main():
                              "counter_bytes_per_update": ctr, "counter_bytes_by_kernel": per,
                              "counter_over_algorithmic": (ctr / by) if ctr else None, "traffic_source": src}
         upd_roof = upd_roofs[[int(b) for b in args.batches.split(",") if b][0]]
-    if rank == 0:
-        line = {
-            "metric": METRIC,
-            "value": value,
-            "unit": "env-steps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * roll["wall"] / args.steps,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32 (MLP, MFMA) / f64 (dynamics)",
-            "data": "synthetic: Env.reset initial states (random.seed(rank)), reference DI seed-0 weights, "
-                    "dVdx labels from the DDP backward pass along the rollouts (cacto_ddp_backward)",
-            "config": {"workload": "double_integrator, w-S=1e-2, %d rollouts per GPU (BASELINE configs[1])"
-                                   % args.rollouts,
-                       "system": args.system, "rollouts_per_gpu": args.rollouts,
-                       "env_steps_per_rollout_batch": roll["steps_per_call"], "T_max": roll["T"],
-                       "parallelism": "dp%d" % world},
-            "segments": roll["segments"],
-            "long_region": roll["long_region"],
-            "roofline": {"kernel": "k_rollout (k_rollout_ks<2>: one slot per wave, layer 2 split over K, at this "
-                                   "schedule)",
-                         "bound": "mfma", "achieved": achieved / 1e12,
-                         "peak": FP32_MFMA_PEAK / 1e12, "unit": "TFLOP/s", "frac": achieved / FP32_MFMA_PEAK,
-                         "traffic": traffic, "traffic_unit": "bytes/launch", "traffic_source": traffic_src,
-                         "kernel_ms": roll["seq_kernel_ms"], "kernel_ms_samples": roll["kernel_ms_samples"],
-                         "flop_per_env_step": fa_flops(ns, na),
-                         "rollout_batch_ms": roll["kernel_ms"], "rewards_kernel_ms": roll["rewards_kernel_ms"],
-                         "env_steps_per_launch": roll["steps_per_call"],
-                         # bytes the batch (k_rollout + k_rollout_rewards) must move: per env step
-                         # s_{t+1} (8 ns), a_t (4 na), r_t (8), EE (24) written; per episode s_0 read
-                         # and written, EE_0, the length; the actor weights read once
-                         "batch_algorithmic_bytes": roll_bytes,
-                         "batch_traffic": (traffic + rw_traffic) if traffic and rw_traffic else None,
-                         "batch_traffic_over_algorithmic": ((traffic + rw_traffic) / roll_bytes
-                                                            if traffic and rw_traffic else None),
-                         "update": upd_roof,
-                         "update_by_batch": {str(k): v for k, v in upd_roofs.items()}},
-            "critic_updates": updates,
-            "update_pipeline": pipe,
-            "episode_to_buffer": e2b,
-            "ddp_labels": ddp,
-            "rollout_diagnostics": diag,
-            "cpu_baseline": cpu,
-            "extra_systems": extra,
-            "config0": c0,
-        }
-        line.update(flat_summary(updates, upd_roof, extra, world))
-        for Bu, r in upd_roofs.items():     # flat per-batch copies (a record that keeps only scalars)
-            line["di_update_counter_over_algorithmic_b%d" % Bu] = r["counter_over_algorithmic"]
-            line["di_update_counter_bytes_b%d" % Bu] = r["counter_bytes_per_update"]
-        print(json.dumps(line))
-    if world > 1 or DP1_GROUP is not None:
-        import torch.distributed as dist
-        dist.destroy_process_group()
+    if rank != 0:
+        return {}
+    rec = {
+        "long_region": roll["long_region"],
+        "roofline": {"update": upd_roof,
+                     "update_by_batch": {str(k): v for k, v in upd_roofs.items()}},
+        "critic_updates": updates,
+        "update_pipeline": pipe,
+        "episode_to_buffer": e2b,
+        "ddp_labels": ddp,
+        "rollout_diagnostics": diag,
+        "cpu_baseline": cpu,
+        "extra_systems": extra,
+        "config0": c0,
+    }
+    rec.update(flat_summary(updates, upd_roof, extra, world))
+    for Bu, r in upd_roofs.items():     # flat per-batch copies (a record that keeps only scalars)
+        rec["di_update_counter_over_algorithmic_b%d" % Bu] = r["counter_over_algorithmic"]
+        rec["di_update_counter_bytes_b%d" % Bu] = r["counter_bytes_per_update"]
+    return rec
 
 
 if __name__ == "__main__":

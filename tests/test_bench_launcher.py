@@ -68,6 +68,33 @@ def test_failing_rank_fails_the_launch():
     assert "rank 1 exited with 3" in r.stderr
 
 
+def test_dump_outputs_is_float_and_samples_the_same_episodes(tmp_path):
+    """--dump-outputs: every array as float32 / float64 .npy; above the byte budget the same seeded
+    episode rows of every array, identical from call to call."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    out = {"S": torch.randn(50, 7, 5, dtype=torch.float64, generator=g),
+           "A": torch.randn(50, 6, 2, dtype=torch.float32, generator=g),
+           "status": torch.arange(50, dtype=torch.int32)}
+    bench.dump_outputs(str(tmp_path / "all"), out)
+    full = {k: np.load(str(tmp_path / "all" / (k + ".npy"))) for k in list(out) + ["episodes"]}
+    assert full["S"].dtype == np.float64 and full["A"].dtype == np.float32 and full["status"].dtype == np.float64
+    assert all(np.array_equal(full[k], out[k].numpy()) for k in out)
+    assert np.array_equal(full["episodes"], np.arange(50))
+    per_episode = 7 * 5 * 8 + 6 * 2 * 4 + 8 + 8     # S, A, status (as float64), episodes
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out, budget=20 * per_episode + 1)
+    a = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in full}
+    b = {k: np.load(str(tmp_path / "b" / (k + ".npy"))) for k in full}
+    idx = a["episodes"].astype(int)
+    assert len(idx) == 20 and (np.diff(idx) > 0).all()
+    assert sum(v.nbytes for v in a.values()) == 20 * per_episode
+    for k in out:
+        assert np.array_equal(a[k], out[k].numpy()[idx]) and np.array_equal(a[k], b[k])
+
+
 def test_hanging_rank_is_killed_at_the_timeout():
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--launch-timeout", "8"],
                        capture_output=True, text=True, timeout=180, env=_env(CACTO_DRYRUN_HANG_RANK="0"))

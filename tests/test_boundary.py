@@ -11,7 +11,7 @@ from cacto_amd import _lib as L
 from cacto_amd.confs import load_conf
 from cacto_amd.robots import builtin_model
 from cacto_amd.urdf import parse_urdf
-from conftest import REFERENCE
+from conftest import GOLDEN
 
 
 def test_library_exports_every_header_symbol():
@@ -44,12 +44,11 @@ def test_workspace_query_without_gpu_needs_a_handle():
     assert L.lib().dll.cacto_workspace_bytes(None, 128) == 0
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference checkout not present")
 @pytest.mark.parametrize("urdf,name", [("double_integrator.urdf", "double_integrator"),
                                        ("planar_manipulator_3dof.urdf", "planar_manipulator_3dof"),
                                        ("ur5_robot.urdf", "ur5")])
 def test_builtin_models_match_reference_urdf(urdf, name):
-    m = parse_urdf(os.path.join(REFERENCE, "urdf", urdf))
+    m = parse_urdf(os.path.join(GOLDEN, "urdf", urdf))
     b = builtin_model(name)
     np.testing.assert_allclose(m.table(), b.table(), atol=1e-12)
     assert m.ee_parent == b.ee_parent
@@ -57,31 +56,23 @@ def test_builtin_models_match_reference_urdf(urdf, name):
     np.testing.assert_allclose(m.ee_R, b.ee_R)
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference checkout not present")
 def test_ur5_urdf_parses():
-    m = parse_urdf(os.path.join(REFERENCE, "urdf", "ur5_robot.urdf"))
+    m = parse_urdf(os.path.join(GOLDEN, "urdf", "ur5_robot.urdf"))
     assert m.nq == 6 and m.ee_parent == 5
     assert all(j.kind == 0 for j in m.joints)
 
 
-def _ref_constants(fname):
-    """Literal module-level constants of a reference conf file (read as text, via ast)."""
-    import ast
-    src = open(os.path.join(REFERENCE, fname)).read()
-    out = {}
-    for node in ast.parse(src).body:
-        if isinstance(node, ast.Assign) and len(node.targets) == 1 and isinstance(node.targets[0], ast.Name):
-            try:
-                out[node.targets[0].id] = ast.literal_eval(node.value)
-            except Exception:
-                pass
-    return out
+def _ref_constants(system):
+    """Literal module-level constants of a reference conf file (tests/golden/ref_conf_constants.json,
+    extracted from the file's text via ast by tests/golden/make_ref_files.py)."""
+    import json
+    with open(os.path.join(GOLDEN, "ref_conf_constants.json")) as f:
+        return json.load(f)[system]
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference checkout not present")
 @pytest.mark.parametrize("system", ["single_integrator", "double_integrator", "manipulator", "car", "car_park", "ur5"])
 def test_conf_constants_match_reference(system):
-    ref = _ref_constants("conf_%s.py" % system)
+    ref = _ref_constants(system)
     conf = load_conf(system)
     keys = [k for k in ref if hasattr(conf, k) and not k.endswith("_path") and k not in ("test_set",)]
     assert len(keys) > 30

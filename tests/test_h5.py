@@ -1,8 +1,8 @@
 """Keras-2.11 .h5 checkpoint interop (cacto_amd/h5.py).
 
 * Reading: the reference's own checkpoints (`Results */NNs/N_try_*/{actor,critic,target_critic}_*.h5`,
-  RL.py:191-195) against the .npz fixtures tests/golden/make_h5_fixtures.py extracted from them with
-  h5py — skipped where /root/reference is absent (the GPU box).
+  RL.py:191-195; copies under tests/golden/h5/) against the .npz fixtures
+  tests/golden/make_h5_fixtures.py extracted from them with h5py.
 * Writing: round trip through the native reader, and — where an interpreter with h5py exists in
   this container (/opt/conda/bin/python3.9) — the written file opened by h5py itself, the library
   Keras' load_weights uses.
@@ -21,6 +21,8 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "weigh
 DI = os.path.join(REF, "Results Double Integrator/Results set test/NNs/N_try_6")
 SI = os.path.join(REF, "Results Single Integrator/Results set test/NNs")
 H5PY_PYTHON = "/opt/conda/bin/python3.9"
+# copies of the checkpoints below (tests/golden/make_ref_files.py), named <tag without its step>_<file>
+H5 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "h5")
 
 CASES = [
     ("di_seed0_0", "actor", os.path.join(DI, "actor_0.h5")),
@@ -36,8 +38,9 @@ CASES = [
 
 @pytest.mark.parametrize("tag,key,path", CASES)
 def test_read_reference_checkpoints(tag, key, path):
-    if not os.path.exists(path):
-        pytest.skip("reference checkpoints are not present on this machine")
+    # `path` is where the checkpoint lies in a reference checkout (and the case's id); what is read is
+    # its copy in the repository
+    path = os.path.join(H5, "%s_%s" % (tag.rsplit("_", 1)[0], os.path.basename(path)))
     z = np.load(os.path.join(GOLD, tag + ".npz"))
     got = h5.read_keras_weights(path)
     n = len([k for k in z.files if k.startswith(key + "_")])
@@ -49,9 +52,7 @@ def test_read_reference_checkpoints(tag, key, path):
 
 
 def test_reference_attributes():
-    path = os.path.join(DI, "target_critic_0.h5")
-    if not os.path.exists(path):
-        pytest.skip("reference checkpoints are not present on this machine")
+    path = os.path.join(H5, "di_seed0_target_critic_0.h5")
     f = h5.H5File(open(path, "rb").read())
     attrs = f.attributes(f.object(f.root))
     assert attrs["keras_version"] == b"2.11.0" and attrs["backend"] == b"tensorflow"

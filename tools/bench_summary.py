@@ -1,4 +1,5 @@
-"""Print the headline figures of a bench.py JSON line: python tools/bench_summary.py FILE"""
+"""Print the headline figures of a bench.py JSON line (every record of a `bench.py --full` line, the
+rollout figures alone of a plain one): python tools/bench_summary.py FILE"""
 import json
 import sys
 
@@ -9,7 +10,7 @@ if d.get("long_region"):
     lr = d["long_region"]
     print("  long region: %d batches, %.2f s, median %.1f M/s, spread %.3f" % (lr["batches"], lr["seconds"],
                                                                              lr["median"] / 1e6, lr["spread"]))
-for k, v in d["critic_updates"].items():
+for k, v in (d.get("critic_updates") or {}).items():
     print("  DI %s: %.0f updates/s (%.1f us) mfma %.3f" % (k, v["value"], v["ms_per_update"] * 1e3, v["mfma_frac"]))
 for s, e in (d.get("extra_systems") or {}).items():
     print("%s rollout %.1f M/s frac %.3f ddp %.2f ms; " % (s, e["env_steps_per_s"] / 1e6, e["rollout_mfma_frac"],

@@ -1,4 +1,4 @@
-"""Print the critic-updates/s entries of bench.py JSON lines: python tools/show_updates.py FILE..."""
+"""Print the critic-updates/s entries of `bench.py --full` JSON lines: python tools/show_updates.py FILE..."""
 import json
 import sys
 
