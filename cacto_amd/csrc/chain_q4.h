@@ -20,7 +20,7 @@
 // Per-sample work (row gathers, input normalisation, dynamics, losses) runs one (sample, feature)
 // element per thread.
 //
-// Included by learn_kernels.hip (uses its GradBufs, ChainScalars, clog, CSTAMP).
+// Included by learn_kernels.hip (uses its clog and CSTAMP, and learn.h's GradBufs and ChainScalars).
 #pragma once
 
 #include "q4.h"

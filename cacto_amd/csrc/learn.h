@@ -1,0 +1,123 @@
+// Where learn_kernels.hip (the kernels, the launch_* functions that name one, the knobs that pick
+// one) and learn_host.hip (workspace, C ABI, update pipelines) meet: plain structs and declarations.
+#pragma once
+
+#include "internal.h"
+#include "per_device.h"
+
+namespace cacto {
+
+struct GradBufs {
+  float* LT[MAX_LAYERS];
+  float* RT[MAX_LAYERS];
+  int ld;  // row stride of the panels
+  int Bp;  // batch rounded up to 16
+};
+
+struct ChainScalars {
+  float w_S;
+  int MC;
+  int B_global;
+  int want_vt;
+  // the two-stream pipeline's device-side ordering (DESIGN §3 "memory-ordering contract"): the actor
+  // chain waits, before its critic pass at s', until *wait_p >= wait_v (the critic's Adam of the same
+  // update has run) — a relaxed poll, no fence: the Adam wrote the critic through to memory at agent
+  // scope and published after its stores completed, and no L2 holds a line of the buffer from before
+  // (kernel starts invalidate; nothing reads it in between)
+  const unsigned long long* wait_p;
+  unsigned long long wait_v;
+  // 1 (the PER loops): that wait at the chain's start, before it gathers the sampled rows (the
+  // sample of the update precedes the critic's Adam on the other stream)
+  int wait_at_start;
+  // 1: the 16-sample tiles dealt so that the tiles of one 256-row GEMM chunk run on the XCD that
+  // k_wgrad_big runs that chunk on (chain_tile_of)
+  int xcd_tiles;
+};
+
+struct WgLayer {
+  const float* LT;
+  const float* RT;
+  int in, out, IT, OT, woff, boff;
+};
+struct WgArgs {
+  WgLayer l[MAX_LAYERS];
+  int nl, ld, r_begin, r_end, bias_r0, CH, nch, P, tpc;
+  int toff[MAX_LAYERS + 1];
+  unsigned char perm[64];  // k_wgrad_big: the items of a chunk by decreasing work (full 4 x 4 blocks first)
+};
+
+struct AdamArgs {
+  double beta1, beta2, eps, tau;
+  double lr[5];
+  double bounds[4];
+  int which;  // 0 critic counter, 1 actor counter
+  int soft;
+};
+struct AdamNet {  // one network of the fused weight-gradient + Adam launch (k_wgrad_adam)
+  WgArgs wg;  // panels, rows, 64-row chunking (as k_wgrad)
+  NetTopo t;
+  const float* src;  // weights the step starts from (== nb for an in-place step)
+  float* nb;
+  float4* pk;
+  float* m;
+  float* v;
+  float* target;  // soft update (critic) or nullptr
+  float4* tpk;
+  AdamArgs ad;
+  int items;                    // weight tiles + bias tiles, all layers
+  int ioff[MAX_LAYERS + 1];     // first item of layer l: KT*OT weight tiles then OT bias tiles
+};
+
+struct Workspace {
+  GradBufs crit, act;
+  float* slab;    // critic weight-gradient slabs
+  float* slab_a;  // actor's (a separate region: cacto_update_n overlaps the two steps)
+  float* cshadow; // two more critic net buffers (cacto_update_n rotates the critic over three)
+  int32_t* pidx;  // cacto_update_n_per: sampled indices, a ring of five buffers of Bp
+  float* pisw;    // and the IS weights of the current update
+  int32_t* runs;  // the overlapped PER loop's per-subtree sample runs (2 x PER_RUN_SUB ints)
+  float* scal;  // y, V, Vt scratch (3 * Bp)
+  size_t bytes;
+  int Bp;
+};
+
+// Which kernel a batch takes (learn_kernels.hip): functions of the batch and the network only.
+int q4_max_bp();
+int chain_tile(int Bp);
+int cu_count();
+int wg_chunk(int rows);
+bool wgrad_big(const NetTopo& t, int rows);
+bool fused_adam(int Bp);
+
+int launch_reduce(const float* slab, int nch, int P, float* out, hipStream_t st);
+// the weight-gradient GEMM of a network into its slabs (launch_wgrad over the critic's / actor's rows)
+int launch_critic_wgrad(const cacto_sys* sys, bool sobolev, const Workspace& w, hipStream_t st,
+                        int* nch, const PerRunArgs* per_run = nullptr);
+int launch_actor_wgrad(const cacto_sys* sys, const Workspace& w, hipStream_t st, int* nch,
+                       unsigned long long* sig_p = nullptr, unsigned long long sig_v = 0);
+int launch_critic_chain(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
+                        const double* storage, const int32_t* idx, const float* isw, int B, float* y, float* V,
+                        float* Vt, const Workspace& w, hipStream_t st);
+int launch_actor_chain(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
+                       const double* storage, const int32_t* idx, int B, const Workspace& w, hipStream_t st,
+                       const unsigned long long* wait_p = nullptr, unsigned long long wait_v = 0,
+                       int wait_at_start = 0);
+ChainScalars chain_scalars(const cacto_update_cfg* cfg, int B);
+int launch_chain_pair(const cacto_sys* sys, const NetView& C, const NetView& Tg, const NetView& Ac,
+                      const ChainScalars& cs, const double* storage, const int32_t* idx_c, const float* isw,
+                      const int32_t* idx_a, int B, const Workspace& w, float* y, float* V, int32_t* step,
+                      hipStream_t st);
+int launch_adam(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg, int which,
+                const float* slab, int nch, int soft, hipStream_t st, const float* src = nullptr,
+                const unsigned long long* wait_p = nullptr, unsigned long long wait_v = 0,
+                unsigned long long* sig_p = nullptr, unsigned long long sig_v = 0,
+                const PerSampleArgs* sample = nullptr, int thru = 0);
+AdamNet critic_adam_net(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg, const Workspace& w,
+                        int soft, const float* src, float* nb);
+AdamNet actor_adam_net(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg, const Workspace& w);
+int launch_wgrad_adam(const cacto_sys* sys, int mode, const AdamNet& n0, const AdamNet* n1, const int32_t* step,
+                      hipStream_t st);
+int launch_soft(const cacto_sys* sys, const cacto_nets* nets, float tau, hipStream_t st);
+int launch_pipe_probe(unsigned long long* w, int role, hipStream_t st);
+
+}  // namespace cacto

@@ -10,14 +10,13 @@
 //   actor rows : [0, Bp) = (h_l, zbar_l)
 //   -> k_wgrad: one wave per (layer, 16x16 output tile | bias tile, row chunk) -> slab[chunk][P]
 //   -> k_adam : sum chunks in fixed order (deterministic), Adam, packed copies, soft update.
+// The host side (workspace, C ABI, update pipelines) is learn_host.hip; the two meet in learn.h.
 #include <algorithm>
-#include <atomic>
-#include <cstring>
 #include <cstdlib>
 #include <vector>
 
+#include "learn.h"
 #include "net_common.h"
-#include "per_device.h"
 
 #ifdef CACTO_STAMPS
 __device__ unsigned long long g_cstamps[32];
@@ -40,33 +39,6 @@ __device__ unsigned long long g_astamps[32];  // actor chain, tile 0 (also insid
 #endif
 
 namespace cacto {
-
-struct GradBufs {
-  float* LT[MAX_LAYERS];
-  float* RT[MAX_LAYERS];
-  int ld;  // row stride of the panels
-  int Bp;  // batch rounded up to 16
-};
-
-struct ChainScalars {
-  float w_S;
-  int MC;
-  int B_global;
-  int want_vt;
-  // the two-stream pipeline's device-side ordering (DESIGN §3 "memory-ordering contract"): the actor
-  // chain waits, before its critic pass at s', until *wait_p >= wait_v (the critic's Adam of the same
-  // update has run) — a relaxed poll, no fence: the Adam wrote the critic through to memory at agent
-  // scope and published after its stores completed, and no L2 holds a line of the buffer from before
-  // (kernel starts invalidate; nothing reads it in between)
-  const unsigned long long* wait_p;
-  unsigned long long wait_v;
-  // 1 (the PER loops): that wait at the chain's start, before it gathers the sampled rows (the
-  // sample of the update precedes the critic's Adam on the other stream)
-  int wait_at_start;
-  // 1: the 16-sample tiles dealt so that the tiles of one 256-row GEMM chunk run on the XCD that
-  // k_wgrad_big runs that chunk on (chain_tile_of)
-  int xcd_tiles;
-};
 
 // Block b -> tile of a 16-sample chain grid. xcd_tiles (ntiles % 128 == 0): block b runs on XCD
 // b % 8 (the dispatcher's round robin), which k_wgrad_big gives the 256-row chunks x, x + 8, ... —
@@ -742,18 +714,6 @@ __global__ void __launch_bounds__(CACTO_THREADS)
 namespace cacto {
 
 // ---------------------------------------------------------------- weight-gradient GEMM
-struct WgLayer {
-  const float* LT;
-  const float* RT;
-  int in, out, IT, OT, woff, boff;
-};
-struct WgArgs {
-  WgLayer l[MAX_LAYERS];
-  int nl, ld, r_begin, r_end, bias_r0, CH, nch, P, tpc;
-  int toff[MAX_LAYERS + 1];
-  unsigned char perm[64];  // k_wgrad_big: the items of a chunk by decreasing work (full 4 x 4 blocks first)
-};
-
 // One workgroup per (row chunk, item). An item is a block of up to 4 x 4 output tiles of one layer
 // (the 4 waves split the chunk's rows, each keeping 16 accumulator tiles, then reduce through LDS
 // in a fixed order, so the result is deterministic), or up to 4 bias tiles (one per wave). A
@@ -935,8 +895,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))
 // NI = 1) and walks every 16-row step of the chunk, so each wave's accumulators cover the whole chunk
 // and are written straight to the slab (no cross-wave LDS reduction). The workgroup stages each
 // step's panel slices (NI + NO slices of 16 features x 16 rows, 2 float4 per thread) through a
-// 2-buffer LDS ring, with the global loads issued AH steps ahead into registers, so the
-// latency of a step's loads hides behind AH steps of MFMAs (k_wgrad: one step, and a wave
+// 2-buffer LDS ring, with the global loads issued WGB_AHEAD steps ahead into registers, so the
+// latency of a step's loads hides behind WGB_AHEAD steps of MFMAs (k_wgrad: one step, and a wave
 // covered only 2-4 steps of its chunk, so its time was mostly load latency: 18-21 us per launch at
 // B = 4096 alone, 0.17 of the MFMA peak). Each tile's sum runs over the chunk's rows in row order
 // (one MFMA accumulator chain; four k-phase chains for the 1-tile waves of edge blocks) — a
@@ -945,12 +905,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))
 constexpr int WGB_FS = 20;                    // floats per staged feature row (16 rows + 4 pad: LDS banks)
 constexpr int WGB_SLICE = 16 * WGB_FS;        // one 16 x 16 panel slice
 constexpr int WGB_STAGE = 8 * WGB_SLICE;      // up to 4 A + 4 B slices
+// The load lead in 16-row steps. A lead of 6 gave the same sums and measured no better (updates/s,
+// two runs each): DI B = 4096 13.41 / 13.38 k at 6 against 13.33 / 13.37 k at 3, manipulator
+// B = 8192 8.29 / 8.26 k against 8.36 / 8.34 k — inside the pipeline the GEMM is not waiting on its
+// loads, so the lighter form stays.
+constexpr int WGB_AHEAD = 3;
 
-template <int NI, int NO, int AH>
+template <int NI, int NO>
 __device__ __forceinline__ void wgb_block(const int ld, const WgLayer Ly, int lo, int hi, int it0, int ot0,
                                           float* __restrict__ out, float* stage) {
   static_assert((NI == 4 && (NO == 4 || NO == 1)) || (NI == 1 && NO == 4), "block shape");
-  static_assert(AH == 3 || AH == 6, "the step loop below is unrolled by hand for 3 or 6 landing buffers");
+  static_assert(WGB_AHEAD == 3, "the step loop below is unrolled by hand for 3 landing buffers");
   constexpr int NS = NI + NO;  // staged slices per step
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, c = lane & 15;
   // the loader's part of a step: slice sl = tid >> 5 (if < NS), feature f = (tid >> 1) & 15, rows
@@ -964,9 +929,9 @@ __device__ __forceinline__ void wgb_block(const int ld, const WgLayer Ly, int lo
     src = base + (size_t)f * ld + 8 * h;
   }
   const int nsteps = (hi - lo) / 16;  // chunks are multiples of 16 rows
-  // landing registers of the next AH steps (named, not an array: an array passed by reference
+  // landing registers of the next WGB_AHEAD steps (named, not an array: an array passed by reference
   // went to scratch)
-  float4 r0a, r0b, r1a, r1b, r2a, r2b, r3a, r3b, r4a, r4b, r5a, r5b;
+  float4 r0a, r0b, r1a, r1b, r2a, r2b;
   // clamped, branch-free loads (a past-the-end or non-loader load rereads a valid address; unused)
   const float* src_c = loader ? src : Ly.RT;
   auto load = [&](float4& ra, float4& rb, int s) {
@@ -977,11 +942,6 @@ __device__ __forceinline__ void wgb_block(const int ld, const WgLayer Ly, int lo
   load(r0a, r0b, 0);
   load(r1a, r1b, 1);
   load(r2a, r2b, 2);
-  if constexpr (AH == 6) {
-    load(r3a, r3b, 3);
-    load(r4a, r4b, 4);
-    load(r5a, r5b, 5);
-  }
   // this wave's tiles: NI = 4 -> (w, 0..NO-1); NI = 1 -> (0, w)
   constexpr int NT = NI == 4 ? NO : 1;
   // accumulator chains per tile: one when the wave has 4 tiles (their MFMAs interleave), one per
@@ -993,7 +953,7 @@ __device__ __forceinline__ void wgb_block(const int ld, const WgLayer Ly, int lo
 #pragma unroll
     for (int k = 0; k < NC; ++k) acc[t][k] = floatx4{0.f, 0.f, 0.f, 0.f};
   const int ai = NI == 4 ? wave : 0;
-  // one step from landing registers r: stage them, refill r with step s + AH, MFMAs
+  // one step from landing registers r: stage them, refill r with step s + WGB_AHEAD, MFMAs
   auto step = [&](float4& ra, float4& rb, int s) {
     float* st = stage + (s & 1) * WGB_STAGE;
     if (loader) {
@@ -1001,7 +961,7 @@ __device__ __forceinline__ void wgb_block(const int ld, const WgLayer Ly, int lo
       q[0] = ra;
       q[1] = rb;
     }
-    load(ra, rb, s + AH);
+    load(ra, rb, s + WGB_AHEAD);
     __syncthreads();
     // operands: lane (g, c) = feature c, rows 4g .. 4g + 3 of the step (the k_wgrad layout)
     const float4 av = *reinterpret_cast<const float4*>(st + ai * WGB_SLICE + c * WGB_FS + 4 * g);
@@ -1016,23 +976,13 @@ __device__ __forceinline__ void wgb_block(const int ld, const WgLayer Ly, int lo
     }
   };
   int s = 0;
-  for (; s + AH <= nsteps; s += AH) {
+  for (; s + WGB_AHEAD <= nsteps; s += WGB_AHEAD) {
     step(r0a, r0b, s);
     step(r1a, r1b, s + 1);
     step(r2a, r2b, s + 2);
-    if constexpr (AH == 6) {
-      step(r3a, r3b, s + 3);
-      step(r4a, r4b, s + 4);
-      step(r5a, r5b, s + 5);
-    }
   }
   if (s < nsteps) step(r0a, r0b, s);
   if (s + 1 < nsteps) step(r1a, r1b, s + 1);
-  if constexpr (AH == 6) {
-    if (s + 2 < nsteps) step(r2a, r2b, s + 2);
-    if (s + 3 < nsteps) step(r3a, r3b, s + 3);
-    if (s + 4 < nsteps) step(r4a, r4b, s + 4);
-  }
   // tile sums (four k-phase chains: (c0 + c1) + (c2 + c3)), straight to the slab
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
@@ -1053,7 +1003,6 @@ __device__ __forceinline__ void wgb_block(const int ld, const WgLayer Ly, int lo
 // block (j = b / 8) takes item perm[j / cpx] of its chunk j % cpx — every XCD starts with the full
 // 4 x 4 blocks of all its chunks, one per CU, before the lighter items fill in (with the work dealt
 // chunk-major, two heavy items could share a CU's matrix cores while others idled).
-template <int AH>
 __device__ __forceinline__ void wgrad_big_body(const int blk, const WgArgs& a, float* __restrict__ slab, int xcd,
                                                unsigned long long* sig_p, unsigned long long sig_v, float* stage) {
   if (sig_p && blk == 0 && threadIdx.x == 0)  // write-after-read order only: relaxed
@@ -1081,9 +1030,9 @@ __device__ __forceinline__ void wgrad_big_body(const int blk, const WgArgs& a, f
     const int it0 = (rem / nbo) * WG_BLK, ot0 = (rem % nbo) * WG_BLK;
     const int ni = min(WG_BLK, Ly.IT - it0), no = min(WG_BLK, Ly.OT - ot0);
     const WgLayer lv{Ly.LT, Ly.RT, Ly.in, Ly.out, Ly.IT, Ly.OT, Ly.woff, Ly.boff};
-    if (ni == 4 && no == 4) wgb_block<4, 4, AH>(a.ld, lv, lo, hi, it0, ot0, out, stage);
-    else if (ni == 1 && no == 4) wgb_block<1, 4, AH>(a.ld, lv, lo, hi, it0, ot0, out, stage);
-    else if (ni == 4 && no == 1) wgb_block<4, 1, AH>(a.ld, lv, lo, hi, it0, ot0, out, stage);
+    if (ni == 4 && no == 4) wgb_block<4, 4>(a.ld, lv, lo, hi, it0, ot0, out, stage);
+    else if (ni == 1 && no == 4) wgb_block<1, 4>(a.ld, lv, lo, hi, it0, ot0, out, stage);
+    else if (ni == 4 && no == 1) wgb_block<4, 1>(a.ld, lv, lo, hi, it0, ot0, out, stage);
     // (the host checks that every block of the network has one of these shapes)
   } else {
     const int ot = (rem - nbi * nbo) * WG_BLK + wave;
@@ -1108,11 +1057,10 @@ __device__ __forceinline__ void wgrad_big_body(const int blk, const WgArgs& a, f
   }
 }
 
-template <int AH>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) k_wgrad_big(WgArgs a, float* __restrict__ slab, int xcd,
                                                    unsigned long long* sig_p, unsigned long long sig_v) {
   __shared__ __attribute__((aligned(16))) float stage[2 * WGB_STAGE];  // 20 KiB
-  wgrad_big_body<AH>(blockIdx.x, a, slab, xcd, sig_p, sig_v, stage);
+  wgrad_big_body(blockIdx.x, a, slab, xcd, sig_p, sig_v, stage);
 }
 
 // The pipelined PER loop's critic GEMM with the priority update of the same update in one grid:
@@ -1120,24 +1068,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))
 // per_update_run_body over the subtrees. Both need only the critic chain before them, and the next
 // sample needs both (the trees, and this stream's order). LDS: the GEMM's 20 KiB ring, the priority
 // update's 10 KiB in the same bytes.
-template <int AH>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8)))
 k_wgrad_big_per(WgArgs a, float* __restrict__ slab, int xcd, int nwg, PerRunArgs pa, int nroot) {
   static_assert(sizeof(PerRunLds) <= 2 * WGB_STAGE * sizeof(float), "LDS union");
   __shared__ __attribute__((aligned(16))) float stage[2 * WGB_STAGE];  // 20 KiB
-  if ((int)blockIdx.x < nwg) wgrad_big_body<AH>(blockIdx.x, a, slab, xcd, nullptr, 0, stage);
+  if ((int)blockIdx.x < nwg) wgrad_big_body(blockIdx.x, a, slab, xcd, nullptr, 0, stage);
   else per_update_run_body(blockIdx.x - nwg, nroot, pa, *reinterpret_cast<PerRunLds*>(stage));
 }
 
 // ---------------------------------------------------------------- Adam (+ packed refresh, soft update)
-struct AdamArgs {
-  double beta1, beta2, eps, tau;
-  double lr[5];
-  double bounds[4];
-  int which;  // 0 critic counter, 1 actor counter
-  int soft;
-};
-
 // write_packed for a weight W_l[i][o] whose layer and indices are known (no search, no division)
 __device__ __forceinline__ void write_packed_w(float4* pk4, const NetTopo& t, int l, int i, int o, float val) {
   float* pk = reinterpret_cast<float*>(pk4);
@@ -1395,20 +1334,6 @@ int launch_reduce(const float* slab, int nch, int P, float* out, hipStream_t st)
 // the order of k_wgrad (per chunk: the four 16-row wave spans, each a 4-MFMA chain from zero,
 // reduced ((p0 + p1) + p2) + p3; bias: 64-row groups, then shuffles over g) followed by k_adam's
 // chunk order, so results are bit-identical to the split path.
-struct AdamNet {
-  WgArgs wg;  // panels, rows, 64-row chunking (as k_wgrad)
-  NetTopo t;
-  const float* src;  // weights the step starts from (== nb for an in-place step)
-  float* nb;
-  float4* pk;
-  float* m;
-  float* v;
-  float* target;  // soft update (critic) or nullptr
-  float4* tpk;
-  AdamArgs ad;
-  int items;                    // weight tiles + bias tiles, all layers
-  int ioff[MAX_LAYERS + 1];     // first item of layer l: KT*OT weight tiles then OT bias tiles
-};
 
 // k_adam's per-parameter arithmetic (same ops, same order), values only
 __device__ __forceinline__ void adam_math(const AdamScalars& s, float g, float& mm, float& vv, float& th, float& tg) {
@@ -1686,23 +1611,21 @@ extern "C" int cacto_debug_actor_stamps(unsigned long long* out_h) {
 }
 #endif
 
-using namespace cacto;
-
-namespace {
+namespace cacto {
 
 // Samples per chain workgroup: 4-sample tiles (chain_q4.h) up to a padded batch of Q4_MAX_BP, so a
 // reference-size batch (64 / 128) spreads over 4x the workgroups; 16-sample tiles above. A function
 // of the batch only, so every update path of one batch size runs the same chain kernels
 // (bit-identical results). CACTO_Q4_MAX_BP overrides the bound (read once; benchmarks).
-inline int q4_max_bp() {
+int q4_max_bp() {
   static const int v = [] {
     const char* e = std::getenv("CACTO_Q4_MAX_BP");
     return e ? std::atoi(e) : 512;
   }();
   return v;
 }
-inline int chain_tile(int Bp) { return Bp <= q4_max_bp() ? Q4_TILE : CACTO_TILE; }
-inline int cu_count() {
+int chain_tile(int Bp) { return Bp <= q4_max_bp() ? Q4_TILE : CACTO_TILE; }
+int cu_count() {
   static const int cus = [] {
     int dev = 0, v = 0;
     return (hipGetDevice(&dev) == hipSuccess &&
@@ -1781,75 +1704,12 @@ inline int wg_chunk_big() {
 // chunk per wave, so longer chunks amortise its pipeline fill (r05, updates/s: DI B = 4096 — the actor's
 // 4096 rows — 12.97 k at 128 rows, 13.25 k at 256; car_park PER B = 4096 10.14 k / 9.86 k; 512 rows
 // 12.49 k); CACTO_WG_CHUNK overrides it above 1024 rows (read once; benchmarks).
-inline int wg_chunk(int rows) {
+int wg_chunk(int rows) {
   if (rows > 1024 && wg_chunk_big() > 0) return wg_chunk_big();
   return rows <= 1024 ? 64 : rows < 4096 ? 128 : 256;
 }
 
-struct Workspace {
-  GradBufs crit, act;
-  float* slab;    // critic weight-gradient slabs
-  float* slab_a;  // actor's (a separate region: cacto_update_n overlaps the two steps)
-  float* cshadow; // two more critic net buffers (cacto_update_n rotates the critic over three)
-  int32_t* pidx;  // cacto_update_n_per: sampled indices, a ring of five buffers of Bp
-  float* pisw;    // and the IS weights of the current update
-  int32_t* runs;  // the overlapped PER loop's per-subtree sample runs (2 x PER_RUN_SUB ints)
-  float* scal;  // y, V, Vt scratch (3 * Bp)
-  size_t bytes;
-  int Bp;
-};
-
-inline size_t align64(size_t n) { return (n + 63) / 64 * 64; }
-
-Workspace plan(const cacto_sys* sys, int B, char* base) {
-  Workspace w{};
-  const int Bp = (B + 15) / 16 * 16;
-  w.Bp = Bp;
-  const NetTopo& tc = sys->critic;
-  const NetTopo& ta = sys->actor;
-  size_t off = 0;
-  float* f = reinterpret_cast<float*>(base);
-  // critic panels (ld = 2Bp)
-  w.crit.ld = 2 * Bp;
-  w.crit.Bp = Bp;
-  size_t coff = 0;
-  for (int l = 0; l < tc.L; ++l) {
-    w.crit.LT[l] = f ? f + coff : nullptr;
-    coff += (size_t)16 * tc.KT[l] * w.crit.ld;
-    w.crit.RT[l] = f ? f + coff : nullptr;
-    coff += (size_t)16 * tc.OT[l] * w.crit.ld;
-  }
-  w.act.ld = Bp;
-  w.act.Bp = Bp;
-  size_t aoff = align64(coff);  // the actor panels follow the critic's (no aliasing, see slab_a)
-  for (int l = 0; l < ta.L; ++l) {
-    w.act.LT[l] = f ? f + aoff : nullptr;
-    aoff += (size_t)16 * ta.KT[l] * w.act.ld;
-    w.act.RT[l] = f ? f + aoff : nullptr;
-    aoff += (size_t)16 * ta.OT[l] * w.act.ld;
-  }
-  off = align64(aoff);
-  const int nch_a = ceil_div(Bp, wg_chunk(Bp));
-  const int nch_c = ceil_div(2 * Bp, wg_chunk(2 * Bp));  // Sobolev rows, or the plain half
-  w.slab = f ? f + off : nullptr;
-  off += align64((size_t)nch_c * tc.params);
-  w.slab_a = f ? f + off : nullptr;
-  off += align64((size_t)nch_a * ta.params);
-  w.cshadow = f ? f + off : nullptr;
-  off += 2 * align64((size_t)flat_span(tc) + (size_t)2 * tc.blocks * 256);
-  w.pidx = f ? reinterpret_cast<int32_t*>(f + off) : nullptr;
-  off += align64((size_t)5 * Bp);
-  w.pisw = f ? f + off : nullptr;
-  off += align64((size_t)Bp);
-  w.runs = f ? reinterpret_cast<int32_t*>(f + off) : nullptr;
-  off += align64((size_t)2 * PER_RUN_SUB);
-  w.scal = f ? f + off : nullptr;
-  off += align64((size_t)3 * Bp);
-  w.bytes = off * sizeof(float);
-  return w;
-}
-
-WgArgs wg_args(const NetTopo& t, const GradBufs& gb, int r_begin, int r_end, int bias_r0) {
+static WgArgs wg_args(const NetTopo& t, const GradBufs& gb, int r_begin, int r_end, int bias_r0) {
   WgArgs a{};
   a.nl = t.L;
   a.ld = gb.ld;
@@ -1908,9 +1768,9 @@ bool wgrad_big(const NetTopo& t, int rows) {
 }
 
 // the weight-gradient GEMM of one network into its slabs; returns the chunk count k_adam sums
-int launch_wgrad(const NetTopo& t, const GradBufs& gb, int r_begin, int r_end, int bias_r0, float* slab,
-                 hipStream_t st, int* nch, unsigned long long* sig_p = nullptr, unsigned long long sig_v = 0,
-                 const PerRunArgs* per_run = nullptr) {
+static int launch_wgrad(const NetTopo& t, const GradBufs& gb, int r_begin, int r_end, int bias_r0, float* slab,
+                        hipStream_t st, int* nch, unsigned long long* sig_p, unsigned long long sig_v,
+                        const PerRunArgs* per_run) {
   const WgArgs a = wg_args(t, gb, r_begin, r_end, bias_r0);
   // chunks grouped by XCD from 8 chunks on (CACTO_WG_XCD=0 / 1 forces it off / on; benchmarks)
   static const int forced = [] {
@@ -1919,31 +1779,30 @@ int launch_wgrad(const NetTopo& t, const GradBufs& gb, int r_begin, int r_end, i
   }();
   const int xcd = forced >= 0 ? forced : a.nch >= 8;
   const int grid = xcd ? 8 * ceil_div(a.nch, 8) * a.tpc : a.nch * a.tpc;
-  // k_wgrad_big's load lead in 16-row steps: 3, or 6 with CACTO_WGB_AHEAD=6 (same sums). Measured
-  // (updates/s, two runs each): DI B = 4096 13.41 / 13.38 k at 6 against 13.33 / 13.37 k at 3,
-  // manipulator B = 8192 8.29 / 8.26 k against 8.36 / 8.34 k — inside the pipeline the GEMM is not
-  // waiting on its loads, so the lighter form stays.
-  static const int ahead = [] {
-    const char* e = std::getenv("CACTO_WGB_AHEAD");
-    return e && std::atoi(e) == 6 ? 6 : 3;
-  }();
   if (per_run) {  // the PER loop's fused form (the caller checked wgrad_big and the tree's shape)
     const int nroot = (int)(per_run->cap / PER_RUN_SUB);
-    if (ahead == 3)
-      hipLaunchKernelGGL(k_wgrad_big_per<3>, dim3(grid + nroot), dim3(256), 0, st, a, slab, xcd, grid, *per_run, nroot);
-    else
-      hipLaunchKernelGGL(k_wgrad_big_per<6>, dim3(grid + nroot), dim3(256), 0, st, a, slab, xcd, grid, *per_run, nroot);
+    hipLaunchKernelGGL(k_wgrad_big_per, dim3(grid + nroot), dim3(256), 0, st, a, slab, xcd, grid, *per_run, nroot);
   } else if (wgrad_big(t, r_end - r_begin)) {
-    if (ahead == 3)
-      hipLaunchKernelGGL(k_wgrad_big<3>, dim3(grid), dim3(256), 0, st, a, slab, xcd, sig_p, sig_v);
-    else
-      hipLaunchKernelGGL(k_wgrad_big<6>, dim3(grid), dim3(256), 0, st, a, slab, xcd, sig_p, sig_v);
-  }
-  else
+    hipLaunchKernelGGL(k_wgrad_big, dim3(grid), dim3(256), 0, st, a, slab, xcd, sig_p, sig_v);
+  } else {
     hipLaunchKernelGGL(k_wgrad, dim3(grid), dim3(256), 0, st, a, slab, xcd, sig_p, sig_v);
+  }
   CACTO_CHECK_HIP(hipGetLastError());
   *nch = a.nch;
   return CACTO_OK;
+}
+
+// the critic's gradient rows: the Sobolev half [0, Bp) only with w_S != 0, the plain half [Bp, 2 Bp) always
+static int critic_r0(bool sobolev, const Workspace& w) { return sobolev ? 0 : w.Bp; }
+
+int launch_critic_wgrad(const cacto_sys* sys, bool sobolev, const Workspace& w, hipStream_t st,
+                        int* nch, const PerRunArgs* per_run) {
+  return launch_wgrad(sys->critic, w.crit, critic_r0(sobolev, w), 2 * w.Bp, w.Bp, w.slab, st, nch, nullptr, 0, per_run);
+}
+
+int launch_actor_wgrad(const cacto_sys* sys, const Workspace& w, hipStream_t st, int* nch, unsigned long long* sig_p,
+                       unsigned long long sig_v) {
+  return launch_wgrad(sys->actor, w.act, 0, w.Bp, 0, w.slab_a, st, nch, sig_p, sig_v, nullptr);
 }
 
 ChainScalars chain_scalars(const cacto_update_cfg* cfg, int B) {
@@ -1965,7 +1824,7 @@ ChainScalars chain_scalars(const cacto_update_cfg* cfg, int B) {
   return cs;
 }
 
-AdamArgs adam_args(const cacto_update_cfg* cfg, int which, int soft) {
+static AdamArgs adam_args(const cacto_update_cfg* cfg, int which, int soft) {
   AdamArgs a{};
   a.beta1 = cfg->beta1;
   a.beta2 = cfg->beta2;
@@ -1977,13 +1836,6 @@ AdamArgs adam_args(const cacto_update_cfg* cfg, int which, int soft) {
   a.which = which == CACTO_NET_CRITIC ? 0 : 1;
   a.soft = soft;
   return a;
-}
-
-int check_nets(const cacto_nets* n) {
-  CACTO_REQUIRE(n && n->actor_d && n->actor_m_d && n->actor_v_d && n->critic_d && n->critic_m_d && n->critic_v_d &&
-                    n->target_d && n->step_d,
-                "cacto_nets: null member");
-  return CACTO_OK;
 }
 
 int launch_critic_chain(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
@@ -2005,19 +1857,9 @@ int launch_critic_chain(const cacto_sys* sys, const cacto_nets* nets, const cact
   return CACTO_OK;
 }
 
-int launch_critic_chain_and_wgrad(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
-                                  const double* storage, const int32_t* idx, const float* isw, int B, float* y,
-                                  float* V, float* Vt, const Workspace& w, hipStream_t st, int* nch_out) {
-  if (int e = launch_critic_chain(sys, nets, cfg, storage, idx, isw, B, y, V, Vt, w, st)) return e;
-  const ChainScalars cs = chain_scalars(cfg, B);
-  const bool sob = cs.w_S != 0.f;
-  return launch_wgrad(sys->critic, w.crit, sob ? 0 : w.Bp, 2 * w.Bp, w.Bp, w.slab, st, nch_out);
-}
-
 int launch_actor_chain(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
                        const double* storage, const int32_t* idx, int B, const Workspace& w, hipStream_t st,
-                       const unsigned long long* wait_p = nullptr, unsigned long long wait_v = 0,
-                       int wait_at_start = 0) {
+                       const unsigned long long* wait_p, unsigned long long wait_v, int wait_at_start) {
   NetView Ac = cacto_make_view(sys, CACTO_NET_ACTOR, nets->actor_d);
   NetView C = cacto_make_view(sys, CACTO_NET_CRITIC, nets->critic_d);
   ChainScalars cs = chain_scalars(cfg, B);
@@ -2027,20 +1869,21 @@ int launch_actor_chain(const cacto_sys* sys, const cacto_nets* nets, const cacto
   return dispatch_nj<LaunchActorChain>(sys->host.p, sys, Ac, C, cs, storage, idx, B, w.act, nets->step_d, st);
 }
 
-int launch_actor_chain_and_wgrad(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
-                                 const double* storage, const int32_t* idx, int B, const Workspace& w, hipStream_t st,
-                                 int* nch_out) {
-  if (int e = launch_actor_chain(sys, nets, cfg, storage, idx, B, w, st)) return e;
-  return launch_wgrad(sys->actor, w.act, 0, w.Bp, 0, w.slab_a, st, nch_out);
+// the critic chain of one update and the actor chain of the one before as one grid (small batches)
+int launch_chain_pair(const cacto_sys* sys, const NetView& C, const NetView& Tg, const NetView& Ac,
+                      const ChainScalars& cs, const double* storage, const int32_t* idx_c, const float* isw,
+                      const int32_t* idx_a, int B, const Workspace& w, float* y, float* V, int32_t* step,
+                      hipStream_t st) {
+  return dispatch_nj<LaunchChainPair>(sys->host.p, sys, C, Tg, Ac, cs, storage, idx_c, isw, idx_a, B, w.crit, w.act, y,
+                                      V, step, st);
 }
 
 // src: the weights the step starts from (nullptr = in place; cacto_update_n steps the critic from one
 // buffer into the other)
 int launch_adam(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg, int which,
-                const float* slab, int nch, int soft, hipStream_t st, const float* src = nullptr,
-                const unsigned long long* wait_p = nullptr, unsigned long long wait_v = 0,
-                unsigned long long* sig_p = nullptr, unsigned long long sig_v = 0,
-                const PerSampleArgs* sample = nullptr, int thru = 0) {
+                const float* slab, int nch, int soft, hipStream_t st, const float* src,
+                const unsigned long long* wait_p, unsigned long long wait_v, unsigned long long* sig_p,
+                unsigned long long sig_v, const PerSampleArgs* sample, int thru) {
   const NetTopo& t = topo(sys, which);
   float* nb = which == CACTO_NET_CRITIC ? nets->critic_d : nets->actor_d;
   float* m = which == CACTO_NET_CRITIC ? nets->critic_m_d : nets->actor_m_d;
@@ -2085,10 +1928,11 @@ int launch_adam(const cacto_sys* sys, const cacto_nets* nets, const cacto_update
 // Sobolev half, actor: Bp) all fall in 64-row chunks; larger batches keep k_wgrad's split-K slabs
 // (many workgroups per tile) and k_adam. A function of B only, so every update path of one batch
 // size takes the same kernels (bit-identical results).
-inline bool fused_adam(int Bp) { return 2 * Bp <= 1024; }
+bool fused_adam(int Bp) { return 2 * Bp <= 1024; }
 
-AdamNet adam_net(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg, int which, const GradBufs& gb,
-                 int r_begin, int r_end, int bias_r0, int soft, const float* src, float* nb) {
+static AdamNet adam_net(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg, int which,
+                        const GradBufs& gb, int r_begin, int r_end, int bias_r0, int soft, const float* src,
+                        float* nb) {
   AdamNet n{};
   const NetTopo& t = topo(sys, which);
   n.wg = wg_args(t, gb, r_begin, r_end, bias_r0);
@@ -2115,8 +1959,7 @@ AdamNet adam_net(const cacto_sys* sys, const cacto_nets* nets, const cacto_updat
 
 AdamNet critic_adam_net(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg, const Workspace& w,
                         int soft, const float* src, float* nb) {
-  const bool sob = cfg->w_S != 0.0;
-  return adam_net(sys, nets, cfg, CACTO_NET_CRITIC, w.crit, sob ? 0 : w.Bp, 2 * w.Bp, w.Bp, soft, src, nb);
+  return adam_net(sys, nets, cfg, CACTO_NET_CRITIC, w.crit, critic_r0(cfg->w_S != 0.0, w), 2 * w.Bp, w.Bp, soft, src, nb);
 }
 
 AdamNet actor_adam_net(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg, const Workspace& w) {
@@ -2139,44 +1982,23 @@ int launch_wgrad_adam(const cacto_sys* sys, int mode, const AdamNet& n0, const A
   return CACTO_OK;
 }
 
-// critic step after its chain: GEMM + Adam (+ soft update) from src into nb
-int critic_step_tail(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg, const Workspace& w,
-                     hipStream_t st, const float* src, float* nb, const unsigned long long* wait_p = nullptr,
-                     unsigned long long wait_v = 0, unsigned long long* sig_p = nullptr, unsigned long long sig_v = 0,
-                     const PerRunArgs* per_run = nullptr, const PerSampleArgs* sample = nullptr, int thru = 0) {
-  const int soft = cfg->MC ? 0 : 1;
-  if (fused_adam(w.Bp)) return launch_wgrad_adam(sys, 0, critic_adam_net(sys, nets, cfg, w, soft, src, nb), nullptr,
-                                                 nets->step_d, st);
-  const bool sob = cfg->w_S != 0.0;
-  int nch = 0;
-  if (int e = launch_wgrad(sys->critic, w.crit, sob ? 0 : w.Bp, 2 * w.Bp, w.Bp, w.slab, st, &nch, nullptr, 0, per_run))
-    return e;
-  cacto_nets dst = *nets;
-  dst.critic_d = nb;
-  return launch_adam(sys, &dst, cfg, CACTO_NET_CRITIC, w.slab, nch, soft, st, src, wait_p, wait_v, sig_p, sig_v,
-                     sample, thru);
+int launch_soft(const cacto_sys* sys, const cacto_nets* nets, float tau, hipStream_t st) {
+  const NetTopo& t = sys->critic;
+  hipLaunchKernelGGL(k_soft, dim3(std::min((t.params + 255) / 256, 1024)), dim3(256), 0, st, t, nets->critic_d,
+                     nets->target_d, reinterpret_cast<float4*>(nets->target_d + flat_span(t)), (double)tau);
+  CACTO_CHECK_HIP(hipGetLastError());
+  return CACTO_OK;
 }
 
-// CACTO_PER_OVERLAP (default 1): the pipelined PER loop's priority update and next sample share the
-// critic GEMM's and Adam's launches (k_wgrad_big_per, k_adam_sample) instead of following them.
-bool per_overlap_on() {
-  static const bool v = [] {
-    const char* e = std::getenv("CACTO_PER_OVERLAP");
-    return !(e && e[0] == '0');
-  }();
-  return v;
+int launch_pipe_probe(unsigned long long* w, int role, hipStream_t st) {
+  hipLaunchKernelGGL(k_pipe_probe, dim3(1), dim3(64), 0, st, w, role);
+  CACTO_CHECK_HIP(hipGetLastError());
+  return CACTO_OK;
 }
 
+}  // namespace cacto
 
-int actor_step_tail(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg, const Workspace& w,
-                    hipStream_t st, unsigned long long* sig_p = nullptr, unsigned long long sig_v = 0) {
-  if (fused_adam(w.Bp)) return launch_wgrad_adam(sys, 1, actor_adam_net(sys, nets, cfg, w), nullptr, nets->step_d, st);
-  int nch = 0;
-  if (int e = launch_wgrad(sys->actor, w.act, 0, w.Bp, 0, w.slab_a, st, &nch, sig_p, sig_v)) return e;
-  return launch_adam(sys, nets, cfg, CACTO_NET_ACTOR, w.slab_a, nch, 0, st);
-}
-
-}  // namespace
+using namespace cacto;
 
 // k_wgrad_adam's XCD bins (see the kernel). Per layer the IT x OT weight tiles are cut into bi x bo
 // = 8 blocks (bi chosen so the blocks are as square as the tile grid allows), block k to bin k; a
@@ -2229,850 +2051,3 @@ int cacto_build_wgrad_adam_items(cacto_sys* sys) {
   return CACTO_OK;
 }
 
-extern "C" size_t cacto_workspace_bytes(const cacto_sys* sys, int B) {
-  if (!sys || B <= 0) return 0;
-  return plan(sys, B, nullptr).bytes;
-}
-
-#define CHECK_WS(ws, nbytes, B)                                                                   \
-  CACTO_REQUIRE((ws) != nullptr && (nbytes) >= plan(sys, (B), nullptr).bytes,                     \
-                "workspace too small: query cacto_workspace_bytes(sys, B)");                      \
-  CACTO_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "workspace must be 256-byte aligned")
-
-extern "C" int cacto_critic_grad(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
-                                 const double* storage_d, const int32_t* idx_d, const float* is_w_d, int B,
-                                 float* grad_d, float* y_d, float* V_d, float* Vt_d, void* workspace_d,
-                                 size_t workspace_bytes, void* stream) {
-  CACTO_REQUIRE(sys && cfg && storage_d && idx_d && grad_d && B > 0, "cacto_critic_grad: bad arguments");
-  if (int e = check_nets(nets)) return e;
-  CHECK_WS(workspace_d, workspace_bytes, B);
-  const Workspace w = plan(sys, B, static_cast<char*>(workspace_d));
-  hipStream_t st = as_stream(stream);
-  int nch = 0;
-  if (int e = launch_critic_chain_and_wgrad(sys, nets, cfg, storage_d, idx_d, is_w_d, B, y_d, V_d, Vt_d, w, st, &nch))
-    return e;
-  const int P = sys->critic.params;
-  if (int e = launch_reduce(w.slab, nch, P, grad_d, st)) return e;
-  return CACTO_OK;
-}
-
-extern "C" int cacto_actor_grad(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
-                                const double* storage_d, const int32_t* idx_d, int B, float* grad_d, void* workspace_d,
-                                size_t workspace_bytes, void* stream) {
-  CACTO_REQUIRE(sys && cfg && storage_d && idx_d && grad_d && B > 0, "cacto_actor_grad: bad arguments");
-  if (int e = check_nets(nets)) return e;
-  CHECK_WS(workspace_d, workspace_bytes, B);
-  const Workspace w = plan(sys, B, static_cast<char*>(workspace_d));
-  hipStream_t st = as_stream(stream);
-  int nch = 0;
-  if (int e = launch_actor_chain_and_wgrad(sys, nets, cfg, storage_d, idx_d, B, w, st, &nch)) return e;
-  const int P = sys->actor.params;
-  if (int e = launch_reduce(w.slab_a, nch, P, grad_d, st)) return e;
-  return CACTO_OK;
-}
-
-extern "C" int cacto_adam_step(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg, int which,
-                               const float* grad_d, int soft_update, void* stream) {
-  CACTO_REQUIRE(sys && cfg && grad_d && (which == CACTO_NET_ACTOR || which == CACTO_NET_CRITIC),
-                "cacto_adam_step: bad arguments");
-  if (int e = check_nets(nets)) return e;
-  return launch_adam(sys, nets, cfg, which, grad_d, 1, soft_update, as_stream(stream));
-}
-
-extern "C" int cacto_soft_update(const cacto_sys* sys, const cacto_nets* nets, float tau, void* stream) {
-  CACTO_REQUIRE(sys, "cacto_soft_update: bad arguments");
-  if (int e = check_nets(nets)) return e;
-  const NetTopo& t = sys->critic;
-  hipLaunchKernelGGL(k_soft, dim3(std::min((t.params + 255) / 256, 1024)), dim3(256), 0, as_stream(stream), t,
-                     nets->critic_d, nets->target_d, reinterpret_cast<float4*>(nets->target_d + flat_span(t)),
-                     (double)tau);
-  CACTO_CHECK_HIP(hipGetLastError());
-  return CACTO_OK;
-}
-
-extern "C" int cacto_update(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
-                            const double* storage_d, const int32_t* idx_d, const float* is_w_d, int B, float* y_d,
-                            float* V_d, float* Vt_d, void* workspace_d, size_t workspace_bytes, void* stream) {
-  CACTO_REQUIRE(sys && cfg && storage_d && idx_d && B > 0, "cacto_update: bad arguments");
-  if (int e = check_nets(nets)) return e;
-  CHECK_WS(workspace_d, workspace_bytes, B);
-  const Workspace w = plan(sys, B, static_cast<char*>(workspace_d));
-  hipStream_t st = as_stream(stream);
-  if (int e = launch_critic_chain(sys, nets, cfg, storage_d, idx_d, is_w_d, B, y_d, V_d, Vt_d, w, st)) return e;
-  if (int e = critic_step_tail(sys, nets, cfg, w, st, nullptr, nets->critic_d)) return e;
-  if (int e = launch_actor_chain(sys, nets, cfg, storage_d, idx_d, B, w, st)) return e;
-  return actor_step_tail(sys, nets, cfg, w, st);
-}
-
-// Data-parallel form of the paired schedule (update_pipeline_pair): per step, the gradients of the
-// critic step of update t and of the actor step of update t - 1 (either may be absent) go to one
-// flat buffer [critic P | actor P], the caller all-reduces it once (RCCL), then both Adam steps.
-namespace {
-// stage bit 0: the chain(s) and the critic's weight gradient; bit 1: the actor's weight gradient
-// (which reads only the actor chain's panels in the workspace)
-int pair_grads(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg, const double* storage_d,
-               const int32_t* idx_c_d, const float* is_w_d, const int32_t* idx_a_d, int B, float* grad_d, float* y_d,
-               float* V_d, void* workspace_d, size_t workspace_bytes, int stages, hipStream_t st) {
-  CHECK_WS(workspace_d, workspace_bytes, B);
-  const Workspace w = plan(sys, B, static_cast<char*>(workspace_d));
-  const int Pc = sys->critic.params, Pa = sys->actor.params;
-  if (stages & 2) {
-    if (!idx_a_d) return CACTO_OK;
-    int nch = 0;
-    if (int e = launch_wgrad(sys->actor, w.act, 0, w.Bp, 0, w.slab_a, st, &nch)) return e;
-    return launch_reduce(w.slab_a, nch, Pa, grad_d + Pc, st);
-  }
-  float* yb = y_d ? y_d : w.scal;
-  float* Vb = V_d ? V_d : w.scal + w.Bp;
-  if (idx_c_d && idx_a_d) {
-    const NetView C = cacto_make_view(sys, CACTO_NET_CRITIC, nets->critic_d);
-    const NetView Tg = cacto_make_view(sys, CACTO_NET_CRITIC, nets->target_d);
-    const NetView Ac = cacto_make_view(sys, CACTO_NET_ACTOR, nets->actor_d);
-    if (int e = dispatch_nj<LaunchChainPair>(sys->host.p, sys, C, Tg, Ac, chain_scalars(cfg, B), storage_d, idx_c_d,
-                                             is_w_d, idx_a_d, B, w.crit, w.act, yb, Vb, nets->step_d, st))
-      return e;
-  } else if (idx_c_d) {
-    if (int e = launch_critic_chain(sys, nets, cfg, storage_d, idx_c_d, is_w_d, B, yb, Vb, nullptr, w, st)) return e;
-  } else {
-    if (int e = launch_actor_chain(sys, nets, cfg, storage_d, idx_a_d, B, w, st)) return e;
-  }
-  if (idx_c_d) {
-    const bool sob = cfg->w_S != 0.0;
-    int nch = 0;
-    if (int e = launch_wgrad(sys->critic, w.crit, sob ? 0 : w.Bp, 2 * w.Bp, w.Bp, w.slab, st, &nch)) return e;
-    if (int e = launch_reduce(w.slab, nch, Pc, grad_d, st)) return e;
-  }
-  if (stages & 2) return pair_grads(sys, nets, cfg, storage_d, idx_c_d, is_w_d, idx_a_d, B, grad_d, y_d, V_d,
-                                    workspace_d, workspace_bytes, 2, st);
-  return CACTO_OK;
-}
-}  // namespace
-
-extern "C" int cacto_update_pair_grads(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
-                                       const double* storage_d, const int32_t* idx_c_d, const float* is_w_d,
-                                       const int32_t* idx_a_d, int B, float* grad_d, float* y_d, float* V_d,
-                                       void* workspace_d, size_t workspace_bytes, void* stream) {
-  CACTO_REQUIRE(sys && cfg && storage_d && grad_d && B > 0 && (idx_c_d || idx_a_d),
-                "cacto_update_pair_grads: bad arguments");
-  if (int e = check_nets(nets)) return e;
-  return pair_grads(sys, nets, cfg, storage_d, idx_c_d, is_w_d, idx_a_d, B, grad_d, y_d, V_d, workspace_d,
-                    workspace_bytes, 1 | 2, as_stream(stream));
-}
-
-extern "C" int cacto_update_pair_grads_stage(const cacto_sys* sys, const cacto_nets* nets,
-                                             const cacto_update_cfg* cfg, const double* storage_d,
-                                             const int32_t* idx_c_d, const float* is_w_d, const int32_t* idx_a_d,
-                                             int B, float* grad_d, float* y_d, float* V_d, void* workspace_d,
-                                             size_t workspace_bytes, int stage, void* stream) {
-  CACTO_REQUIRE(sys && cfg && storage_d && grad_d && B > 0 && (idx_c_d || idx_a_d) && (stage == 0 || stage == 1),
-                "cacto_update_pair_grads_stage: bad arguments");
-  if (int e = check_nets(nets)) return e;
-  return pair_grads(sys, nets, cfg, storage_d, idx_c_d, is_w_d, idx_a_d, B, grad_d, y_d, V_d, workspace_d,
-                    workspace_bytes, stage == 0 ? 1 : 2, as_stream(stream));
-}
-
-extern "C" int cacto_update_pair_apply(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
-                                       const float* grad_d, int critic, int actor, int soft_update, void* stream) {
-  CACTO_REQUIRE(sys && cfg && grad_d && (critic || actor), "cacto_update_pair_apply: bad arguments");
-  if (int e = check_nets(nets)) return e;
-  hipStream_t st = as_stream(stream);
-  if (critic)
-    if (int e = launch_adam(sys, nets, cfg, CACTO_NET_CRITIC, grad_d, 1, soft_update, st)) return e;
-  if (actor)
-    if (int e = launch_adam(sys, nets, cfg, CACTO_NET_ACTOR, grad_d + sys->critic.params, 1, 0, st)) return e;
-  return CACTO_OK;
-}
-
-// K consecutive updates (learn_and_update's loop with its minibatches drawn up front, RL.py:120-143)
-// as a two-stream pipeline. The critic step of update t+1 reads only the critic, the target and the
-// rows — never the actor — so it runs while the actor step of update t is still going:
-//   stream : critic chain(t) on C_t, wgrad, Adam(t): C_t -> C_{t+1} (+ soft target update)
-//   side   : [wait Adam(t)], actor chain(t) against C_{t+1}, wgrad, Adam(actor), [event]
-// The critic rotates over the caller's net buffer and two workspace copies (C_t in buffer t % 3),
-// so Adam(t) overwrites the buffer actor chain(t-3) read (and, with PER, the sampler of update t
-// the index buffer it read) — the only ordering the stream needs from the side stream: the event
-// of side iteration t-3, recorded after that iteration's Adam, normally long signalled. (With two
-// buffers the event had to follow the actor chain itself, and its record packet cost the side
-// stream — the critical one — a queue gap between the chain and its GEMM.) Every kernel sees the
-// same inputs as in K sequential cacto_update calls, so the results are bit-identical; the final
-// critic is copied back if it ended in a workspace buffer, and the side stream joins the caller's
-// stream before returning.
-namespace {
-// PER state of cacto_update_n_per (replay_buffer.py:139-218)
-struct PerArgs {
-  double *sum_tree, *min_tree;
-  int64_t cap, max_idx;
-  double beta, fresh, eps, alpha;
-  const double* uniforms;  // [K][B]
-  double *exp_counter, *max_priority;
-};
-
-// Whether the PER loop of this batch can take the overlapped form: the count deferred into the
-// priority update (large batches), a priority update at all (alpha != 0), 256-leaf subtrees whose
-// roots fit one workgroup, the large-batch critic GEMM and an Adam step with all chunks in flight.
-bool per_overlap_ok(const cacto_sys* sys, const cacto_update_cfg* cfg, const PerArgs* per, int B, const Workspace& w) {
-  if (!per || !per_overlap_on() || B < cacto_per_mw_min() || per->alpha == 0.0) return false;
-  if (per->cap < 2 * PER_RUN_SUB || per->cap > (int64_t)PER_RUN_SUB * PER_RUN_SUB || per->cap % PER_RUN_SUB) return false;
-  if (fused_adam(w.Bp)) return false;
-  const bool sob = cfg->w_S != 0.0;
-  const int r0 = sob ? 0 : w.Bp, r1 = 2 * w.Bp;
-  return wgrad_big(sys->critic, r1 - r0) && ceil_div(r1 - r0, wg_chunk(r1 - r0)) <= 64;
-}
-
-// The priority update of one PER step (RL.py:129-131). late_count: the sampler left its
-// exp_counter += 1 to this call (large batches), which applies it first, in the same launch. With
-// alpha == 0 the reference skips update_priorities (RL.py:130) — the count still happens.
-int per_priority_update(const PerArgs* per, const int32_t* idx, const float* y, const float* V, int B, bool late_count,
-                        hipStream_t st) {
-  if (per->alpha == 0.0) return late_count ? cacto_per_count_launch(idx, B, per->exp_counter, st) : CACTO_OK;
-  if (late_count)
-    return cacto_per_update_count(per->sum_tree, per->min_tree, per->cap, idx, y, V, per->exp_counter, per->fresh,
-                                  per->eps, per->alpha, per->max_priority, B, st);
-  return cacto_per_update(per->sum_tree, per->min_tree, per->cap, idx, y, V, per->exp_counter, per->fresh, per->eps,
-                          per->alpha, per->max_priority, B, st);
-}
-
-// Small batches (fused_adam): one stream, K + 1 steps. Step t runs the critic chain of update t
-// and the actor chain of update t - 1 as one grid (k_chain_pair), then both GEMM + Adam steps as
-// one k_wgrad_adam launch:
-//   critic(t) reads C_t, T_t (Adam of step t - 1 wrote them); actor(t-1) reads A_{t-1} and C_t —
-//   exactly what RL.py:104-109 gives it (the critic after its own update t - 1);
-//   Adam: C_t -> C_{t+1} (+ soft T), A_{t-1} -> A_t.
-// Every kernel sees the inputs of the sequential loop, so results are bit-identical, with no
-// cross-stream events and three launches per update (five with PER).
-int update_pipeline_pair(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
-                         const double* storage_d, const int32_t* idx_d, const PerArgs* per, int K, int B,
-                         const Workspace& w, hipStream_t st) {
-  float* const y = w.scal;
-  float* const V = w.scal + w.Bp;
-  const int soft = cfg->MC ? 0 : 1;
-  const ChainScalars cs = chain_scalars(cfg, B);
-  const NetView C = cacto_make_view(sys, CACTO_NET_CRITIC, nets->critic_d);
-  const NetView Tg = cacto_make_view(sys, CACTO_NET_CRITIC, nets->target_d);
-  const NetView Ac = cacto_make_view(sys, CACTO_NET_ACTOR, nets->actor_d);
-  const AdamNet cn = critic_adam_net(sys, nets, cfg, w, soft, nullptr, nets->critic_d);
-  const AdamNet an = actor_adam_net(sys, nets, cfg, w);
-  const bool late_count = per && B >= cacto_per_mw_min();  // exp_counter += 1 just before the priority update
-  const int32_t* idx_prev = nullptr;
-  for (int t = 0; t <= K; ++t) {
-    const int32_t* idx = nullptr;
-    const float* isw = nullptr;
-    if (t < K) {
-      idx = idx_d ? idx_d + (size_t)t * B : nullptr;
-      if (per) {
-        int32_t* pi = w.pidx + (size_t)(t & 1) * w.Bp;
-        if (int e = cacto_per_sample(per->sum_tree, per->min_tree, per->cap, per->max_idx, per->beta,
-                                     per->uniforms + (size_t)t * B, B, pi, w.pisw, late_count ? nullptr : per->exp_counter, st))
-          return e;
-        idx = pi;
-        isw = w.pisw;
-      }
-    }
-    if (t < K && t > 0) {
-      if (int e = dispatch_nj<LaunchChainPair>(sys->host.p, sys, C, Tg, Ac, cs, storage_d, idx, isw, idx_prev, B,
-                                               w.crit, w.act, y, V, nets->step_d, st))
-        return e;
-      if (int e = launch_wgrad_adam(sys, 2, cn, &an, nets->step_d, st)) return e;
-    } else if (t < K) {
-      if (int e = launch_critic_chain(sys, nets, cfg, storage_d, idx, isw, B, y, V, nullptr, w, st)) return e;
-      if (int e = launch_wgrad_adam(sys, 0, cn, nullptr, nets->step_d, st)) return e;
-    } else {
-      if (int e = launch_actor_chain(sys, nets, cfg, storage_d, idx_prev, B, w, st)) return e;
-      if (int e = launch_wgrad_adam(sys, 1, an, nullptr, nets->step_d, st)) return e;
-    }
-    if (per && t < K)
-      if (int e = per_priority_update(per, idx, y, V, B, late_count, st)) return e;
-    idx_prev = idx;
-  }
-  return CACTO_OK;
-}
-
-// The side stream and its events, created once per handle and published only when all exist.
-int ensure_side_stream(cacto_sys* ms) {
-  if (ms->side) return CACTO_OK;
-  hipStream_t side = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipError_t e = hipStreamCreateWithFlags(&side, hipStreamNonBlocking);
-  // device-scope events: every producer and consumer of these dependencies is a kernel on this device
-  const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
-  for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&ev[k], evf);
-  unsigned long long* sig = nullptr;
-  if (e == hipSuccess) e = hipMalloc(&sig, 8 * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMemset(sig, 0, 8 * sizeof(unsigned long long));
-  if (e != hipSuccess) {
-    if (sig) (void)hipFree(sig);
-    for (hipEvent_t x : ev)
-      if (x) (void)hipEventDestroy(x);
-    if (side) (void)hipStreamDestroy(side);
-    return hip_fail(e, "cacto_update_n: side stream / events / pipeline signal");
-  }
-  ms->pipe_sig = sig;
-  ms->pipe_seq = 0;
-  ms->ev_critic = ev[0];
-  ms->ev_actor[0] = ev[1];
-  ms->ev_actor[1] = ev[2];
-  ms->ev_actor[2] = ev[3];
-  ms->side = side;
-  return CACTO_OK;
-}
-
-// How the two streams of this call are ordered: true = device-side waits (the default), false = queue
-// markers (event record / wait). CACTO_PIPE_DEVWAIT=0 / 1 forces markers / device waits (read once;
-// A/B and the timeout test). Otherwise markers when kernels are serialized by the environment
-// (AMD_SERIALIZE_KERNEL, HIP_LAUNCH_BLOCKING) or when the handle's one-time concurrency probe failed
-// (k_pipe_probe; e.g. counter collection). Always markers while `st` is being captured into a graph:
-// the waits compare device counters with absolute targets baked into the launches, and a replayed
-// graph would find its targets already reached.
-int pipe_devwait(cacto_sys* ms, hipStream_t st, bool* out) {
-  static const int env = [] {
-    const char* e = std::getenv("CACTO_PIPE_DEVWAIT");
-    if (e) return std::atoi(e) != 0 ? 1 : 0;
-    const char* s1 = std::getenv("AMD_SERIALIZE_KERNEL");
-    const char* s2 = std::getenv("HIP_LAUNCH_BLOCKING");
-    if ((s1 && std::atoi(s1) != 0) || (s2 && std::atoi(s2) != 0)) return 0;
-    return -1;  // probe
-  }();
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  CACTO_CHECK_HIP(hipStreamIsCapturing(st, &cap));
-  if (cap != hipStreamCaptureStatusNone) {
-    *out = false;
-    return CACTO_OK;
-  }
-  if (env >= 0) {
-    *out = env == 1;
-    return CACTO_OK;
-  }
-  if (ms->pipe_probe < 0) {
-    // both probe kernels start after everything already queued on `st`; the side one first
-    unsigned long long* w = ms->pipe_sig;
-    CACTO_CHECK_HIP(hipMemsetAsync(w + 4, 0, 4 * sizeof(unsigned long long), st));
-    CACTO_CHECK_HIP(hipEventRecord(ms->ev_critic, st));
-    CACTO_CHECK_HIP(hipStreamWaitEvent(ms->side, ms->ev_critic, 0));
-    hipLaunchKernelGGL(k_pipe_probe, dim3(1), dim3(64), 0, ms->side, w, 0);
-    CACTO_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_pipe_probe, dim3(1), dim3(64), 0, st, w, 1);
-    CACTO_CHECK_HIP(hipGetLastError());
-    CACTO_CHECK_HIP(hipStreamSynchronize(ms->side));
-    CACTO_CHECK_HIP(hipStreamSynchronize(st));
-    unsigned long long ok[2] = {0, 0};
-    CACTO_CHECK_HIP(hipMemcpy(ok, w + 6, sizeof(ok), hipMemcpyDeviceToHost));
-    ms->pipe_probe = ok[0] && ok[1] ? 1 : 0;
-  }
-  *out = ms->pipe_probe == 1;
-  return CACTO_OK;
-}
-
-int update_pipeline_body(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
-                         const double* storage_d, const int32_t* idx_d, const PerArgs* per, int K, int B,
-                         const Workspace& w, hipStream_t st, int* cbuf, bool devwait);
-
-int update_pipeline(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg, const double* storage_d,
-                    const int32_t* idx_d, const PerArgs* per, int K, int B, const Workspace& w, hipStream_t st) {
-  cacto_sys* ms = const_cast<cacto_sys*>(sys);
-  std::lock_guard<std::mutex> lock(ms->pipe_mu);
-  if (int e = ensure_side_stream(ms)) return e;
-  if (!ms->latch_host) {
-    CACTO_CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&ms->latch_host), sizeof(unsigned long long),
-                                  hipHostMallocDefault));
-    *ms->latch_host = 0;
-  }
-  // a device-side wait of an earlier call timed out and nobody has collected it with
-  // cacto_pipeline_check (the Python layer does at the end of every learn_and_update and before
-  // every checkpoint save): refuse to build on results whose order cannot be trusted
-  if (*reinterpret_cast<volatile unsigned long long*>(ms->latch_host)) {
-    set_error("cacto_update_n: a device-side pipeline wait of an earlier call timed out (kernels serialized?); its "
-              "results are not trustworthy — collect it with cacto_pipeline_check, or run with CACTO_PIPE_DEVWAIT=0");
-    return CACTO_EINVAL;
-  }
-  bool devwait = false;
-  if (int e = pipe_devwait(ms, st, &devwait)) return e;
-  const NetTopo& tc = sys->critic;
-  const size_t nb_bytes = ((size_t)flat_span(tc) + (size_t)2 * tc.blocks * 256) * sizeof(float);
-  const size_t nb_stride = align64((size_t)flat_span(tc) + (size_t)2 * tc.blocks * 256);
-  CACTO_CHECK_HIP(hipMemcpyAsync(w.cshadow, nets->critic_d, nb_bytes, hipMemcpyDeviceToDevice, st));
-  CACTO_CHECK_HIP(hipMemcpyAsync(w.cshadow + nb_stride, nets->critic_d, nb_bytes, hipMemcpyDeviceToDevice, st));
-  CACTO_CHECK_HIP(hipEventRecord(ms->ev_critic, st));  // everything the caller queued before
-  CACTO_CHECK_HIP(hipStreamWaitEvent(ms->side, ms->ev_critic, 0));
-  // cbuf: the buffer (0 caller's, 1-2 workspace) holding the newest critic; on every exit, error or
-  // not, the side stream joins the caller's stream and the newest critic lands in the caller's buffer
-  int cbuf = 0;
-  const int err = update_pipeline_body(sys, nets, cfg, storage_d, idx_d, per, K, B, w, st, &cbuf, devwait);
-  CACTO_CHECK_HIP(hipEventRecord(ms->ev_critic, ms->side));
-  CACTO_CHECK_HIP(hipStreamWaitEvent(st, ms->ev_critic, 0));
-  // the timeout latch's host copy, read by cacto_pipeline_check after a synchronisation of `st`
-  if (devwait)
-    CACTO_CHECK_HIP(hipMemcpyAsync(ms->latch_host, ms->pipe_sig + 1, sizeof(unsigned long long),
-                                   hipMemcpyDeviceToHost, st));
-  if (cbuf)
-    CACTO_CHECK_HIP(hipMemcpyAsync(nets->critic_d, w.cshadow + (cbuf - 1) * nb_stride, nb_bytes,
-                                   hipMemcpyDeviceToDevice, st));
-  return err;
-}
-
-int update_pipeline_body(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
-                         const double* storage_d, const int32_t* idx_d, const PerArgs* per, int K, int B,
-                         const Workspace& w, hipStream_t st, int* cbuf, bool devwait) {
-  cacto_sys* ms = const_cast<cacto_sys*>(sys);
-  hipStream_t side = ms->side;
-  const size_t nb_stride = align64((size_t)flat_span(sys->critic) + (size_t)2 * sys->critic.blocks * 256);
-  float* const buf[3] = {nets->critic_d, w.cshadow, w.cshadow + nb_stride};
-  float* const y = w.scal;
-  float* const V = w.scal + w.Bp;
-  const bool late_count = per && B >= cacto_per_mw_min();  // exp_counter += 1 just before the priority update
-  // queue markers (devwait off): every other iteration with PER (car_park B = 4096: 9.04 k -> 9.36 k
-  // updates/s), every iteration without (manipulator B = 8192 lost 8 % to the tighter wait)
-  const bool every2 = per != nullptr;
-  // devwait: the critic stream's ordering against the side stream without queue markers — the
-  // actor's GEMM (the launch after each actor chain) publishes the count of finished actor chains on
-  // the device, and the critic's Adam(t) polls it (pipe_wait) before overwriting the buffer actor
-  // chain(t-3) read; the PER index ring has four buffers, so the sampler of update t overwrites the
-  // one actor chain(t-4) read, which Adam(t-1)'s wait covers. Measured r05 (1 MI355X, updates/s): DI
-  // B = 4096 12.3 k -> 12.7 k, car_park PER B = 4096 9.88 k -> 9.98 k, manipulator B = 8192 unchanged.
-  // ... and the side stream's wait on the critic's Adam too (devwait_actor): the critic's Adam writes
-  // the weights through to memory at agent scope and publishes after its stores completed, the actor
-  // chain polls relaxed just before its critic pass at s' (with PER at its start, before it gathers
-  // the sampled rows) — where that cannot starve the critic stream of CUs: 16-sample actor tiles (the
-  // q4 chains take no wait), at most one actor workgroup per CU (a CU holding one actor workgroup
-  // still fits a critic chain, GEMM or Adam workgroup beside it, so the critic stream always
-  // progresses). DI B = 4096 13.2-13.3 k -> 14.2-14.4 k updates/s (r05).
-  const bool devwait_actor = devwait && chain_tile(w.Bp) == CACTO_TILE && w.Bp / CACTO_TILE <= cu_count();
-  const int thru = devwait_actor ? 1 : 0;
-  unsigned long long* const sig = ms->pipe_sig;
-  // the overlapped PER form (per_overlap_ok): priority update t inside the critic GEMM's launch,
-  // sample t + 1 inside its Adam's; the index ring has five buffers (sample t + 1 runs in the launch
-  // after the Adam(t - 1) that waited for actor chain t - 4). Otherwise the sample and the priority
-  // update run on the critic stream between its launches.
-  const bool ovl = per && devwait && per_overlap_ok(sys, cfg, per, B, w);
-  const int nring = ovl ? 5 : devwait ? 4 : 3;
-  const int nroot = per ? (int)(per->cap / PER_RUN_SUB) : 0;
-  const unsigned long long base = ms->pipe_seq;
-  ms->pipe_seq = base + K;  // reserved up front: no later call's waits can be satisfied by this call's values
-  // test hook (tests/test_gpu_per_pipeline.py): CACTO_PIPE_FAULT_INJECT=1 gives the first device-side
-  // wait of the process an unreachable target, so it times out and latches (once per process)
-  static std::atomic<int> inject{[] {
-    const char* e = std::getenv("CACTO_PIPE_FAULT_INJECT");
-    return e && e[0] == '1' ? 1 : 0;
-  }()};
-  for (int t = 0; t < K; ++t) {
-    // actor chain(t-3) read the critic buffer Adam(t) writes and (PER) the index buffer of update t.
-    // every2: the side stream records only at even iterations and the critic waits at even t for
-    // side iteration t-2 (which covers t-3 here and at t+1) — half the queue markers on each stream
-    if (devwait) {
-    } else if (every2) {
-      if (t >= 2 && (t & 1) == 0) CACTO_CHECK_HIP(hipStreamWaitEvent(st, ms->ev_actor[((t - 2) >> 1) & 1], 0));
-    } else if (t >= 3) {
-      CACTO_CHECK_HIP(hipStreamWaitEvent(st, ms->ev_actor[t % 3], 0));
-    }
-    const int32_t* idx = idx_d + (size_t)t * B;
-    const float* isw = nullptr;
-    if (per) {
-      int32_t* pi = w.pidx + (size_t)(t % nring) * w.Bp;
-      if (ovl) {
-        if (t == 0) {  // the first sample, recording its runs; later ones run inside the Adam launch
-          CACTO_CHECK_HIP(hipMemsetAsync(w.runs, 0x7f, (size_t)nroot * sizeof(int32_t), st));
-          CACTO_CHECK_HIP(hipMemsetAsync(w.runs + nroot, 0, (size_t)nroot * sizeof(int32_t), st));
-          if (int e = cacto_per_sample_runs_launch(per->sum_tree, per->min_tree, per->cap, per->max_idx, per->beta,
-                                                   per->uniforms, B, pi, w.pisw, w.runs, st))
-            return e;
-        }
-      } else if (int e = cacto_per_sample(per->sum_tree, per->min_tree, per->cap, per->max_idx, per->beta,
-                                          per->uniforms + (size_t)t * B, B, pi, w.pisw,
-                                          late_count ? nullptr : per->exp_counter, st)) {
-        return e;
-      }
-      idx = pi;
-      isw = w.pisw;
-    }
-    cacto_nets cur = *nets, nxt = *nets;
-    cur.critic_d = buf[t % 3];
-    nxt.critic_d = buf[(t + 1) % 3];
-    if (int e = launch_critic_chain(sys, &cur, cfg, storage_d, idx, isw, B, y, V, nullptr, w, st)) return e;
-    const bool dw = devwait && t >= 3;
-    const unsigned long long wait_c = dw && inject.exchange(0) ? ~0ull : base + t - 2;
-    PerRunArgs pra{};
-    PerSampleArgs psa{};
-    if (ovl) {
-      pra = PerRunArgs{per->sum_tree, per->min_tree, per->cap, idx, y, V, per->exp_counter, per->max_idx,
-                       per->fresh, per->eps, per->alpha, per->max_priority, w.runs, nullptr};
-      if (t + 1 < K)
-        psa = PerSampleArgs{per->sum_tree, per->min_tree, per->cap, per->max_idx, per->beta,
-                            per->uniforms + (size_t)(t + 1) * B, B, w.pidx + (size_t)((t + 1) % nring) * w.Bp,
-                            w.pisw, nullptr, 0, w.runs};
-    }
-    if (int e = critic_step_tail(sys, nets, cfg, w, st, cur.critic_d, nxt.critic_d, dw ? sig : nullptr, wait_c,
-                                 devwait_actor ? sig : nullptr, base + t + 1, ovl ? &pra : nullptr,
-                                 ovl && t + 1 < K ? &psa : nullptr, thru))
-      return e;
-    *cbuf = (t + 1) % 3;
-    if (!devwait_actor) CACTO_CHECK_HIP(hipEventRecord(ms->ev_critic, st));
-    if (per && !ovl)
-      if (int e = per_priority_update(per, idx, y, V, B, late_count, st)) return e;
-    if (!devwait_actor) CACTO_CHECK_HIP(hipStreamWaitEvent(side, ms->ev_critic, 0));
-    if (int e = launch_actor_chain(sys, &nxt, cfg, storage_d, idx, B, w, side, devwait_actor ? sig + 2 : nullptr,
-                                   base + t + 1, per ? 1 : 0))
-      return e;
-    if (int e = actor_step_tail(sys, nets, cfg, w, side, devwait ? sig : nullptr, base + t + 1)) return e;
-    if (devwait) {
-    } else if (!every2) {
-      CACTO_CHECK_HIP(hipEventRecord(ms->ev_actor[t % 3], side));
-    } else if ((t & 1) == 0) {
-      CACTO_CHECK_HIP(hipEventRecord(ms->ev_actor[(t >> 1) & 1], side));
-    }
-  }
-  return CACTO_OK;
-}
-}  // namespace
-
-extern "C" int cacto_pipeline_status(const cacto_sys* sys, unsigned long long* out4_h) {
-  CACTO_REQUIRE(sys && out4_h, "cacto_pipeline_status: bad arguments");
-  for (int k = 0; k < 4; ++k) out4_h[k] = 0;
-  if (!sys->pipe_sig) return CACTO_OK;
-  CACTO_CHECK_HIP(hipDeviceSynchronize());
-  CACTO_CHECK_HIP(hipMemcpy(out4_h, sys->pipe_sig, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  out4_h[3] = sys->pipe_probe < 0 ? 0 : (unsigned long long)sys->pipe_probe + 1;
-  return CACTO_OK;
-}
-
-extern "C" int cacto_pipeline_check(cacto_sys* sys, void* stream) {
-  CACTO_REQUIRE(sys, "cacto_pipeline_check: bad arguments");
-  if (!sys->pipe_sig || !sys->latch_host) return CACTO_OK;
-  std::lock_guard<std::mutex> lock(sys->pipe_mu);
-  CACTO_CHECK_HIP(hipStreamSynchronize(as_stream(stream)));
-  volatile unsigned long long* lh = reinterpret_cast<volatile unsigned long long*>(sys->latch_host);
-  if (*lh == 0) return CACTO_OK;
-  // collected: clear both copies, so the handle's next calls run again
-  CACTO_CHECK_HIP(hipMemset(sys->pipe_sig + 1, 0, sizeof(unsigned long long)));
-  *lh = 0;
-  set_error("cacto_pipeline_check: a device-side wait of the two-stream update pipeline timed out since the last "
-            "check (kernels serialized?); the updates of that call ran without their cross-stream order and their "
-            "results are not trustworthy — rerun them with CACTO_PIPE_DEVWAIT=0");
-  return CACTO_EINVAL;
-}
-
-extern "C" int cacto_update_n(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
-                              const double* storage_d, const int32_t* idx_d, int K, int B, void* workspace_d,
-                              size_t workspace_bytes, void* stream) {
-  CACTO_REQUIRE(sys && cfg && storage_d && idx_d && B > 0 && K >= 0, "cacto_update_n: bad arguments");
-  if (int e = check_nets(nets)) return e;
-  CHECK_WS(workspace_d, workspace_bytes, B);
-  if (K == 0) return CACTO_OK;
-  const Workspace w = plan(sys, B, static_cast<char*>(workspace_d));
-  if (fused_adam(w.Bp)) return update_pipeline_pair(sys, nets, cfg, storage_d, idx_d, nullptr, K, B, w, as_stream(stream));
-  return update_pipeline(sys, nets, cfg, storage_d, idx_d, nullptr, K, B, w, as_stream(stream));
-}
-
-// learn_and_update with PER (RL.py:122-137) for K updates: sample (stratified, IS weights) ->
-// update -> priority update per step, the sampling and priority update on the critic's stream
-// (the next sample depends on them), pipelined with the actor steps as in cacto_update_n.
-extern "C" int cacto_update_n_per(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
-                                  const double* storage_d, double* sum_tree_d, double* min_tree_d, int64_t capacity,
-                                  int64_t max_idx, double beta, const double* uniforms_d, double* exp_counter_d,
-                                  double fresh_factor, double eps, double alpha, double* max_priority_d, int K, int B,
-                                  void* workspace_d, size_t workspace_bytes, void* stream) {
-  CACTO_REQUIRE(sys && cfg && storage_d && sum_tree_d && min_tree_d && uniforms_d && exp_counter_d &&
-                    max_priority_d && B > 0 && K >= 0,
-                "cacto_update_n_per: bad arguments");
-  if (int e = check_nets(nets)) return e;
-  CHECK_WS(workspace_d, workspace_bytes, B);
-  if (K == 0) return CACTO_OK;
-  const Workspace w = plan(sys, B, static_cast<char*>(workspace_d));
-  const PerArgs per{sum_tree_d, min_tree_d, capacity, max_idx, beta, fresh_factor, eps, alpha, uniforms_d,
-                    exp_counter_d, max_priority_d};
-  // small batches: the paired single-stream schedule with the sampling and priority update between
-  // steps (car_park B = 64 with the q4 chains: 21.1 k vs 19.8 k updates/s two-stream); larger
-  // batches keep the two-stream pipeline (the actor step beside the sampling / priority update)
-  if (fused_adam(w.Bp))
-    return update_pipeline_pair(sys, nets, cfg, storage_d, nullptr, &per, K, B, w, as_stream(stream));
-  return update_pipeline(sys, nets, cfg, storage_d, nullptr, &per, K, B, w, as_stream(stream));
-}
-
-// ---------------------------------------------------------------- data-parallel pipeline (RCCL)
-// The data-parallel learn_and_update (main.py:219-225 runs the reference's loop on one process; here
-// one process per GPU, the gradients all-reduced over xGMI). The K updates of a call run as the
-// two-stream pipeline of cacto_update_n with each network's exchange inside its own stream:
-//   stream : [PER: shard stats -> all-gather -> stratified sample over the union] critic chain(t) ->
-//            weight-gradient GEMM -> slab reduce -> all-reduce (comm 0) -> Adam(t) (+ soft target
-//            update) [-> PER priority update]
-//   side   : [marker: Adam(t)] actor chain(t) against C_{t+1} -> GEMM -> reduce -> all-reduce (comm 1)
-//            -> Adam
-// Every rank issues the same collectives in the same order on each communicator, one communicator
-// per stream, so neither stream's collectives can interleave with the other's. The streams are
-// ordered with queue markers (no device-side polls beside collectives that wait for other ranks).
-// The gradients are scaled by 1/B_global inside the chain kernels, so the exchange is a plain sum;
-// every rank applies the same Adam to the same sum, so the replicas stay bit-identical. With one
-// rank the all-reduce is the identity and the result equals cacto_update_n / the Python
-// dp_pipeline bit for bit (tests/test_gpu_dp.py). The host issues ~14 HIP / RCCL calls per update
-// (the Python loop of RL_AC issued ~10 ctypes calls and two torch.distributed collectives: ~160 us
-// of host time per update, more than the GPU's).
-#include <dlfcn.h>
-#include <rccl/rccl.h>
-
-namespace {
-// RCCL entry points of the copy already in the process (torch.distributed's, found by soname), else
-// the ROCm library: no link-time dependency, one RCCL instance per process.
-struct Rccl {
-  decltype(&ncclGetUniqueId) get_id = nullptr;
-  decltype(&ncclCommInitRank) init = nullptr;
-  decltype(&ncclCommDestroy) destroy = nullptr;
-  decltype(&ncclAllReduce) all_reduce = nullptr;
-  decltype(&ncclAllGather) all_gather = nullptr;
-  decltype(&ncclGetErrorString) err = nullptr;
-  bool ok = false;
-};
-const Rccl& rccl() {
-  static const Rccl r = [] {
-    Rccl x;
-    void* h = dlopen("librccl.so.1", RTLD_NOW | RTLD_NOLOAD);
-    if (!h) h = dlopen("librccl.so.1", RTLD_NOW);
-    if (!h) h = dlopen("/opt/rocm/lib/librccl.so.1", RTLD_NOW);
-    if (!h) return x;
-    x.get_id = reinterpret_cast<decltype(x.get_id)>(dlsym(h, "ncclGetUniqueId"));
-    x.init = reinterpret_cast<decltype(x.init)>(dlsym(h, "ncclCommInitRank"));
-    x.destroy = reinterpret_cast<decltype(x.destroy)>(dlsym(h, "ncclCommDestroy"));
-    x.all_reduce = reinterpret_cast<decltype(x.all_reduce)>(dlsym(h, "ncclAllReduce"));
-    x.all_gather = reinterpret_cast<decltype(x.all_gather)>(dlsym(h, "ncclAllGather"));
-    x.err = reinterpret_cast<decltype(x.err)>(dlsym(h, "ncclGetErrorString"));
-    x.ok = x.get_id && x.init && x.destroy && x.all_reduce && x.all_gather && x.err;
-    return x;
-  }();
-  return r;
-}
-
-int rccl_fail(ncclResult_t r, const char* what) {
-  set_error(std::string(what) + ": " + (rccl().err ? rccl().err(r) : "RCCL error"));
-  return CACTO_EHIP;
-}
-#define CACTO_CHECK_RCCL(call, what)            \
-  do {                                          \
-    const ncclResult_t r_ = (call);             \
-    if (r_ != ncclSuccess) return rccl_fail(r_, what); \
-  } while (0)
-
-int update_pipeline_dp_body(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
-                            const double* storage_d, const int32_t* idx_d, const PerArgs* per, int K, int B,
-                            const Workspace& w, hipStream_t st, int* cbuf) {
-  cacto_sys* ms = const_cast<cacto_sys*>(sys);
-  const Rccl& R = rccl();
-  ncclComm_t cc = static_cast<ncclComm_t>(ms->dp_comm[0]), ca = static_cast<ncclComm_t>(ms->dp_comm[1]);
-  hipStream_t side = ms->side;
-  const int Pc = sys->critic.params, Pa = sys->actor.params;
-  const size_t nb_stride = align64((size_t)flat_span(sys->critic) + (size_t)2 * sys->critic.blocks * 256);
-  float* const buf[3] = {nets->critic_d, w.cshadow, w.cshadow + nb_stride};
-  float* const y = w.scal;
-  float* const V = w.scal + w.Bp;
-  const bool sob = cfg->w_S != 0.0;
-  const int soft = cfg->MC ? 0 : 1;
-  // queue markers: every other iteration with PER, every iteration without (update_pipeline_body)
-  const bool every2 = per != nullptr;
-  // PER in the critic's GEMM and Adam launches (per_overlap_ok, as cacto_update_n_per): the priority
-  // update of update t inside the GEMM's launch, then this shard's statistics and their all-gather,
-  // and the sample of t + 1 (IS weights over the union) inside the Adam's launch; the index ring has
-  // five buffers (sample t + 1 overwrites the one actor chain t - 4 read, which the marker before
-  // update t - 1 or t covers). Otherwise the sample and the priority update run between the launches.
-  const bool ovl = per && per_overlap_ok(sys, cfg, per, B, w);
-  const int nring = ovl ? 5 : 3;
-  const int nroot = per ? (int)(per->cap / PER_RUN_SUB) : 0;
-  double* const stats = ms->dp_stats;       // [3] this shard
-  double* const shards = ms->dp_stats + 3;  // [world][3]
-  auto gather_stats = [&]() -> int {
-    if (int e = cacto_per_shard_stats(per->sum_tree, per->min_tree, per->max_idx, stats, st)) return e;
-    CACTO_CHECK_RCCL(R.all_gather(stats, shards, 3, ncclFloat64, cc, st), "ncclAllGather(PER shards)");
-    return CACTO_OK;
-  };
-  for (int t = 0; t < K; ++t) {
-    if (every2) {
-      if (t >= 2 && (t & 1) == 0) CACTO_CHECK_HIP(hipStreamWaitEvent(st, ms->ev_actor[((t - 2) >> 1) & 1], 0));
-    } else if (t >= 3) {
-      CACTO_CHECK_HIP(hipStreamWaitEvent(st, ms->ev_actor[t % 3], 0));
-    }
-    const int32_t* idx = idx_d + (size_t)t * B;
-    const float* isw = nullptr;
-    if (per) {
-      // replay_buffer.py:139-188 over the union of the ranks' shards: this shard's (sum, min, rows),
-      // all-gathered, then the stratified sample with IS weights against the union
-      int32_t* pi = w.pidx + (size_t)(t % nring) * w.Bp;
-      if (ovl) {
-        if (t == 0) {  // the first sample, recording its runs; later ones run inside the Adam launch
-          CACTO_CHECK_HIP(hipMemsetAsync(w.runs, 0x7f, (size_t)nroot * sizeof(int32_t), st));
-          CACTO_CHECK_HIP(hipMemsetAsync(w.runs + nroot, 0, (size_t)nroot * sizeof(int32_t), st));
-          if (int e = gather_stats()) return e;
-          if (int e = cacto_per_sample_runs_launch(per->sum_tree, per->min_tree, per->cap, per->max_idx, per->beta,
-                                                   per->uniforms, B, pi, w.pisw, w.runs, st, shards, ms->dp_world))
-            return e;
-        }
-      } else {
-        if (int e = gather_stats()) return e;
-        if (int e = cacto_per_sample_global(per->sum_tree, per->min_tree, per->cap, per->max_idx, per->beta,
-                                            per->uniforms + (size_t)t * B, B, shards, ms->dp_world, pi, w.pisw,
-                                            per->exp_counter, st))
-          return e;
-      }
-      idx = pi;
-      isw = w.pisw;
-    }
-    cacto_nets cur = *nets, nxt = *nets;
-    cur.critic_d = buf[t % 3];
-    nxt.critic_d = buf[(t + 1) % 3];
-    if (int e = launch_critic_chain(sys, &cur, cfg, storage_d, idx, isw, B, y, V, nullptr, w, st)) return e;
-    int nch = 0;
-    PerRunArgs pra{};
-    PerSampleArgs psa{};
-    if (ovl) {
-      // the trees after priority update t: the statistics sample t + 1 weighs against, written by the
-      // workgroup of the GEMM's launch that rebuilds the top of the trees (with one subtree, a launch)
-      pra = PerRunArgs{per->sum_tree, per->min_tree, per->cap, idx, y, V, per->exp_counter, per->max_idx,
-                       per->fresh, per->eps, per->alpha, per->max_priority, w.runs,
-                       t + 1 < K && nroot > 1 ? shards : nullptr, 3 * ms->dp_rank, 3 * ms->dp_world};
-      if (t + 1 < K)
-        psa = PerSampleArgs{per->sum_tree, per->min_tree, per->cap, per->max_idx, per->beta,
-                            per->uniforms + (size_t)(t + 1) * B, B, w.pidx + (size_t)((t + 1) % nring) * w.Bp,
-                            w.pisw, shards, ms->dp_world, w.runs};
-    }
-    if (int e = launch_wgrad(sys->critic, w.crit, sob ? 0 : w.Bp, 2 * w.Bp, w.Bp, w.slab, st, &nch, nullptr, 0,
-                             ovl ? &pra : nullptr))
-      return e;
-    if (ovl && t + 1 < K) {
-      if (nroot > 1)  // the table with this rank's words filled and the others zero: summed = gathered
-        CACTO_CHECK_RCCL(R.all_reduce(shards, shards, (size_t)3 * ms->dp_world, ncclFloat64, ncclSum, cc, st),
-                         "ncclAllReduce(PER shards)");
-      else if (int e = gather_stats())
-        return e;
-    }
-    if (int e = launch_reduce(w.slab, nch, Pc, ms->dp_gc, st)) return e;
-    CACTO_CHECK_RCCL(R.all_reduce(ms->dp_gc, ms->dp_gc, (size_t)Pc, ncclFloat32, ncclSum, cc, st),
-                     "ncclAllReduce(critic gradient)");
-    cacto_nets dst = *nets;
-    dst.critic_d = nxt.critic_d;
-    if (int e = launch_adam(sys, &dst, cfg, CACTO_NET_CRITIC, ms->dp_gc, 1, soft, st, cur.critic_d, nullptr, 0, nullptr,
-                            0, ovl && t + 1 < K ? &psa : nullptr))
-      return e;
-    *cbuf = (t + 1) % 3;
-    CACTO_CHECK_HIP(hipEventRecord(ms->ev_critic, st));
-    if (per && !ovl)
-      if (int e = per_priority_update(per, idx, y, V, B, false, st)) return e;
-    CACTO_CHECK_HIP(hipStreamWaitEvent(side, ms->ev_critic, 0));
-    if (int e = launch_actor_chain(sys, &nxt, cfg, storage_d, idx, B, w, side)) return e;
-    int ncha = 0;
-    if (int e = launch_wgrad(sys->actor, w.act, 0, w.Bp, 0, w.slab_a, side, &ncha)) return e;
-    if (int e = launch_reduce(w.slab_a, ncha, Pa, ms->dp_ga, side)) return e;
-    CACTO_CHECK_RCCL(R.all_reduce(ms->dp_ga, ms->dp_ga, (size_t)Pa, ncclFloat32, ncclSum, ca, side),
-                     "ncclAllReduce(actor gradient)");
-    if (int e = launch_adam(sys, nets, cfg, CACTO_NET_ACTOR, ms->dp_ga, 1, 0, side)) return e;
-    if (!every2) {
-      CACTO_CHECK_HIP(hipEventRecord(ms->ev_actor[t % 3], side));
-    } else if ((t & 1) == 0) {
-      CACTO_CHECK_HIP(hipEventRecord(ms->ev_actor[(t >> 1) & 1], side));
-    }
-  }
-  return CACTO_OK;
-}
-
-int update_pipeline_dp(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
-                       const double* storage_d, const int32_t* idx_d, const PerArgs* per, int K, int B,
-                       const Workspace& w, hipStream_t st) {
-  cacto_sys* ms = const_cast<cacto_sys*>(sys);
-  std::lock_guard<std::mutex> lock(ms->pipe_mu);
-  if (!ms->dp_comm[0] || !ms->dp_comm[1]) {
-    set_error("cacto_update_n_dp: no RCCL communicators on this handle (cacto_dp_attach)");
-    return CACTO_EINVAL;
-  }
-  if (int e = ensure_side_stream(ms)) return e;
-  const NetTopo& tc = sys->critic;
-  const size_t nb_bytes = ((size_t)flat_span(tc) + (size_t)2 * tc.blocks * 256) * sizeof(float);
-  const size_t nb_stride = align64((size_t)flat_span(tc) + (size_t)2 * tc.blocks * 256);
-  CACTO_CHECK_HIP(hipMemcpyAsync(w.cshadow, nets->critic_d, nb_bytes, hipMemcpyDeviceToDevice, st));
-  CACTO_CHECK_HIP(hipMemcpyAsync(w.cshadow + nb_stride, nets->critic_d, nb_bytes, hipMemcpyDeviceToDevice, st));
-  CACTO_CHECK_HIP(hipEventRecord(ms->ev_critic, st));
-  CACTO_CHECK_HIP(hipStreamWaitEvent(ms->side, ms->ev_critic, 0));
-  int cbuf = 0;
-  const int err = update_pipeline_dp_body(sys, nets, cfg, storage_d, idx_d, per, K, B, w, st, &cbuf);
-  CACTO_CHECK_HIP(hipEventRecord(ms->ev_critic, ms->side));
-  CACTO_CHECK_HIP(hipStreamWaitEvent(st, ms->ev_critic, 0));
-  if (cbuf)
-    CACTO_CHECK_HIP(hipMemcpyAsync(nets->critic_d, w.cshadow + (cbuf - 1) * nb_stride, nb_bytes,
-                                   hipMemcpyDeviceToDevice, st));
-  return err;
-}
-}  // namespace
-
-void cacto_dp_release(cacto_sys* sys) {
-  for (void*& c : sys->dp_comm) {
-    if (c && rccl().ok) (void)rccl().destroy(static_cast<ncclComm_t>(c));
-    c = nullptr;
-  }
-  if (sys->dp_gc) (void)hipFree(sys->dp_gc);
-  if (sys->dp_ga) (void)hipFree(sys->dp_ga);
-  if (sys->dp_stats) (void)hipFree(sys->dp_stats);
-  sys->dp_gc = sys->dp_ga = nullptr;
-  sys->dp_stats = nullptr;
-  sys->dp_rank = sys->dp_world = 0;
-}
-
-extern "C" int cacto_dp_unique_ids(void* out_h, int n) {
-  CACTO_REQUIRE(out_h && n >= 1 && n <= 16, "cacto_dp_unique_ids: bad arguments");
-  const Rccl& R = rccl();
-  CACTO_REQUIRE(R.ok, "cacto_dp_unique_ids: RCCL (librccl.so.1) not found");
-  for (int k = 0; k < n; ++k) {
-    ncclUniqueId id;
-    CACTO_CHECK_RCCL(R.get_id(&id), "ncclGetUniqueId");
-    std::memcpy(static_cast<char*>(out_h) + (size_t)k * sizeof(ncclUniqueId), &id, sizeof(ncclUniqueId));
-  }
-  return CACTO_OK;
-}
-
-extern "C" int cacto_dp_attach(cacto_sys* sys, const void* ids_h, int rank, int world) {
-  CACTO_REQUIRE(sys && ids_h && world >= 1 && rank >= 0 && rank < world, "cacto_dp_attach: bad arguments");
-  const Rccl& R = rccl();
-  CACTO_REQUIRE(R.ok, "cacto_dp_attach: RCCL (librccl.so.1) not found");
-  std::lock_guard<std::mutex> lock(sys->pipe_mu);
-  cacto_dp_release(sys);
-  for (int k = 0; k < 2; ++k) {
-    ncclUniqueId id;
-    std::memcpy(&id, static_cast<const char*>(ids_h) + (size_t)k * sizeof(ncclUniqueId), sizeof(ncclUniqueId));
-    ncclComm_t c = nullptr;
-    CACTO_CHECK_RCCL(R.init(&c, world, id, rank), "ncclCommInitRank");
-    sys->dp_comm[k] = c;
-  }
-  CACTO_CHECK_HIP(hipMalloc(&sys->dp_gc, sizeof(float) * sys->critic.params));
-  CACTO_CHECK_HIP(hipMalloc(&sys->dp_ga, sizeof(float) * sys->actor.params));
-  CACTO_CHECK_HIP(hipMalloc(&sys->dp_stats, sizeof(double) * 3 * (world + 1)));
-  sys->dp_rank = rank;
-  sys->dp_world = world;
-  return CACTO_OK;
-}
-
-extern "C" int cacto_dp_detach(cacto_sys* sys) {
-  CACTO_REQUIRE(sys, "cacto_dp_detach: bad arguments");
-  std::lock_guard<std::mutex> lock(sys->pipe_mu);
-  if (sys->side) CACTO_CHECK_HIP(hipStreamSynchronize(sys->side));
-  cacto_dp_release(sys);
-  return CACTO_OK;
-}
-
-extern "C" int cacto_update_n_dp(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
-                                 const double* storage_d, const int32_t* idx_d, int K, int B, void* workspace_d,
-                                 size_t workspace_bytes, void* stream) {
-  CACTO_REQUIRE(sys && cfg && storage_d && idx_d && B > 0 && K >= 0, "cacto_update_n_dp: bad arguments");
-  if (int e = check_nets(nets)) return e;
-  CHECK_WS(workspace_d, workspace_bytes, B);
-  if (K == 0) return CACTO_OK;
-  const Workspace w = plan(sys, B, static_cast<char*>(workspace_d));
-  return update_pipeline_dp(sys, nets, cfg, storage_d, idx_d, nullptr, K, B, w, as_stream(stream));
-}
-
-extern "C" int cacto_update_n_per_dp(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
-                                     const double* storage_d, double* sum_tree_d, double* min_tree_d, int64_t capacity,
-                                     int64_t max_idx, double beta, const double* uniforms_d, double* exp_counter_d,
-                                     double fresh_factor, double eps, double alpha, double* max_priority_d, int K,
-                                     int B, void* workspace_d, size_t workspace_bytes, void* stream) {
-  CACTO_REQUIRE(sys && cfg && storage_d && sum_tree_d && min_tree_d && uniforms_d && exp_counter_d &&
-                    max_priority_d && B > 0 && K >= 0,
-                "cacto_update_n_per_dp: bad arguments");
-  if (int e = check_nets(nets)) return e;
-  CHECK_WS(workspace_d, workspace_bytes, B);
-  if (K == 0) return CACTO_OK;
-  const Workspace w = plan(sys, B, static_cast<char*>(workspace_d));
-  const PerArgs per{sum_tree_d, min_tree_d, capacity, max_idx, beta, fresh_factor, eps, alpha, uniforms_d,
-                    exp_counter_d, max_priority_d};
-  return update_pipeline_dp(sys, nets, cfg, storage_d, nullptr, &per, K, B, w, as_stream(stream));
-}

@@ -805,7 +805,7 @@ extern "C" int cacto_debug_per_stamps(unsigned long long* out_h) {  // [64][8], 
 }
 #endif
 
-// The fused PER loop's first sample (learn_kernels.hip): k_per_sample_runs, recording the per-subtree
+// The fused PER loop's first sample (learn_host.hip, per_first_sample): k_per_sample_runs, recording the per-subtree
 // runs (runs_d: 2 cap / PER_RUN_SUB ints, PER_RUN_EMPTY / 0 on entry).
 int cacto_per_sample_runs_launch(const double* sum_tree_d, const double* min_tree_d, int64_t capacity, int64_t max_idx,
                                  double beta, const double* uniforms_d, int B, int32_t* idx_d, float* is_w_d,

@@ -313,9 +313,12 @@ class RL_AC:
         idx_steps [K, B] int32 (device, kept alive by the caller). With `per_buffer` (a
         PrioritizedReplayBuffer) each step instead samples from `uniforms[k]` ([K, B] f64) and
         updates the priorities (learn_and_update with PER, RL.py:122-137).
-        Data parallel (RCCL process group): the graph holds the dp_pipeline loop — stage kernels,
-        the all-reduces on RCCL's stream and the Adam steps joined by stream waits — since nothing
-        in it waits on the host (gloo's collectives run on the host and cannot be captured)."""
+        Data parallel (RCCL process group): the graph holds one cacto_update_n_dp (with
+        `per_buffer`, cacto_update_n_per_dp) call — the library's two-stream pipeline with each
+        network's all-reduce inside its own stream, the streams ordered by queue markers — or, with
+        the native loop off (CACTO_DP_NATIVE=0), the dp_pipeline loop with the all-reduces on RCCL's
+        stream; nothing in either waits on the host (gloo's collectives run on the host and cannot
+        be captured)."""
         K = (uniforms if per_buffer is not None else idx_steps).shape[0]
         B = (uniforms if per_buffer is not None else idx_steps).shape[1]
         self.workspace(B)                       # allocated before the capture
