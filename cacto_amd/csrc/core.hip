@@ -137,16 +137,44 @@ extern "C" int cacto_sys_create(const cacto_sys_params* params_h, const double* 
 }
 
 extern "C" int cacto_sys_set_critic_type(cacto_sys* sys, int critic_type) {
-  CACTO_REQUIRE(sys && (critic_type == 0 || critic_type == 1),
-                "cacto_sys_set_critic_type: 0 (sine) or 1 (sine-elu); the elu / relu critics are not built");
+  CACTO_REQUIRE(sys && critic_type >= 0 && critic_type <= 2,
+                "cacto_sys_set_critic_type: 0 (sine), 1 (sine-elu) or 2 (elu); the relu critic is not built");
 #ifndef CACTO_CRITIC_ELU
-  // the elu layers are compiled into the kernels only in the CACTO_CRITIC_ELU build
-  // (cacto_amd/libcacto_hip_sine_elu.so): a runtime branch in the chain kernels' epilogues cost the
-  // sine critic 4-7 % of its B = 4096 update rate
-  CACTO_REQUIRE(critic_type == 0, "cacto_sys_set_critic_type: critic_type 'sine-elu' needs the CACTO_CRITIC_ELU build "
+  // the sine-elu critic's elu layers are compiled into the sine kernels only in the CACTO_CRITIC_ELU
+  // build (cacto_amd/libcacto_hip_sine_elu.so): a runtime branch in the chain kernels' epilogues cost
+  // the sine critic 4-7 % of its B = 4096 update rate. The elu critic (2) has kernels of its own
+  // (elu_kernels.hip) in every build.
+  CACTO_REQUIRE(critic_type != 1, "cacto_sys_set_critic_type: critic_type 'sine-elu' needs the CACTO_CRITIC_ELU build "
                                   "(CACTO_HIP_LIB=cacto_amd/libcacto_hip_sine_elu.so)");
 #endif
-  sys->critic.act = critic_type == 1 ? 0xA : 0;  // hidden layers 1 and 3 elu
+  const cacto_sys_params& p = sys->host.p;
+  const cacto::NetTopo t = cacto::make_topo(CACTO_NET_CRITIC, p.nb_state, p.nb_action, critic_type);
+  if (t.params == sys->critic.params && t.out[0] == sys->critic.out[0]) {
+    sys->critic.act = t.act;  // same widths (sine <-> sine-elu): hidden layers 1 and 3 elu or not
+    return CACTO_OK;
+  }
+  // another shape: the topology and what cacto_sys_create derived from it (k_wgrad_adam's work lists).
+  // The caller holds no critic net buffer, workspace or captured graph of the old shape (their sizes
+  // come from cacto_mlp_netbuf_floats / cacto_workspace_bytes, which now answer for the new one).
+  CACTO_CHECK_HIP(hipDeviceSynchronize());
+  const cacto::NetTopo old = sys->critic;
+  int32_t* old_items[3];
+  int old_stride[3];
+  for (int m = 0; m < 3; ++m) {
+    old_items[m] = sys->wa_items[m], old_stride[m] = sys->wa_stride[m];
+    sys->wa_items[m] = nullptr;
+  }
+  sys->critic = t;
+  if (int rc = cacto_build_wgrad_adam_items(sys)) {
+    for (int m = 0; m < 3; ++m) {
+      if (sys->wa_items[m]) (void)hipFree(sys->wa_items[m]);
+      sys->wa_items[m] = old_items[m], sys->wa_stride[m] = old_stride[m];
+    }
+    sys->critic = old;
+    return rc;
+  }
+  for (int m = 0; m < 3; ++m)
+    if (old_items[m]) (void)hipFree(old_items[m]);
   return CACTO_OK;
 }
 

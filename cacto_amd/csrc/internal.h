@@ -45,6 +45,9 @@ namespace cacto {
 inline const NetTopo& topo(const cacto_sys* s, int net) { return net == CACTO_NET_ACTOR ? s->actor : s->critic; }
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline int64_t flat_span(const NetTopo& t) { return ((int64_t)t.params + 63) / 64 * 64; }
+// elu_kernels.hip: V (and dV/ds when dVdS is non-null) of the elu critic
+int launch_critic_forward_elu(const cacto_sys* sys, const NetView& N, const float* S, float* V, float* dVdS, int B,
+                              hipStream_t st);
 }  // namespace cacto
 
 cacto::NetView cacto_make_view(const cacto_sys* sys, int net, const float* netbuf);

@@ -83,7 +83,7 @@ struct Workspace {
 
 // Which kernel a batch takes (learn_kernels.hip): functions of the batch and the network only.
 int q4_max_bp();
-int chain_tile(int Bp);
+int chain_tile(const NetTopo& critic, int Bp);
 int cu_count();
 int wg_chunk(int rows);
 bool wgrad_big(const NetTopo& t, int rows);
@@ -119,5 +119,18 @@ int launch_wgrad_adam(const cacto_sys* sys, int mode, const AdamNet& n0, const A
                       hipStream_t st);
 int launch_soft(const cacto_sys* sys, const cacto_nets* nets, float tau, hipStream_t st);
 int launch_pipe_probe(unsigned long long* w, int role, hipStream_t st);
+
+// elu_kernels.hip: the chain kernels of a handle whose critic is the elu network (is_elu_topo);
+// launch_critic_chain / launch_actor_chain / launch_chain_pair hand over to them
+int launch_critic_chain_elu(const cacto_sys* sys, const NetView& C, const NetView& Tg, const ChainScalars& cs,
+                            const double* storage, const int32_t* idx, const float* isw, int B, const GradBufs& gb,
+                            float* y, float* V, float* Vt, int32_t* step, hipStream_t st);
+int launch_actor_chain_elu(const cacto_sys* sys, const NetView& Ac, const NetView& C, const ChainScalars& cs,
+                           const double* storage, const int32_t* idx, int B, const GradBufs& gb, int32_t* step,
+                           hipStream_t st);
+int launch_chain_pair_elu(const cacto_sys* sys, const NetView& C, const NetView& Tg, const NetView& Ac,
+                          const ChainScalars& cs, const double* storage, const int32_t* idx_c, const float* isw,
+                          const int32_t* idx_a, int B, const GradBufs& gbc, const GradBufs& gba, float* y, float* V,
+                          int32_t* step, hipStream_t st);
 
 }  // namespace cacto

@@ -524,7 +524,7 @@ int update_pipeline_body(const cacto_sys* sys, const cacto_nets* nets, const cac
   // q4 chains take no wait), at most one actor workgroup per CU (a CU holding one actor workgroup
   // still fits a critic chain, GEMM or Adam workgroup beside it, so the critic stream always
   // progresses). DI B = 4096 13.2-13.3 k -> 14.2-14.4 k updates/s (r05).
-  const bool devwait_actor = devwait && chain_tile(w.Bp) == CACTO_TILE && w.Bp / CACTO_TILE <= cu_count();
+  const bool devwait_actor = devwait && chain_tile(sys->critic, w.Bp) == CACTO_TILE && w.Bp / CACTO_TILE <= cu_count();
   const int thru = devwait_actor ? 1 : 0;
   unsigned long long* const sig = ms->pipe_sig;
   // the overlapped PER form (per_overlap_ok): priority update t inside the critic GEMM's launch,

@@ -36,11 +36,16 @@ struct NetTopo {
   int act;                // critic: bit l set = hidden layer l is elu (critic_type 'sine-elu'), else sine
 };
 
-inline NetTopo make_topo(int net, int ns, int na) {
+// critic_type (cacto_sys_set_critic_type): 0 sine, 1 sine-elu — both 64, 64, 128, 128 wide — and 2
+// elu, 16, 32, 256, 256 wide with every hidden layer elu (NeuralNetwork.py:65-78)
+inline NetTopo make_topo(int net, int ns, int na, int critic_type = 0) {
   NetTopo t{};
   const int actor_dims[4] = {ns, 256, 256, na};
-  const int critic_dims[6] = {ns, 64, 64, 128, 128, 1};
+  const int sine_dims[6] = {ns, 64, 64, 128, 128, 1};
+  const int elu_dims[6] = {ns, 16, 32, 256, 256, 1};
+  const int* critic_dims = critic_type == 2 ? elu_dims : sine_dims;
   const int* d = net == CACTO_NET_ACTOR ? actor_dims : critic_dims;
+  if (net == CACTO_NET_CRITIC) t.act = critic_type == 2 ? 0xF : critic_type == 1 ? 0xA : 0;
   t.L = net == CACTO_NET_ACTOR ? ACTOR_LAYERS : CRITIC_LAYERS;
   int off = 0, blk = 0;
   for (int l = 0; l < t.L; ++l) {
@@ -59,6 +64,8 @@ inline NetTopo make_topo(int net, int ns, int na) {
   t.params = off;
   return t;
 }
+// the elu critic's shape: its kernels are elu_kernels.hip's, picked at the launch_* level
+inline bool is_elu_topo(const NetTopo& t) { return t.L == CRITIC_LAYERS && t.out[0] == 16; }
 
 // Device view of one network: flat Keras params (biases, W5 column) + packed fragments.
 struct NetView {

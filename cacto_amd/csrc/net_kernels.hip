@@ -150,6 +150,7 @@ extern "C" int cacto_critic_input_grad(const cacto_sys* sys, const float* critic
   CACTO_REQUIRE(sys && critic_netbuf_d && S_d && B >= 0, "cacto_critic_input_grad: bad arguments");
   if (B == 0) return CACTO_OK;
   NetView v = cacto_make_view(sys, CACTO_NET_CRITIC, critic_netbuf_d);
+  if (is_elu_topo(sys->critic)) return launch_critic_forward_elu(sys, v, S_d, V_d, dVdS_d, B, as_stream(stream));
   hipLaunchKernelGGL(k_critic_forward, dim3(ceil_div(B, CACTO_TILE)), dim3(CACTO_THREADS), 0, as_stream(stream),
                      sys->dev, v, S_d, V_d, dVdS_d, B);
   CACTO_CHECK_HIP(hipGetLastError());

@@ -17,10 +17,12 @@ ACTOR, CRITIC = L.CACTO_NET_ACTOR, L.CACTO_NET_CRITIC
 SINE_ELU = ("sine", "elu", "sine", "elu")  # critic_type 'sine-elu' hidden layers (NeuralNetwork.py:80-93)
 
 
-def layer_shapes(kind, ns, na):
+def layer_shapes(kind, ns, na, critic_type="sine"):
     if kind == ACTOR:  # NeuralNetwork.py:51-63
         dims = [ns, 256, 256, na]
-    else:              # NeuralNetwork.py:95-108 (critic_type 'sine', every shipped config)
+    elif critic_type == "elu":  # NeuralNetwork.py:65-78
+        dims = [ns, 16, 32, 256, 256, 1]
+    else:              # NeuralNetwork.py:80-108 ('sine', every shipped config, and 'sine-elu')
         dims = [ns, 64, 64, 128, 128, 1]
     shapes = []
     for i, o in zip(dims[:-1], dims[1:]):
@@ -46,6 +48,13 @@ LAYER_NAMES_SINE_ELU = {
     "target": ["sinusodial_representation_dense_2", "dense_6", "sinusodial_representation_dense_3", "dense_7",
                "dense_8"],
 }
+# the elu critic is all Dense layers (NeuralNetwork.py:65-78): they continue the actor's dense_* count
+LAYER_NAMES_ELU = {
+    "actor": LAYER_NAMES["actor"],
+    "critic": ["dense_3", "dense_4", "dense_5", "dense_6", "dense_7"],
+    "target": ["dense_8", "dense_9", "dense_10", "dense_11", "dense_12"],
+}
+LAYER_NAMES_BY_TYPE = {"sine": LAYER_NAMES, "sine-elu": LAYER_NAMES_SINE_ELU, "elu": LAYER_NAMES_ELU}
 
 
 class Net:
@@ -55,12 +64,13 @@ class Net:
         self.sys = sys
         self.kind = kind
         self.role = role or ("actor" if kind == ACTOR else "critic")
-        self.shapes = layer_shapes(kind, sys.ns, sys.na)
+        # the critic's shape and activations belong to the system handle: a critic net fixes them
+        # (System.set_critic_type)
+        self.critic_type = getattr(sys, "critic_type", "sine") if kind == CRITIC else None
+        self.shapes = layer_shapes(kind, sys.ns, sys.na, self.critic_type)
         self.P = sys.param_count(kind)
         assert self.P == sum(int(np.prod(s)) for s in self.shapes)
         self.buf = torch.zeros(sys.netbuf_floats(kind), dtype=torch.float32, device=DEVICE)
-        # the critic activations belong to the system handle: a critic net fixes them (System.set_critic_type)
-        self.critic_type = getattr(sys, "critic_type", "sine") if kind == CRITIC else None
         if kind == CRITIC:
             if getattr(sys, "critic_nets", None) is None:
                 import weakref
@@ -114,7 +124,7 @@ class Net:
         writer, cacto_amd/h5.py), else an .npz of the Keras-order arrays."""
         ws = self.get_weights()
         if str(path).endswith(".h5"):
-            names = (LAYER_NAMES_SINE_ELU if self.critic_type == "sine-elu" else LAYER_NAMES)[self.role]
+            names = LAYER_NAMES_BY_TYPE[self.critic_type or "sine"][self.role]
             h5.write_keras_weights(path, [(n, [(n + "/kernel:0", ws[2 * i]), (n + "/bias:0", ws[2 * i + 1])])
                                           for i, n in enumerate(names)])
         else:
@@ -135,7 +145,8 @@ def init_weights(kind, ns, na, rng, critic_acts=("sine",) * 4):
     U(+-sqrt(6/units)). `critic_acts`: the critic's hidden layers ('sine' SIREN layers, 'elu' Dense
     layers: NeuralNetwork.py:80-93)."""
     ws = []
-    shapes = layer_shapes(kind, ns, na)
+    all_elu = kind == CRITIC and tuple(critic_acts) == ("elu",) * 4  # the elu critic has its own widths
+    shapes = layer_shapes(kind, ns, na, "elu" if all_elu else "sine")
     for li in range(0, len(shapes), 2):
         fi, fo = shapes[li]
         siren = kind == CRITIC and li < 8 and critic_acts[li // 2] == "sine"
@@ -177,10 +188,16 @@ class NN:
         return net
 
     def create_critic_elu(self):
-        raise NotImplementedError("critic_type 'elu' (16, 32, 256, 256 wide) is not built; every shipped conf "
-                                  "uses 'sine' ('sine-elu' is built)")
+        """NeuralNetwork.py:65-78: Dense 16, 32, 256, 256 with elu, then Dense(1); Glorot-uniform kernels,
+        zero biases. The shape is a property of the system handle, as the activations are."""
+        self.sys.set_critic_type("elu")
+        net = Net(self.sys, CRITIC)
+        net.set_weights(init_weights(CRITIC, self.sys.ns, self.sys.na, self.rng, critic_acts=("elu",) * 4))
+        return net
 
-    create_critic_relu = create_critic_elu
+    def create_critic_relu(self):
+        raise NotImplementedError("critic_type 'relu' is not built (RL.py:66-76 never selects it); 'sine', "
+                                  "'sine-elu' and 'elu' are")
 
     # ---- NeuralNetwork.py:130-138 ----
     def eval(self, model, x):
@@ -226,8 +243,9 @@ class NN:
         """Workspace and a private optimizer-counter pair for the standalone gradient calls: the
         device gradient kernels advance `step_d` (the fused update's Keras iterations), which a
         bare compute_*_grad must not do to the learner's counters."""
-        if getattr(self, "_ws_B", 0) < B:
-            self._ws = torch.empty(self.sys.workspace_bytes(B) // 4 + 64, dtype=torch.float32, device=DEVICE)
+        nbytes = self.sys.workspace_bytes(B)  # depends on the critic's shape too
+        if getattr(self, "_ws_B", 0) < B or self._ws.numel() * 4 < nbytes:
+            self._ws = torch.empty(nbytes // 4 + 64, dtype=torch.float32, device=DEVICE)
             self._ws_B = B
             self._steps = torch.zeros(2, dtype=torch.int32, device=DEVICE)
         return self._ws, self._steps

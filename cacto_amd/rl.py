@@ -115,8 +115,8 @@ class RL_AC:
         """`weights`: optional dict {'actor', 'critic', 'target'} of Keras-order arrays (e.g. the
         .h5-derived fixtures) instead of fresh initialisers."""
         self.actor_model = self.NN.create_actor()
-        # RL.py:65-76 (critic_type: 'sine' in every shipped config; 'sine-elu' built; 'elu' / 'relu'
-        # raise NotImplementedError)
+        # RL.py:65-76 (critic_type: 'sine' in every shipped config; 'sine-elu' and 'elu' built; anything
+        # else is the reference's relu critic, which raises NotImplementedError)
         ctype = getattr(self.conf, "critic_type", "sine")
         create = {"sine": self.NN.create_critic_sine, "sine-elu": self.NN.create_critic_sine_elu,
                   "elu": self.NN.create_critic_elu}.get(ctype, self.NN.create_critic_relu)

@@ -121,10 +121,16 @@ int cacto_abi_version(void);
 /* joint_table_h: n_joints x CACTO_JOINT_COLS float64 (host), see cacto_amd/robots.py */
 int cacto_sys_create(const cacto_sys_params* params_h, const double* joint_table_h, cacto_sys** out);
 int cacto_sys_destroy(cacto_sys* sys);
-/* The critic's hidden activations (RL.py:65-76 critic_type): 0 = 'sine' (4 SIREN layers, the
- * default, every shipped config), 1 = 'sine-elu' (NeuralNetwork.py:80-93: sine, elu, sine, elu
- * layers of the same widths). Set before creating or updating critic networks of this handle; the
- * 'elu' and 'relu' critics (16, 32, 256, 256 wide) are not built (CACTO_EINVAL). */
+/* The critic network of this handle (RL.py:65-76 critic_type): 0 = 'sine' (4 SIREN layers 64, 64,
+ * 128, 128 wide, the default, every shipped config), 1 = 'sine-elu' (NeuralNetwork.py:80-93: sine,
+ * elu, sine, elu layers of the same widths; the CACTO_CRITIC_ELU build only), 2 = 'elu'
+ * (NeuralNetwork.py:65-78: Dense 16, 32, 256, 256 with elu, then Dense 1; 16 ns + 75,057 parameters,
+ * kernels of its own in every build). Set before creating or updating critic networks of this
+ * handle: 2 (and leaving 2) changes the critic's topology, so cacto_mlp_param_count,
+ * cacto_mlp_netbuf_floats and cacto_workspace_bytes answer for the new network from then on, and no
+ * critic net buffer, workspace or captured graph of the old one may be used after it (the call
+ * synchronises the device and rebuilds the handle's fused weight-gradient + Adam work lists). The
+ * 'relu' critic is not built (CACTO_EINVAL). */
 int cacto_sys_set_critic_type(cacto_sys* sys, int critic_type);
 
 /* ---------------------------------------------------------------- environment ------------ */
