@@ -53,6 +53,8 @@ int launch_critic_forward_elu(const cacto_sys* sys, const NetView& N, const floa
 cacto::NetView cacto_make_view(const cacto_sys* sys, int net, const float* netbuf);
 int cacto_const_dyn_init(cacto_sys* sys);  // SysDevice::cd_* of a prismatic-only chain (env_kernels.hip)
 int cacto_build_wgrad_adam_items(cacto_sys* sys);  // learn_kernels.hip
+// ddp_kernels.hip: the handle's grow-only device workspace (derivative records), at least `bytes`
+int cacto_ddp_workspace(cacto_sys* sys, size_t bytes, double** out);
 void cacto_dp_release(cacto_sys* sys);  // learn_host.hip: the RCCL communicators and buffers
 // replay_kernels.hip: batches from this size on take the multi-workgroup PER kernels; the update
 // pipelines (learn_host.hip) then issue the sample's exp_counter increment just before the priority update (its only

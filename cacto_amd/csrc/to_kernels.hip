@@ -1,0 +1,1104 @@
+// TO_System_Solve (TO.py:37-100) on the GPU: a batched iLQR on the reference's problem.
+//
+// The reference states one NLP per episode (CasADi + IPOPT, multiple shooting): minimise
+// sum_t cost(x_t, u_t; w_running) + cost(x_T; w_terminal) subject to x_{t+1} = simulate(x_t, u_t) and
+// the given x_0, with the control bounds as the penalty w_b (u/u_max)^10 inside the cost
+// (environment_TO.py:201-206). Apart from the dynamics it is unconstrained, so single shooting
+// with Gauss-Newton DDP works on exactly that problem:
+//   backward   Q_x = l_x + A^T V_x, Q_u = l_u + B^T V_x, Q_xx = l_xx + A^T V_xx A,
+//              Q_ux = B^T V_xx A, Q_uu = l_uu + B^T V_xx B (cost convention, l_xu = 0),
+//              Qbar_uu = Q_uu + mu I by Cholesky (a pivot <= 0: not positive definite, raise mu),
+//              k = -Qbar_uu^-1 Q_u, K = -Qbar_uu^-1 Q_ux,
+//              V_x = Q_x + K^T Q_uu k + K^T Q_u + Q_ux^T k,
+//              V_xx = Q_xx + K^T Q_uu K + K^T Q_ux + Q_ux^T K, symmetrised;
+//   forward    u_t = ubar_t + alpha k_t + K_t (x_t - xbar_t), x_{t+1} = env_simulate (float64), the
+//              largest alpha = 2^-j, j = 0..max_ls, with J - J(alpha) >= armijo * -(alpha dJ1 +
+//              alpha^2 dJ2) and J(alpha) <= J;
+//   mu         x mu_up (at least mu_min) after a failed factorisation or line search, / mu_down
+//              after an accepted step (0 once below mu_min).
+// The derivatives are those of cacto_ddp_backward (ddp_device.h; they are the reward's, so the
+// signs flip on the way in). Everything is float64 VALU and LDS; there is no matrix-core work here.
+//
+// Closed-form family (single integrator, car, double integrator): k_to_solve_thread, one
+// persistent kernel, one thread per episode, the whole iteration loop on the device. Trajectory
+// and gains live in the workspace in the [t][k][e] layout of DdpRec (a wave's lanes touch
+// consecutive addresses); episodes are handed out longest first so a wave's lanes have similar Te.
+// Split family (car_park, manipulator, UR5): per iteration the per-(episode, step) derivative
+// kernels of the label pass (fed a live copy of nsteps in which finished episodes are -1),
+// k_to_gains_wave (one wave per episode, operands in LDS, the M x M Cholesky on one lane) and
+// k_to_linesearch (one thread per (episode, j): every step size at once, then the largest
+// admissible one — by definition what sequential backtracking picks).
+#include "ddp_device.h"
+
+namespace cacto {
+
+// element (t, i) of a per-episode array at p[t * st + i * si]: the caller's [e][t][i] layout
+// (st = width, si = 1) or the workspace's [t][i][e] (st = width * n_ep, si = n_ep)
+struct View {
+  double* p;
+  size_t st, si;
+  __device__ __forceinline__ double& at(int t, int i) const { return p[(size_t)t * st + (size_t)i * si]; }
+};
+struct Traj {
+  View S, U;
+};
+struct Gains {
+  View k, K;  // K: element (i, j) of step t at index i * N + j
+};
+
+// l_u, l_uu (diagonal) of the cost at control u_j: w6 scale (u^2 + w_b (u/u_max)^10)' — the
+// expressions of k_ddp_backward with the sign of the cost
+__device__ __forceinline__ void to_lu(const cacto_sys_params& p, double w6, double u, int j, double* lu, double* luu) {
+  const double um = p.u_max[j];
+  *lu = -(p.scale * (-w6 * (2.0 * u + p.w_b * 10.0 * pow(u / um, 9.0) / um)));
+  *luu = -(p.scale * (-w6 * (2.0 + p.w_b * 90.0 * pow(u / um, 8.0) / (um * um))));
+}
+
+// The TO cost of one node: -Env.reward; UR5.reward leaves the bound penalty to reward_batch
+// (environment.py:780-805) while its TO cost has it (environment_TO.py:731-758), so it is added here.
+template <int NJ>
+__device__ inline double to_cost(const SysDevice& sd, const double* w, const double* s, const double* u) {
+  double c = -env_reward<NJ>(sd, w, s, u, false);
+  if constexpr (NJ > 2) {
+    if (u && sd.p.reward_kind == CACTO_REW_UR5) {
+      double b = 0.0;
+#pragma unroll
+      for (int i = 0; i < NJ; ++i) b += sd.p.w_b * pow(u[i] / sd.p.u_max[i], 10.0);
+      c += sd.p.scale * (w[6] * b);
+    }
+  }
+  return c;
+}
+
+// Cholesky of the M x M matrix a (lower triangle, in place, L L^T): false at a pivot <= 0 or a
+// non-finite one.
+template <int M>
+__device__ inline bool to_chol(double* a) {
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    double d = a[j * M + j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) d -= a[j * M + k] * a[j * M + k];
+    if (!(d > 0.0) || !isfinite(d)) return false;
+    const double l = sqrt(d);
+    a[j * M + j] = l;
+#pragma unroll
+    for (int i = j + 1; i < M; ++i) {
+      double s = a[i * M + j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) s -= a[i * M + k] * a[j * M + k];
+      a[i * M + j] = s / l;
+    }
+  }
+  return true;
+}
+// x <- (L L^T)^-1 x, x with stride sx
+template <int M>
+__device__ inline void to_chol_solve(const double* L, double* x, int sx) {
+#pragma unroll
+  for (int i = 0; i < M; ++i) {
+    double s = x[i * sx];
+#pragma unroll
+    for (int k = 0; k < i; ++k) s -= L[i * M + k] * x[k * sx];
+    x[i * sx] = s / L[i * M + i];
+  }
+#pragma unroll
+  for (int i = M - 1; i >= 0; --i) {
+    double s = x[i * sx];
+#pragma unroll
+    for (int k = i + 1; k < M; ++k) s -= L[k * M + i] * x[k * sx];
+    x[i * sx] = s / L[i * M + i];
+  }
+}
+
+// One step of the backward recursion on one thread (cost convention). In: A, B, l_x, l_xx, l_u,
+// diagonal l_uu, V_x / V_xx of step t+1. Out: k [M], K [M*N], V_x / V_xx of step t, dJ
+// accumulated. false: Qbar_uu is not positive definite (nothing is updated).
+template <int N, int M>
+__device__ inline bool to_riccati_step(const double* A, const double* B, const double* lx, const double* lxx,
+                                       const double* lu, const double* luu, double mu, double* Vx, double* Vxx,
+                                       double* k, double* K, double* dJ) {
+  double Qx[N], Qu[M], Qxx[N * N], Qux[M * N], Quu[M * M], VA[N * N], VB[N * M];
+#pragma unroll
+  for (int r = 0; r < N; ++r) {
+    double s = 0.0;
+#pragma unroll
+    for (int c = 0; c < N; ++c) s += A[c * N + r] * Vx[c];
+    Qx[r] = lx[r] + s;
+  }
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    double s = 0.0;
+#pragma unroll
+    for (int c = 0; c < N; ++c) s += B[c * M + j] * Vx[c];
+    Qu[j] = lu[j] + s;
+  }
+#pragma unroll
+  for (int r = 0; r < N; ++r) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+      double s = 0.0;
+#pragma unroll
+      for (int q = 0; q < N; ++q) s += Vxx[r * N + q] * A[q * N + c];
+      VA[r * N + c] = s;
+    }
+#pragma unroll
+    for (int c = 0; c < M; ++c) {
+      double s = 0.0;
+#pragma unroll
+      for (int q = 0; q < N; ++q) s += Vxx[r * N + q] * B[q * M + c];
+      VB[r * M + c] = s;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < N; ++r)
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+      double s = 0.0;
+#pragma unroll
+      for (int q = 0; q < N; ++q) s += A[q * N + r] * VA[q * N + c];
+      Qxx[r * N + c] = lxx[r * N + c] + s;
+    }
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+      double s = 0.0;
+#pragma unroll
+      for (int q = 0; q < N; ++q) s += B[q * M + j] * VA[q * N + c];
+      Qux[j * N + c] = s;
+    }
+#pragma unroll
+    for (int c = 0; c < M; ++c) {
+      double s = 0.0;
+#pragma unroll
+      for (int q = 0; q < N; ++q) s += B[q * M + j] * VB[q * M + c];
+      Quu[j * M + c] = (j == c ? luu[j] : 0.0) + s;
+    }
+  }
+  double L[M * M];
+#pragma unroll
+  for (int j = 0; j < M; ++j)
+#pragma unroll
+    for (int c = 0; c < M; ++c) L[j * M + c] = Quu[j * M + c] + (j == c ? mu : 0.0);
+  if (!to_chol<M>(L)) return false;
+#pragma unroll
+  for (int j = 0; j < M; ++j) k[j] = -Qu[j];
+  to_chol_solve<M>(L, k, 1);
+#pragma unroll
+  for (int q = 0; q < M * N; ++q) K[q] = -Qux[q];
+#pragma unroll
+  for (int c = 0; c < N; ++c) to_chol_solve<M>(L, K + c, N);
+  double Tk[M], T[M * N], d0 = 0.0, d1 = 0.0, d2 = dJ[2];
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    double s = 0.0;
+#pragma unroll
+    for (int c = 0; c < M; ++c) s += Quu[j * M + c] * k[c];
+    Tk[j] = s;
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+      double v = 0.0;
+#pragma unroll
+      for (int q = 0; q < M; ++q) v += Quu[j * M + q] * K[q * N + c];
+      T[j * N + c] = v;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    d0 += k[j] * Qu[j];
+    d1 += k[j] * Tk[j];
+    d2 = fmax(d2, fabs(Qu[j]));
+  }
+  dJ[0] += d0;
+  dJ[1] += 0.5 * d1;
+  dJ[2] = d2;
+#pragma unroll
+  for (int r = 0; r < N; ++r) {
+    double s = Qx[r];
+#pragma unroll
+    for (int j = 0; j < M; ++j) s += K[j * N + r] * (Tk[j] + Qu[j]) + Qux[j * N + r] * k[j];
+    Vx[r] = s;
+  }
+  double W[N * N];
+#pragma unroll
+  for (int r = 0; r < N; ++r)
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+      double s = Qxx[r * N + c];
+#pragma unroll
+      for (int j = 0; j < M; ++j) s += K[j * N + r] * (T[j * N + c] + Qux[j * N + c]) + Qux[j * N + r] * K[j * N + c];
+      W[r * N + c] = s;
+    }
+#pragma unroll
+  for (int r = 0; r < N; ++r)
+#pragma unroll
+    for (int c = 0; c < N; ++c) Vxx[r * N + c] = 0.5 * (W[r * N + c] + W[c * N + r]);
+  return true;
+}
+
+// M^-1 of a constant-M chain (the double integrator), once per episode
+template <int NJ>
+__device__ inline void to_minv(const SysDevice& sd, const double* q0, double* Minv) {
+  if constexpr (NJ > 0) {
+    double Mm[NJ * NJ];
+    chain_mass<NJ>(sd, q0, Mm);
+    small_inverse<NJ>(Mm, Minv);
+  }
+}
+
+// The backward pass of one closed-form episode on one thread. Returns -1, or the step at which
+// Qbar_uu was not positive definite. dJ [3] is reset here.
+template <int NJ>
+__device__ inline int to_backward_thread(const SysDevice& sd, const double* Minv, const Traj& cur, int Te, double mu,
+                                         const Gains& g, double* dJ) {
+  constexpr int N = DdpDims<NJ>::N, M = DdpDims<NJ>::M;
+  const cacto_sys_params& p = sd.p;
+  double w_run[7], w_term[7];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) {
+    w_run[k] = p.w_running[k];
+    w_term[k] = p.w_terminal[k];
+  }
+  double Vx[N], Vxx[N * N], x[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) x[k] = cur.S.at(Te, k);
+  ddp_lx<NJ>(sd, w_term, x, Vx, Vxx);
+#pragma unroll
+  for (int k = 0; k < N; ++k) Vx[k] = -Vx[k];
+#pragma unroll
+  for (int k = 0; k < N * N; ++k) Vxx[k] = -Vxx[k];
+  dJ[0] = dJ[1] = dJ[2] = 0.0;
+  for (int i = Te - 1; i >= 0; --i) {
+    double u[M], A[N * N], B[N * M], lx[N], lxx[N * N], lu[M], luu[M], kk[M], KK[M * N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) x[k] = cur.S.at(i, k);
+#pragma unroll
+    for (int k = 0; k < M; ++k) u[k] = cur.U.at(i, k);
+    ddp_jacobians<NJ>(sd, x, Minv, A, B);
+    ddp_lx<NJ>(sd, w_run, x, lx, lxx);
+#pragma unroll
+    for (int k = 0; k < N; ++k) lx[k] = -lx[k];
+#pragma unroll
+    for (int k = 0; k < N * N; ++k) lxx[k] = -lxx[k];
+#pragma unroll
+    for (int j = 0; j < M; ++j) to_lu(p, w_run[6], u[j], j, &lu[j], &luu[j]);
+    if (!to_riccati_step<N, M>(A, B, lx, lxx, lu, luu, mu, Vx, Vxx, kk, KK, dJ)) return i;
+#pragma unroll
+    for (int j = 0; j < M; ++j) g.k.at(i, j) = kk[j];
+#pragma unroll
+    for (int q = 0; q < M * N; ++q) g.K.at(i, q) = KK[q];
+  }
+  return -1;
+}
+
+// One roll-out of one episode on one thread: closed loop around (cur, g) with step size alpha, or
+// open loop (g.k.p == nullptr). STORE: the new trajectory goes to nw and the node costs to cost
+// (element t at cost.at(t, 0)); nw may be cur itself, since node t+1 of cur is read before node
+// t+1 of nw is written. Returns the total cost.
+template <int NJ, bool STORE>
+__device__ inline double to_forward_thread(const SysDevice& sd, const Traj& cur, const Gains& g, int Te, double alpha,
+                                           const Traj& nw, const View& cost) {
+  constexpr int N = DdpDims<NJ>::N, M = DdpDims<NJ>::M, ns = N + 1;
+  const cacto_sys_params& p = sd.p;
+  double w_run[7], w_term[7];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) {
+    w_run[k] = p.w_running[k];
+    w_term[k] = p.w_terminal[k];
+  }
+  double x[ns], xb[N], xn[ns], u[M];
+#pragma unroll
+  for (int k = 0; k < ns; ++k) x[k] = cur.S.at(0, k);
+#pragma unroll
+  for (int k = 0; k < N; ++k) xb[k] = x[k];
+  const double t0 = x[N];
+  if (STORE)
+#pragma unroll
+    for (int k = 0; k < ns; ++k) nw.S.at(0, k) = x[k];
+  double J = 0.0;
+  for (int t = 0; t < Te; ++t) {
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+      double v = cur.U.at(t, j);
+      if (g.k.p) {
+        v += alpha * g.k.at(t, j);
+#pragma unroll
+        for (int c = 0; c < N; ++c) v += g.K.at(t, j * N + c) * (x[c] - xb[c]);
+      }
+      u[j] = v;
+    }
+    const double c = to_cost<NJ>(sd, w_run, x, u);
+    J += c;
+    env_simulate<NJ>(sd, x, u, false, xn);
+    xn[N] = t0 + p.dt * (double)(t + 1);  // TO.py:115: t0 + dt * t, by multiplication
+#pragma unroll
+    for (int k = 0; k < N; ++k) xb[k] = cur.S.at(t + 1, k);
+    if (STORE) {
+#pragma unroll
+      for (int j = 0; j < M; ++j) nw.U.at(t, j) = u[j];
+      cost.at(t, 0) = c;
+#pragma unroll
+      for (int k = 0; k < ns; ++k) nw.S.at(t + 1, k) = xn[k];
+    }
+#pragma unroll
+    for (int k = 0; k < ns; ++k) x[k] = xn[k];
+  }
+  const double c = to_cost<NJ>(sd, w_term, x, nullptr);
+  J += c;
+  if (STORE) cost.at(Te, 0) = c;
+  return J;
+}
+
+__device__ __forceinline__ bool to_valid_len(int Te, int64_t ldS, int64_t ldU) { return Te >= 0 && Te < ldS && Te <= ldU; }
+
+// views of episode e in the caller's layout
+template <int NJ>
+__device__ __forceinline__ Traj api_traj(double* S, int64_t ldS, double* U, int64_t ldU, int e) {
+  constexpr int ns = Dims<NJ>::NS, na = Dims<NJ>::NA;
+  return Traj{View{S + (size_t)e * ldS * ns, (size_t)ns, 1}, View{U + (size_t)e * ldU * na, (size_t)na, 1}};
+}
+template <int NJ>
+__device__ __forceinline__ Gains api_gains(double* k, double* K, int64_t ldU, int e) {
+  constexpr int N = DdpDims<NJ>::N, na = Dims<NJ>::NA;
+  return Gains{View{k ? k + (size_t)e * ldU * na : nullptr, (size_t)na, 1},
+               View{K ? K + (size_t)e * ldU * na * N : nullptr, (size_t)na * N, 1}};
+}
+
+// cacto_to_backward_gains, closed-form family: one thread per episode.
+template <int NJ>
+__global__ void __launch_bounds__(64) k_to_gains_thread(const SysDevice* __restrict__ sdp, const double* S, int64_t ldS,
+                                                         const double* U, int64_t ldU,
+                                                         const int32_t* __restrict__ nsteps, int n_ep, double mu,
+                                                         double* k_out, double* K_out, double* __restrict__ dJ_out,
+                                                         int32_t* __restrict__ pd_out) {
+  constexpr int M = DdpDims<NJ>::M;
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_ep) return;
+  const int Te = nsteps[e];
+  if (!to_valid_len(Te, ldS, ldU)) return;
+  const SysDevice& sd = *sdp;
+  const Traj cur = api_traj<NJ>(const_cast<double*>(S), ldS, const_cast<double*>(U), ldU, e);
+  double Minv[NJ > 0 ? M * M : 1], q0[NJ > 0 ? NJ : 1];
+  if constexpr (NJ > 0) {
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) q0[i] = cur.S.at(0, i);
+    to_minv<NJ>(sd, q0, Minv);
+  }
+  double dJ[3];
+  const int pd = to_backward_thread<NJ>(sd, Minv, cur, Te, mu, api_gains<NJ>(k_out, K_out, ldU, e), dJ);
+  pd_out[e] = pd;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) dJ_out[(size_t)e * 3 + k] = dJ[k];
+}
+
+// cacto_to_forward, every system: one thread per episode.
+template <int NJ>
+__global__ void __launch_bounds__(64) k_to_forward(const SysDevice* __restrict__ sdp, const double* S, int64_t ldS,
+                                                    const double* U, int64_t ldU, const double* k_in,
+                                                    const double* K_in, const int32_t* __restrict__ nsteps, int n_ep,
+                                                    double alpha, double* S_new, double* U_new, double* cost_new) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_ep) return;
+  const int Te = nsteps[e];
+  if (!to_valid_len(Te, ldS, ldU)) return;
+  const Traj cur = api_traj<NJ>(const_cast<double*>(S), ldS, const_cast<double*>(U), ldU, e);
+  const Traj nw = api_traj<NJ>(S_new, ldS, U_new, ldU, e);
+  const Gains g = api_gains<NJ>(const_cast<double*>(k_in), const_cast<double*>(K_in), ldU, e);
+  to_forward_thread<NJ, true>(*sdp, cur, g, Te, alpha, nw, View{cost_new + (size_t)e * ldS, 1, 1});
+}
+
+struct ToCfgDev {
+  int max_iter, max_ls;
+  double gtol, armijo, mu_min, mu_up, mu_down, mu_max;
+};
+
+// mu after a failed factorisation or line search; true: past mu_max
+__device__ __forceinline__ bool to_raise_mu(const ToCfgDev& c, double* mu) {
+  *mu = fmax(*mu * c.mu_up, c.mu_min);
+  return *mu > c.mu_max;
+}
+__device__ __forceinline__ void to_lower_mu(const ToCfgDev& c, double* mu) {
+  *mu = *mu / c.mu_down;
+  if (*mu < c.mu_min) *mu = 0.0;
+}
+__device__ __forceinline__ bool to_admissible(const ToCfgDev& c, double J, double Jc, double alpha, const double* dJ) {
+  return isfinite(Jc) && (J - Jc >= c.armijo * -(alpha * dJ[0] + alpha * alpha * dJ[1])) && Jc <= J;
+}
+
+// Episodes sorted by decreasing length (counting sort over Te; one workgroup). order [n_ep],
+// hist [ldS + 1] scratch. The place of an episode among those of its own length depends on the
+// atomics' order; it only decides which lane runs it.
+__global__ void __launch_bounds__(256) k_to_order(const int32_t* __restrict__ nsteps, int n_ep, int64_t ldS,
+                                                  int32_t* __restrict__ order, int32_t* __restrict__ hist) {
+  const int nb = (int)ldS + 1;  // bucket 0: skipped or invalid, bucket b: Te = ldS - b
+  for (int b = threadIdx.x; b < nb; b += blockDim.x) hist[b] = 0;
+  __syncthreads();
+  for (int e = threadIdx.x; e < n_ep; e += blockDim.x) {
+    const int Te = nsteps[e];
+    atomicAdd(&hist[(Te < 0 || Te >= ldS) ? 0 : (int)ldS - Te], 1);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    // longest first; bucket 0 (nothing to do) last
+    int acc = 0;
+    for (int b = 1; b < nb; ++b) {
+      const int c = hist[b];
+      hist[b] = acc;
+      acc += c;
+    }
+    hist[0] = acc;
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < n_ep; e += blockDim.x) {
+    const int Te = nsteps[e];
+    order[atomicAdd(&hist[(Te < 0 || Te >= ldS) ? 0 : (int)ldS - Te], 1)] = e;
+  }
+}
+
+// The solver of the closed-form family: one thread per episode, the whole loop on the device.
+// ws: trajectory S [ldS][ns][n_ep], U [ldS][na][n_ep], node costs [ldS][n_ep], gains k
+// [ldS][na][n_ep], K [ldS][na*nx][n_ep]. The line search evaluates the candidates' costs without
+// storing them and rolls the accepted one out again in place.
+template <int NJ>
+__global__ void __launch_bounds__(64) k_to_solve_thread(const SysDevice* __restrict__ sdp, const double* __restrict__ S0,
+                                                         const double* __restrict__ U_init, int64_t ldU,
+                                                         const int32_t* __restrict__ nsteps, int n_ep, int64_t ldS,
+                                                         ToCfgDev cfg, const int32_t* __restrict__ order,
+                                                         double* __restrict__ ws, double* __restrict__ S_out,
+                                                         double* __restrict__ U_out, double* __restrict__ cost_out,
+                                                         int32_t* __restrict__ status_out, int32_t* __restrict__ iters_out,
+                                                         double* __restrict__ J_out) {
+  constexpr int N = DdpDims<NJ>::N, M = DdpDims<NJ>::M, ns = N + 1;
+  const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot >= n_ep) return;
+  const int e = order[slot];
+  const int Te = nsteps[e];
+  if (Te < 0) return;
+  if (!to_valid_len(Te, ldS, ldU)) {
+    status_out[e] = CACTO_TO_FAILED;
+    iters_out[e] = 0;
+    return;
+  }
+  const SysDevice& sd = *sdp;
+  const size_t E = (size_t)n_ep, L = (size_t)ldS;
+  double* wS = ws + e;
+  double* wU = wS + L * ns * E;
+  double* wC = wU + L * M * E;
+  double* wk = wC + L * E;
+  double* wK = wk + L * M * E;
+  const Traj cur{View{wS, ns * E, E}, View{wU, M * E, E}};
+  const Gains g{View{wk, M * E, E}, View{wK, (size_t)M * N * E, E}};
+  const View cost{wC, E, E};
+  // the warm start: U_init rolled out from s0
+#pragma unroll
+  for (int k = 0; k < ns; ++k) cur.S.at(0, k) = S0[(size_t)e * ns + k];
+  for (int t = 0; t < Te; ++t)
+#pragma unroll
+    for (int j = 0; j < M; ++j) cur.U.at(t, j) = U_init[((size_t)e * ldU + t) * M + j];
+  const Gains none{View{nullptr, 0, 0}, View{nullptr, 0, 0}};
+  double J = to_forward_thread<NJ, true>(sd, cur, none, Te, 0.0, cur, cost);
+  const double J0 = J;
+  int status = CACTO_TO_MAXITER, iters = 0;
+  if (Te == 0) status = CACTO_TO_CONVERGED;
+  if (!isfinite(J)) status = CACTO_TO_FAILED;
+  if (status == CACTO_TO_MAXITER) {
+    double Minv[NJ > 0 ? M * M : 1], q0[NJ > 0 ? NJ : 1];
+    if constexpr (NJ > 0) {
+#pragma unroll
+      for (int i = 0; i < NJ; ++i) q0[i] = cur.S.at(0, i);
+      to_minv<NJ>(sd, q0, Minv);
+    }
+    double mu = 0.0, dJ[3];
+    for (int it = 0; it < cfg.max_iter; ++it) {
+      ++iters;
+      const int pd = to_backward_thread<NJ>(sd, Minv, cur, Te, mu, g, dJ);
+      bool raise = pd >= 0;
+      if (!raise) {
+        if (dJ[2] <= cfg.gtol) {
+          status = CACTO_TO_CONVERGED;
+          break;
+        }
+        int sel = -1;
+        for (int j = 0; j <= cfg.max_ls && sel < 0; ++j) {
+          const double alpha = ldexp(1.0, -j);
+          const double Jc = to_forward_thread<NJ, false>(sd, cur, g, Te, alpha, cur, cost);
+          if (to_admissible(cfg, J, Jc, alpha, dJ)) sel = j;
+        }
+        if (sel >= 0) {
+          J = to_forward_thread<NJ, true>(sd, cur, g, Te, ldexp(1.0, -sel), cur, cost);
+          to_lower_mu(cfg, &mu);
+        } else {
+          raise = true;
+        }
+      }
+      if (raise && to_raise_mu(cfg, &mu)) {
+        status = CACTO_TO_FAILED;
+        break;
+      }
+    }
+  }
+  for (int t = 0; t <= Te; ++t) {
+#pragma unroll
+    for (int k = 0; k < ns; ++k) S_out[((size_t)e * ldS + t) * ns + k] = cur.S.at(t, k);
+    cost_out[(size_t)e * ldS + t] = cost.at(t, 0);
+    if (t < Te)
+#pragma unroll
+      for (int j = 0; j < M; ++j) U_out[((size_t)e * ldU + t) * M + j] = cur.U.at(t, j);
+  }
+  status_out[e] = status;
+  iters_out[e] = iters;
+  J_out[(size_t)e * 2] = J0;
+  J_out[(size_t)e * 2 + 1] = J;
+}
+
+// The backward pass of the split family with gains: one wavefront per episode, every product's
+// outputs spread over the lanes, operands in LDS, the M x M Cholesky and its solves on lane 0.
+// rec: the derivative records of k_ddp_derivs / k_ddp_prim + k_ddp_tan + k_ddp_lx (the reward's:
+// l_x, l_xx change sign on load). mu_ep: per-episode mu (the solver) or nullptr (mu).
+template <int NJ>
+__global__ void __launch_bounds__(64) k_to_gains_wave(const SysDevice* __restrict__ sdp, const double* __restrict__ U,
+                                                      int64_t ldU, const int32_t* __restrict__ nsteps, int n_ep,
+                                                      int64_t ldS, double mu, const double* __restrict__ mu_ep,
+                                                      const double* __restrict__ rec_ws, double* __restrict__ k_out,
+                                                      double* __restrict__ K_out, double* __restrict__ dJ_out,
+                                                      int32_t* __restrict__ pd_out) {
+  using RC = DdpRec<NJ>;
+  constexpr int N = RC::N, M = RC::M, na = Dims<NJ>::NA;
+  __shared__ double sA[N * N], sB[N * M], sLx[N], sLxx[N * N], sVx[N], sVxx[N * N], sU[M];
+  __shared__ double sVA[N * N], sVB[N * M], sQx[N], sQu[M], sQxx[N * N], sQux[M * N], sQuu[M * M];
+  __shared__ double sk[M], sK[M * N], sTk[M], sT[M * N], sW[N * N];
+  __shared__ int sFail;
+  const int e = blockIdx.x, lane = threadIdx.x;
+  const cacto_sys_params& p = sdp->p;
+  const double w6 = p.w_running[6];
+  const int Te = nsteps[e];
+  if (!to_valid_len(Te, ldS, ldU)) return;  // uniform over the workgroup
+  if (mu_ep) mu = mu_ep[e];
+  const double* Ue = U + (size_t)e * ldU * na;
+  double* ke = k_out + (size_t)e * ldU * na;
+  double* Ke = K_out + (size_t)e * ldU * na * N;
+  {
+    const double* rec = rec_ws + (size_t)Te * RC::R * n_ep + e;
+    for (int k = lane; k < N; k += 64) sVx[k] = -rec[(size_t)(RC::LX + k) * n_ep];
+    for (int k = lane; k < N * N; k += 64) sVxx[k] = -rec[(size_t)(RC::LXX + k) * n_ep];
+    if (lane == 0) sFail = 0;
+  }
+  double d0 = 0.0, d1 = 0.0, d2 = 0.0;  // lane 0's
+  int pd = -1;
+  __syncthreads();
+  for (int i = Te - 1; i >= 0; --i) {
+    const double* rec = rec_ws + (size_t)i * RC::R * n_ep + e;
+    for (int k = lane; k < N * N; k += 64) {
+      sA[k] = rec[(size_t)(RC::A + k) * n_ep];
+      sLxx[k] = -rec[(size_t)(RC::LXX + k) * n_ep];
+    }
+    for (int k = lane; k < N * M; k += 64) sB[k] = rec[(size_t)(RC::B + k) * n_ep];
+    for (int k = lane; k < N; k += 64) sLx[k] = -rec[(size_t)(RC::LX + k) * n_ep];
+    for (int k = lane; k < M; k += 64) sU[k] = Ue[(size_t)i * na + k];
+    __syncthreads();
+    // V_xx A, V_xx B, Q_x = l_x + A^T V_x, Q_u = l_u + B^T V_x
+    for (int o = lane; o < N * N + N * M + N + M; o += 64) {
+      double s = 0.0;
+      if (o < N * N) {
+        const int r = o / N, c = o - r * N;
+#pragma unroll
+        for (int k = 0; k < N; ++k) s += sVxx[r * N + k] * sA[k * N + c];
+        sVA[o] = s;
+      } else if (o < N * N + N * M) {
+        const int q = o - N * N, r = q / M, c = q - r * M;
+#pragma unroll
+        for (int k = 0; k < N; ++k) s += sVxx[r * N + k] * sB[k * M + c];
+        sVB[q] = s;
+      } else if (o < N * N + N * M + N) {
+        const int r = o - N * N - N * M;
+#pragma unroll
+        for (int k = 0; k < N; ++k) s += sA[k * N + r] * sVx[k];
+        sQx[r] = sLx[r] + s;
+      } else {
+        const int j = o - N * N - N * M - N;
+        double lu, luu;
+        to_lu(p, w6, sU[j], j, &lu, &luu);
+#pragma unroll
+        for (int k = 0; k < N; ++k) s += sB[k * M + j] * sVx[k];
+        sQu[j] = lu + s;
+      }
+    }
+    __syncthreads();
+    // Q_xx = l_xx + A^T V_xx A, Q_ux = B^T V_xx A, Q_uu = l_uu + B^T V_xx B
+    for (int o = lane; o < N * N + M * N + M * M; o += 64) {
+      double s = 0.0;
+      if (o < N * N) {
+        const int r = o / N, c = o - r * N;
+#pragma unroll
+        for (int k = 0; k < N; ++k) s += sA[k * N + r] * sVA[k * N + c];
+        sQxx[o] = sLxx[o] + s;
+      } else if (o < N * N + M * N) {
+        const int q = o - N * N, j = q / N, c = q - j * N;
+#pragma unroll
+        for (int k = 0; k < N; ++k) s += sB[k * M + j] * sVA[k * N + c];
+        sQux[q] = s;
+      } else {
+        const int q = o - N * N - M * N, r = q / M, c = q - r * M;
+#pragma unroll
+        for (int k = 0; k < N; ++k) s += sB[k * M + r] * sVB[k * M + c];
+        double lu, luu = 0.0;
+        if (r == c) to_lu(p, w6, sU[r], r, &lu, &luu);
+        sQuu[q] = luu + s;
+      }
+    }
+    __syncthreads();
+    if (lane == 0) {
+      double Lm[M * M], kk[M];
+#pragma unroll
+      for (int q = 0; q < M * M; ++q) Lm[q] = sQuu[q] + (q % (M + 1) == 0 ? mu : 0.0);
+      if (!to_chol<M>(Lm)) {
+        sFail = 1;
+        pd = i;
+      } else {
+#pragma unroll
+        for (int j = 0; j < M; ++j) kk[j] = -sQu[j];
+        to_chol_solve<M>(Lm, kk, 1);
+#pragma unroll 1
+        for (int c = 0; c < N; ++c) {
+          double col[M];
+#pragma unroll
+          for (int j = 0; j < M; ++j) col[j] = -sQux[j * N + c];
+          to_chol_solve<M>(Lm, col, 1);
+#pragma unroll
+          for (int j = 0; j < M; ++j) sK[j * N + c] = col[j];
+        }
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+          double s = 0.0;
+#pragma unroll
+          for (int c = 0; c < M; ++c) s += sQuu[j * M + c] * kk[c];
+          sTk[j] = s;
+          sk[j] = kk[j];
+          d0 += kk[j] * sQu[j];
+          d1 += kk[j] * s;
+          d2 = fmax(d2, fabs(sQu[j]));
+        }
+      }
+    }
+    __syncthreads();
+    if (sFail) break;  // uniform
+    // T = Q_uu K; the gains to memory
+    for (int o = lane; o < M * N; o += 64) {
+      const int j = o / N, c = o - j * N;
+      double s = 0.0;
+#pragma unroll
+      for (int q = 0; q < M; ++q) s += sQuu[j * M + q] * sK[q * N + c];
+      sT[o] = s;
+      Ke[(size_t)i * na * N + o] = sK[o];
+    }
+    for (int j = lane; j < M; j += 64) ke[(size_t)i * na + j] = sk[j];
+    __syncthreads();
+    // V_x, and V_xx before symmetrisation
+    for (int o = lane; o < N * N + N; o += 64) {
+      if (o < N * N) {
+        const int r = o / N, c = o - r * N;
+        double s = sQxx[o];
+#pragma unroll
+        for (int j = 0; j < M; ++j)
+          s += sK[j * N + r] * (sT[j * N + c] + sQux[j * N + c]) + sQux[j * N + r] * sK[j * N + c];
+        sW[o] = s;
+      } else {
+        const int r = o - N * N;
+        double s = sQx[r];
+#pragma unroll
+        for (int j = 0; j < M; ++j) s += sK[j * N + r] * (sTk[j] + sQu[j]) + sQux[j * N + r] * sk[j];
+        sVx[r] = s;
+      }
+    }
+    __syncthreads();
+    for (int o = lane; o < N * N; o += 64) {
+      const int r = o / N, c = o - r * N;
+      sVxx[o] = 0.5 * (sW[o] + sW[c * N + r]);
+    }
+    __syncthreads();
+  }
+  if (lane == 0) {
+    pd_out[e] = pd;
+    dJ_out[(size_t)e * 3] = d0;
+    dJ_out[(size_t)e * 3 + 1] = 0.5 * d1;
+    dJ_out[(size_t)e * 3 + 2] = d2;
+  }
+}
+
+// Solver state of the split family, per episode: live (Te while the episode is being optimised,
+// -1 once finished or skipped: the derivative and gains kernels skip it), mu, J; done counts the
+// finished episodes (the host's poll).
+struct ToState {
+  int32_t* live;
+  double* mu;
+  double* J;
+  int32_t* done;
+};
+
+// Warm start of the split family: U_init rolled out from s0 into the caller's S / U / step_cost.
+template <int NJ>
+__global__ void __launch_bounds__(64) k_to_init(const SysDevice* __restrict__ sdp, const double* __restrict__ S0,
+                                                const double* __restrict__ U_init, int64_t ldU,
+                                                const int32_t* __restrict__ nsteps, int n_ep, int64_t ldS, ToState st,
+                                                double* S_out, double* U_out, double* cost_out,
+                                                int32_t* __restrict__ status_out, int32_t* __restrict__ iters_out,
+                                                double* __restrict__ J_out) {
+  constexpr int ns = Dims<NJ>::NS, na = Dims<NJ>::NA;
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_ep) return;
+  const int Te = nsteps[e];
+  st.mu[e] = 0.0;
+  st.live[e] = -1;
+  if (Te < 0) {
+    atomicAdd(st.done, 1);
+    return;
+  }
+  if (!to_valid_len(Te, ldS, ldU)) {
+    status_out[e] = CACTO_TO_FAILED;
+    iters_out[e] = 0;
+    atomicAdd(st.done, 1);
+    return;
+  }
+  const Traj cur = api_traj<NJ>(S_out, ldS, U_out, ldU, e);
+#pragma unroll
+  for (int k = 0; k < ns; ++k) cur.S.at(0, k) = S0[(size_t)e * ns + k];
+  for (int t = 0; t < Te; ++t)
+#pragma unroll
+    for (int j = 0; j < na; ++j) cur.U.at(t, j) = U_init[((size_t)e * ldU + t) * na + j];
+  const Gains none{View{nullptr, 0, 0}, View{nullptr, 0, 0}};
+  const double J = to_forward_thread<NJ, true>(*sdp, cur, none, Te, 0.0, cur, View{cost_out + (size_t)e * ldS, 1, 1});
+  st.J[e] = J;
+  J_out[(size_t)e * 2] = J;
+  J_out[(size_t)e * 2 + 1] = J;
+  iters_out[e] = 0;
+  int status = CACTO_TO_MAXITER;
+  if (Te == 0) status = CACTO_TO_CONVERGED;
+  if (!isfinite(J)) status = CACTO_TO_FAILED;
+  status_out[e] = status;
+  if (status == CACTO_TO_MAXITER)
+    st.live[e] = Te;
+  else
+    atomicAdd(st.done, 1);
+}
+
+// One iteration's decision and line search of the split family. A workgroup of 64 threads holds
+// 64 / LSP episodes (LSP: the power of two >= max_ls + 1), thread (episode, j) evaluates the cost
+// of alpha = 2^-j without storing the trajectory, the episode's first thread picks the smallest
+// admissible j and updates the episode's state, and thread j rolls the accepted step out in place.
+template <int NJ>
+__global__ void __launch_bounds__(64) k_to_linesearch(const SysDevice* __restrict__ sdp, double* S, int64_t ldS, double* U,
+                                                       int64_t ldU, double* k_in, double* K_in,
+                                                       const double* __restrict__ dJ_in, const int32_t* __restrict__ pd_in,
+                                                       int n_ep, ToCfgDev cfg, int LSP, ToState st, double* cost_out,
+                                                       int32_t* __restrict__ status_out, int32_t* __restrict__ iters_out,
+                                                       double* __restrict__ J_out) {
+  __shared__ double sJ[64];
+  __shared__ int sSel[64];
+  const int G = 64 / LSP, tid = threadIdx.x;
+  const int grp = tid / LSP, j = tid - grp * LSP;
+  const int e = blockIdx.x * G + grp;
+  const bool have = e < n_ep;
+  const int Te = have ? st.live[e] : -1;
+  const bool live = Te >= 0;
+  double dJ[3] = {0.0, 0.0, 0.0}, J = 0.0;
+  int pd = -1;
+  if (live) {
+    pd = pd_in[e];
+    J = st.J[e];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dJ[k] = dJ_in[(size_t)e * 3 + k];
+  }
+  const bool search = live && pd < 0 && !(dJ[2] <= cfg.gtol);
+  const double alpha = ldexp(1.0, -j);
+  Traj cur{};
+  Gains g{};
+  View cost{};
+  if (live) {
+    cur = api_traj<NJ>(S, ldS, U, ldU, e);
+    g = api_gains<NJ>(k_in, K_in, ldU, e);
+    cost = View{cost_out + (size_t)e * ldS, 1, 1};
+  }
+  double Jc = 0.0;
+  bool ok = false;
+  if (search && j <= cfg.max_ls) {
+    Jc = to_forward_thread<NJ, false>(*sdp, cur, g, Te, alpha, cur, cost);
+    ok = to_admissible(cfg, J, Jc, alpha, dJ);
+  }
+  sJ[tid] = ok ? Jc : __builtin_nan("");
+  __syncthreads();
+  if (j == 0) {
+    int sel = -1;
+    if (live) {
+      double mu = st.mu[e];
+      int finished = -1;
+      iters_out[e] += 1;
+      bool raise = pd >= 0;
+      if (!raise) {
+        if (!search) {
+          finished = CACTO_TO_CONVERGED;
+        } else {
+          for (int q = 0; q <= cfg.max_ls && sel < 0; ++q)
+            if (sJ[grp * LSP + q] == sJ[grp * LSP + q]) sel = q;
+          if (sel >= 0) {
+            st.J[e] = sJ[grp * LSP + sel];
+            J_out[(size_t)e * 2 + 1] = sJ[grp * LSP + sel];
+            to_lower_mu(cfg, &mu);
+          } else {
+            raise = true;
+          }
+        }
+      }
+      if (raise && to_raise_mu(cfg, &mu)) finished = CACTO_TO_FAILED;
+      st.mu[e] = mu;
+      if (finished >= 0) {
+        status_out[e] = finished;
+        st.live[e] = -1;
+        atomicAdd(st.done, 1);
+      }
+    }
+    sSel[grp] = sel;
+  }
+  __syncthreads();
+  if (search && j == sSel[grp]) to_forward_thread<NJ, true>(*sdp, cur, g, Te, alpha, cur, cost);
+}
+
+}  // namespace cacto
+
+using namespace cacto;
+
+namespace {
+
+inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
+
+template <int NJ>
+constexpr bool to_split() {
+  return NJ > 2 || NJ == -2;
+}
+
+// the (dynamics, reward) combinations of the six systems, as cacto_ddp_backward
+template <int NJ>
+bool to_supported(const cacto_sys* sys, const char* who) {
+  bool ok = DdpDims<NJ>::ok;
+  if (ok) {
+    const int rk = sys->host.p.reward_kind;
+    const bool rk_ok = NJ == -2 ? rk == CACTO_REW_CAR_PARK
+                                : NJ > 0 ? (sys->host.p.const_dyn ? rk == CACTO_REW_PLANAR
+                                                                 : rk == CACTO_REW_MANIPULATOR || rk == CACTO_REW_UR5)
+                                         : rk == CACTO_REW_PLANAR;
+    ok = rk_ok && !(NJ > 0 && (sys->host.p.const_dyn ? NJ != 2 : NJ == 2));
+  }
+  if (!ok) set_error(std::string(who) + ": unsupported (dynamics, reward) combination");
+  return ok;
+}
+
+// doubles of derivative records (and, revolute chains, the primal workspace) for ldS steps
+template <int NJ>
+size_t to_rec_doubles(int n_ep, int64_t ldS) {
+  size_t n = (size_t)ldS * DdpRec<NJ>::R * n_ep;
+  if constexpr (NJ > 2) n += (size_t)ldS * DdpPrim<NJ>::R * n_ep;
+  return n;
+}
+
+// the derivative kernels of the label pass over (episode, step)
+template <int NJ>
+int to_launch_derivs(const cacto_sys* sys, const double* S, int64_t ldS, const double* U, int64_t ldU, const int32_t* n,
+                     int n_ep, double* rec, hipStream_t st) {
+  const dim3 g(ceil_div(n_ep, 64), (unsigned)ldS);
+  if constexpr (NJ > 2) {
+    double* pw = rec + (size_t)ldS * DdpRec<NJ>::R * n_ep;
+    hipLaunchKernelGGL(k_ddp_prim<NJ>, g, dim3(64), 0, st, sys->dev, S, ldS, U, ldU, n, n_ep, rec, pw);
+    CACTO_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_ddp_lx<NJ>, g, dim3(64), 0, st, sys->dev, S, ldS, n, n_ep, rec);
+    CACTO_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_ddp_tan<NJ>, dim3(g.x, g.y, 2 * NJ), dim3(64), 0, st, sys->dev, S, ldS, n, n_ep, rec, pw);
+  } else {
+    hipLaunchKernelGGL(k_ddp_derivs<NJ>, g, dim3(64), 0, st, sys->dev, S, ldS, U, ldU, n, n_ep, rec);
+  }
+  CACTO_CHECK_HIP(hipGetLastError());
+  return CACTO_OK;
+}
+
+template <int NJ>
+struct LaunchToGains {
+  static int run(const cacto_sys* sys, const double* S, int64_t ldS, const double* U, int64_t ldU, const int32_t* n,
+                 int n_ep, double mu, double* k, double* K, double* dJ, int32_t* pd, hipStream_t st) {
+    if (!to_supported<NJ>(sys, "cacto_to_backward_gains")) return CACTO_EUNSUPPORTED;
+    if constexpr (DdpDims<NJ>::ok) {
+      if constexpr (to_split<NJ>()) {
+        double* rec = nullptr;
+        const int rc = cacto_ddp_workspace(const_cast<cacto_sys*>(sys), to_rec_doubles<NJ>(n_ep, ldS) * sizeof(double), &rec);
+        if (rc != CACTO_OK) return rc;
+        const int rc2 = to_launch_derivs<NJ>(sys, S, ldS, U, ldU, n, n_ep, rec, st);
+        if (rc2 != CACTO_OK) return rc2;
+        hipLaunchKernelGGL(k_to_gains_wave<NJ>, dim3(n_ep), dim3(64), 0, st, sys->dev, U, ldU, n, n_ep, ldS, mu,
+                           (const double*)nullptr, rec, k, K, dJ, pd);
+      } else {
+        hipLaunchKernelGGL(k_to_gains_thread<NJ>, dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S, ldS, U, ldU, n,
+                           n_ep, mu, k, K, dJ, pd);
+      }
+      CACTO_CHECK_HIP(hipGetLastError());
+    }
+    return CACTO_OK;
+  }
+};
+
+template <int NJ>
+struct LaunchToForward {
+  static int run(const cacto_sys* sys, const double* S, int64_t ldS, const double* U, int64_t ldU, const double* k,
+                 const double* K, const int32_t* n, int n_ep, double alpha, double* Sn, double* Un, double* cost,
+                 hipStream_t st) {
+    if (!to_supported<NJ>(sys, "cacto_to_forward")) return CACTO_EUNSUPPORTED;
+    if constexpr (DdpDims<NJ>::ok) {
+      hipLaunchKernelGGL(k_to_forward<NJ>, dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S, ldS, U, ldU, k, K, n,
+                         n_ep, alpha, Sn, Un, cost);
+      CACTO_CHECK_HIP(hipGetLastError());
+    }
+    return CACTO_OK;
+  }
+};
+
+// Workspace of cacto_to_solve, in 256-byte aligned blocks.
+//   closed-form family: order [n_ep] + hist [ldS + 1] int32; trajectory, costs and gains [t][k][e]
+//   split family: live [n_ep] int32 + done; mu, J [n_ep]; dJ [n_ep, 3]; pd [n_ep] int32; gains k
+//                 [n_ep, ldS, na], K [n_ep, ldS, na, nx]; the derivative records
+template <int NJ>
+struct ToWs {
+  static constexpr int N = DdpDims<NJ>::N, M = DdpDims<NJ>::M;
+  size_t off_i32, off_d, off_rec, bytes;
+  ToWs(int n_ep, int64_t ldS) {
+    const size_t E = (size_t)n_ep, L = (size_t)ldS;
+    off_i32 = 0;
+    if constexpr (to_split<NJ>()) {
+      off_d = align256((2 * E + 1) * sizeof(int32_t));  // live, pd, done
+      const size_t d = 2 * E + 3 * E + E * L * M + E * L * M * N;
+      off_rec = off_d + align256(d * sizeof(double));
+      bytes = off_rec + align256(to_rec_doubles<NJ>(n_ep, ldS) * sizeof(double));
+    } else {
+      off_d = align256((E + L + 1) * sizeof(int32_t));
+      off_rec = 0;
+      bytes = off_d + align256(E * L * (size_t)(N + 1 + M + 1 + M + M * N) * sizeof(double));
+    }
+  }
+};
+
+template <int NJ>
+struct LaunchToBytes {
+  static int run(int n_ep, int64_t ldS, size_t* out) {
+    if constexpr (DdpDims<NJ>::ok) *out = ToWs<NJ>(n_ep, ldS).bytes;
+    return CACTO_OK;
+  }
+};
+
+template <int NJ>
+struct LaunchToSolve {
+  static int run(const cacto_sys* sys, const double* S0, const double* U_init, int64_t ldU, const int32_t* n, int n_ep,
+                 int64_t ldS, const cacto_to_cfg* cfg, double* S, double* U, double* cost, int32_t* status,
+                 int32_t* iters, double* J, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (!to_supported<NJ>(sys, "cacto_to_solve")) return CACTO_EUNSUPPORTED;
+    if constexpr (DdpDims<NJ>::ok) {
+      const ToWs<NJ> lay(n_ep, ldS);
+      CACTO_REQUIRE(ws_bytes >= lay.bytes, "cacto_to_solve: workspace smaller than cacto_to_workspace_bytes");
+      const ToCfgDev c{cfg->max_iter, cfg->max_ls, cfg->gtol, cfg->armijo, cfg->mu_min, cfg->mu_up, cfg->mu_down, cfg->mu_max};
+      char* base = static_cast<char*>(ws);
+      constexpr int M = DdpDims<NJ>::M, N = DdpDims<NJ>::N;
+      const size_t E = (size_t)n_ep, L = (size_t)ldS;
+      if constexpr (!to_split<NJ>()) {
+        int32_t* order = reinterpret_cast<int32_t*>(base + lay.off_i32);
+        int32_t* hist = order + E;
+        hipLaunchKernelGGL(k_to_order, dim3(1), dim3(256), 0, st, n, n_ep, ldS, order, hist);
+        CACTO_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_to_solve_thread<NJ>, dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S0, U_init, ldU, n,
+                           n_ep, ldS, c, order, reinterpret_cast<double*>(base + lay.off_d), S, U, cost, status, iters, J);
+        CACTO_CHECK_HIP(hipGetLastError());
+      } else {
+        int32_t* live = reinterpret_cast<int32_t*>(base + lay.off_i32);
+        int32_t* pd = live + E;
+        int32_t* done = pd + E;
+        double* mu = reinterpret_cast<double*>(base + lay.off_d);
+        double* Jc = mu + E;
+        double* dJ = Jc + E;
+        double* kg = dJ + 3 * E;
+        double* Kg = kg + E * L * M;
+        double* rec = reinterpret_cast<double*>(base + lay.off_rec);
+        const ToState state{live, mu, Jc, done};
+        // the gains kernel indexes the gains with ldU; the workspace holds ldS rows of them
+        CACTO_REQUIRE(ldU <= ldS, "cacto_to_solve: ldU > ldS");
+        CACTO_CHECK_HIP(hipMemsetAsync(done, 0, sizeof(int32_t), st));
+        hipLaunchKernelGGL(k_to_init<NJ>, dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S0, U_init, ldU, n, n_ep,
+                           ldS, state, S, U, cost, status, iters, J);
+        CACTO_CHECK_HIP(hipGetLastError());
+        int LSP = 1;
+        while (LSP < c.max_ls + 1) LSP *= 2;
+        const int G = 64 / LSP;
+        for (int it = 0; it < c.max_iter; ++it) {
+          if (cfg->poll_every > 0 && it % cfg->poll_every == 0) {
+            int32_t d = 0;
+            CACTO_CHECK_HIP(hipMemcpyAsync(&d, done, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            CACTO_CHECK_HIP(hipStreamSynchronize(st));
+            if (d >= n_ep) break;
+          }
+          const int rc = to_launch_derivs<NJ>(sys, S, ldS, U, ldU, live, n_ep, rec, st);
+          if (rc != CACTO_OK) return rc;
+          hipLaunchKernelGGL(k_to_gains_wave<NJ>, dim3(n_ep), dim3(64), 0, st, sys->dev, U, ldU, live, n_ep, ldS, 0.0,
+                             (const double*)mu, rec, kg, Kg, dJ, pd);
+          CACTO_CHECK_HIP(hipGetLastError());
+          hipLaunchKernelGGL(k_to_linesearch<NJ>, dim3(ceil_div(n_ep, G)), dim3(64), 0, st, sys->dev, S, ldS, U, ldU, kg,
+                             Kg, dJ, pd, n_ep, c, LSP, state, cost, status, iters, J);
+          CACTO_CHECK_HIP(hipGetLastError());
+        }
+      }
+    }
+    return CACTO_OK;
+  }
+};
+
+}  // namespace
+
+extern "C" int cacto_to_backward_gains(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d,
+                                       int64_t ldU, const int32_t* nsteps_d, int n_ep, double mu, double* k_d,
+                                       double* K_d, double* dJ_d, int32_t* pd_d, void* stream) {
+  CACTO_REQUIRE(sys && S_d && U_d && nsteps_d && k_d && K_d && dJ_d && pd_d && n_ep >= 0 && ldS >= 1 && ldU >= 0,
+                "cacto_to_backward_gains: bad arguments");
+  if (n_ep == 0) return CACTO_OK;
+  return dispatch_nj<LaunchToGains>(sys->host.p, sys, S_d, ldS, U_d, ldU, nsteps_d, n_ep, mu, k_d, K_d, dJ_d, pd_d,
+                                    as_stream(stream));
+}
+
+extern "C" int cacto_to_forward(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d, int64_t ldU,
+                                const double* k_d, const double* K_d, const int32_t* nsteps_d, int n_ep, double alpha,
+                                double* S_new_d, double* U_new_d, double* cost_new_d, void* stream) {
+  CACTO_REQUIRE(sys && S_d && U_d && nsteps_d && S_new_d && U_new_d && cost_new_d && n_ep >= 0 && ldS >= 1 && ldU >= 0 &&
+                    (k_d == nullptr) == (K_d == nullptr),
+                "cacto_to_forward: bad arguments");
+  if (n_ep == 0) return CACTO_OK;
+  return dispatch_nj<LaunchToForward>(sys->host.p, sys, S_d, ldS, U_d, ldU, k_d, K_d, nsteps_d, n_ep, alpha, S_new_d,
+                                      U_new_d, cost_new_d, as_stream(stream));
+}
+
+extern "C" size_t cacto_to_workspace_bytes(const cacto_sys* sys, int n_ep, int64_t ldS) {
+  if (!sys || n_ep < 0 || ldS < 1) return 0;
+  size_t out = 0;
+  if (dispatch_nj<LaunchToBytes>(sys->host.p, n_ep, ldS, &out) != CACTO_OK) return 0;
+  return out;
+}
+
+extern "C" int cacto_to_solve(const cacto_sys* sys, const double* S0_d, const double* U_init_d, int64_t ldU,
+                              const int32_t* nsteps_d, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h, double* S_d,
+                              double* U_d, double* step_cost_d, int32_t* status_d, int32_t* iters_d, double* J_d,
+                              void* ws_d, size_t ws_bytes, void* stream) {
+  CACTO_REQUIRE(cfg_h, "cacto_to_solve: null config");
+  CACTO_REQUIRE(sys && S0_d && U_init_d && nsteps_d && S_d && U_d && step_cost_d && status_d && iters_d && J_d && ws_d &&
+                    n_ep >= 0 && ldS >= 1 && ldU >= 0 && ldU <= ldS,
+                "cacto_to_solve: bad arguments (null pointer, n_ep < 0, ldS < 1, ldU < 0 or ldU > ldS)");
+  CACTO_REQUIRE(cfg_h->max_iter >= 0 && cfg_h->max_ls >= 0 && cfg_h->max_ls <= 63 && cfg_h->mu_up > 1.0 &&
+                    cfg_h->mu_down > 1.0 && cfg_h->mu_min > 0.0 && cfg_h->poll_every >= 0,
+                "cacto_to_solve: bad config (max_iter >= 0, 0 <= max_ls <= 63, mu_up > 1, mu_down > 1, mu_min > 0)");
+  if (sys->host.p.w_terminal[6] != 0.0) {
+    set_error("cacto_to_solve: w_terminal[6] != 0 (the reference adds u_{T-1} to the terminal cost through it, TO.py:60)");
+    return CACTO_EUNSUPPORTED;
+  }
+  if (n_ep == 0) return CACTO_OK;
+  return dispatch_nj<LaunchToSolve>(sys->host.p, sys, S0_d, U_init_d, ldU, nsteps_d, n_ep, ldS, cfg_h, S_d, U_d,
+                                    step_cost_d, status_d, iters_d, J_d, ws_d, ws_bytes, as_stream(stream));
+}

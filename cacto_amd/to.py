@@ -1,17 +1,49 @@
-"""TO — the value-gradient half of the reference's trajectory optimisation (TO.py:9-202).
+"""TO — the reference's trajectory optimisation (TO.py:9-202) on the GPU.
 
-The NLP solve itself (TO_System_Solve, TO.py:37-100: CasADi + ipopt) stays on the host CPU and is
-not part of this package. What the learner consumes from it besides the trajectory is the Sobolev
-label dV/dx, which the reference computes with a DDP backward pass (TO.backward_pass,
-TO.py:119-202). That pass runs here on the GPU (`cacto_ddp_backward`), one thread per episode,
-along any recorded trajectory — a TO solution handed over from the host, or the policy rollouts
-of `RL_AC.rollout_batch` (the TO warm start, RL.py:197-233).
+`TO_System_Solve` (TO.py:37-100) states one NLP per episode with CasADi and solves it with IPOPT.
+The problem is unconstrained apart from the dynamics and the fixed initial state (the control
+bounds are the penalty w_b (u/u_max)^10 inside the cost, environment_TO.py:201-206), so here it is
+solved by a batched iLQR (`cacto_to_solve`): single shooting, Gauss-Newton DDP with first-order
+dynamics and exact cost Hessians, a backtracking line search and Levenberg-Marquardt
+regularisation, all episodes of a main.py iteration in one call, float64 throughout. The cost is
+the TO cost (-Env.reward; for UR5 plus the bound penalty that environment_TO.py has and
+UR5.reward leaves out), the dynamics Env.simulate. It is a local method like IPOPT: both stop at a
+stationary point of the same problem, not necessarily the same one.
+
+  solve_batch            the solver on device tensors
+  backward_gains_batch   one regularised backward pass (gains k, K, expected decrease, PD verdict)
+  forward_batch          one closed-loop roll-out with step size alpha
+  TO_System_Solve        the reference's per-episode signature and return tuple (TO.py:100)
+  TO_Solve               TO.py:102-117: + the time column and the Sobolev label dV/dx
+  backward_pass[_batch]  TO.backward_pass (TO.py:119-202, `cacto_ddp_backward`) along any recorded
+                         trajectory — a TO solution or the policy roll-outs of RL_AC.rollout_batch
 """
+import ctypes as C
+
 import numpy as np
 import torch
 
 from . import _lib as L
 from .system import DEVICE, dptr, stream
+
+CONVERGED, MAXITER, FAILED = L.CACTO_TO_CONVERGED, L.CACTO_TO_MAXITER, L.CACTO_TO_FAILED
+
+# max_iter backward passes, step sizes 2^0..2^-max_ls, stop at max_t |Q_u|_inf <= gtol, the Armijo
+# fraction, mu x10 (from mu_min) on failure and /10 on success, poll the device every 8 iterations
+DEFAULT_CFG = dict(max_iter=400, max_ls=10, gtol=1e-4, armijo=1e-4, mu_min=1e-6, mu_up=10.0, mu_down=10.0,
+                   mu_max=1e10, poll_every=8)
+
+
+def make_cfg(cfg=None):
+    vals = dict(DEFAULT_CFG)
+    vals.update(cfg or {})
+    unknown = set(vals) - set(DEFAULT_CFG)
+    if unknown:
+        raise ValueError("unknown TO settings: %s" % sorted(unknown))
+    c = L.ToCfg()
+    for k, v in vals.items():
+        setattr(c, k, v)
+    return c
 
 
 class TO:
@@ -21,6 +53,106 @@ class TO:
         self.w_S = w_S
         self.sys = env.sys
 
+    # ------------------------------------------------------------------ the solver
+    def solve_batch(self, S0, U_init, nsteps, cfg=None, out=None):
+        """cacto_to_solve. S0 [E, ns] f64, U_init [E, ldU, na] f64 (the warm start's controls),
+        nsteps [E] int32 (Te; < 0 skips the episode), all on the device; cfg: a dict over
+        DEFAULT_CFG. Returns a dict of device tensors S [E, ldS, ns], U [E, ldU, na], step_cost
+        [E, ldS], status [E] (CONVERGED / MAXITER / FAILED), iters [E], J [E, 2] (warm start's cost,
+        final cost), ldS = ldU + 1. Rows past Te, and every row of a skipped episode, keep what
+        `out` (the same dict, optional) held — zeros (status -1) when it is not given."""
+        E, ldU = U_init.shape[0], U_init.shape[1]
+        ldS = ldU + 1
+        ns, na = self.conf.nb_state, self.conf.nb_action
+        if out is None:
+            f64 = dict(dtype=torch.float64, device=DEVICE)
+            out = dict(S=torch.zeros(E, ldS, ns, **f64), U=torch.zeros(E, ldU, na, **f64),
+                       step_cost=torch.zeros(E, ldS, **f64),
+                       status=torch.full((E,), -1, dtype=torch.int32, device=DEVICE),
+                       iters=torch.zeros(E, dtype=torch.int32, device=DEVICE), J=torch.zeros(E, 2, **f64))
+        nbytes = int(L.lib().raw("cacto_to_workspace_bytes")(self.sys.handle, E, ldS))
+        ws = getattr(self, "_to_ws", None)
+        if ws is None or ws.numel() < nbytes:
+            ws = self._to_ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=DEVICE)
+        c = cfg if isinstance(cfg, L.ToCfg) else make_cfg(cfg)
+        L.lib().call("cacto_to_solve", self.sys.handle, dptr(S0, torch.float64), dptr(U_init, torch.float64), ldU,
+                     dptr(nsteps, torch.int32), E, ldS, C.byref(c), dptr(out["S"], torch.float64),
+                     dptr(out["U"], torch.float64), dptr(out["step_cost"], torch.float64),
+                     dptr(out["status"], torch.int32), dptr(out["iters"], torch.int32), dptr(out["J"], torch.float64),
+                     dptr(ws), nbytes, stream())
+        return out
+
+    def backward_gains_batch(self, S_traj, U_traj, nsteps, mu=0.0):
+        """cacto_to_backward_gains along S_traj [E, ldS, ns], U_traj [E, ldU, na]: a dict k [E, ldU,
+        na], K [E, ldU, na, nx], dJ [E, 3] = (sum k^T Q_u, 1/2 sum k^T Q_uu k, max |Q_u|), pd [E]
+        (-1: Q_uu + mu I positive definite at every step, else the step where it was not; nothing
+        below that step is defined)."""
+        E, ldS, ldU = S_traj.shape[0], S_traj.shape[1], U_traj.shape[1]
+        ns, na = self.conf.nb_state, self.conf.nb_action
+        f64 = dict(dtype=torch.float64, device=DEVICE)
+        out = dict(k=torch.zeros(E, ldU, na, **f64), K=torch.zeros(E, ldU, na, ns - 1, **f64),
+                   dJ=torch.zeros(E, 3, **f64), pd=torch.full((E,), -1, dtype=torch.int32, device=DEVICE))
+        L.lib().call("cacto_to_backward_gains", self.sys.handle, dptr(S_traj, torch.float64), ldS,
+                     dptr(U_traj, torch.float64), ldU, dptr(nsteps, torch.int32), E, float(mu), dptr(out["k"]),
+                     dptr(out["K"]), dptr(out["dJ"]), dptr(out["pd"]), stream())
+        return out
+
+    def forward_batch(self, S_traj, U_traj, k, K, nsteps, alpha=1.0):
+        """cacto_to_forward: u_t = ubar_t + alpha k_t + K_t (x_t - xbar_t) rolled out from S_traj[:, 0].
+        Returns (S_new, U_new, cost_new [E, ldS]); k = K = None gives the open-loop roll-out."""
+        E, ldS, ldU = S_traj.shape[0], S_traj.shape[1], U_traj.shape[1]
+        S_new, U_new = torch.zeros_like(S_traj), torch.zeros_like(U_traj)
+        cost = torch.zeros(E, ldS, dtype=torch.float64, device=DEVICE)
+        L.lib().call("cacto_to_forward", self.sys.handle, dptr(S_traj, torch.float64), ldS,
+                     dptr(U_traj, torch.float64), ldU, dptr(k, torch.float64), dptr(K, torch.float64),
+                     dptr(nsteps, torch.int32), E, float(alpha), dptr(S_new), dptr(U_new), dptr(cost), stream())
+        return S_new, U_new, cost
+
+    # ------------------------------------------------------------------ the reference's signatures
+    def TO_System_Solve(self, ICS_state, init_TO_states, init_TO_controls, T, cfg=None, accept_maxiter=False):
+        """TO.py:37-100 for one episode: returns (success_flag, TO_controls [T, na], TO_states
+        [T+1, nx], TO_ee_pos_arr [T+1, 3], TO_total_cost, TO_step_cost [T+1]) as numpy float64.
+        The solver is single shooting: the warm start is its controls rolled out from ICS_state, so
+        init_TO_states is accepted and ignored. Controls may be float32 (a roll-out's actions);
+        they are converted to float64. success_flag is 1 only when the solver converged (or, with
+        accept_maxiter, stopped at max_iter); otherwise the reference's failure branch: the last
+        iterate's controls and states, None for the EE positions, the total and the step costs."""
+        ns, na = self.conf.nb_state, self.conf.nb_action
+        T = int(T)
+        S0 = torch.as_tensor(np.asarray(ICS_state, dtype=np.float64).reshape(1, ns), device=DEVICE)
+        U = np.zeros((1, max(T, 1), na))
+        U[0, :T] = np.asarray(init_TO_controls, dtype=np.float64).reshape(-1, na)[:T]
+        out = self.solve_batch(S0, torch.as_tensor(U, device=DEVICE),
+                               torch.tensor([T], dtype=torch.int32, device=DEVICE), cfg=cfg)
+        status = int(out["status"][0].item())
+        states = out["S"][0, :T + 1]
+        TO_states = states[:, :ns - 1].cpu().numpy()
+        TO_controls = out["U"][0, :T].cpu().numpy()
+        if not (status == CONVERGED or (accept_maxiter and status == MAXITER)):
+            return 0, TO_controls, TO_states, None, None, None
+        EE = torch.empty(T + 1, 3, dtype=torch.float64, device=DEVICE)
+        L.lib().call("cacto_env_ee", self.sys.handle, dptr(states.contiguous()), dptr(EE), T + 1, stream())
+        return (1, TO_controls, TO_states, EE.cpu().numpy(), float(out["J"][0, 1].item()),
+                out["step_cost"][0, :T + 1].cpu().numpy())
+
+    def TO_Solve(self, ICS_state, init_TO_states, init_TO_controls, T, cfg=None, accept_maxiter=False):
+        """TO.py:102-117: (TO_controls, TO_states [T+1, ns] with the time column ICS time + dt * t,
+        success_flag, TO_ee_pos_arr, TO_step_cost, dVdx [T+1, ns]); dVdx from backward_pass
+        (mu = 1e-9) when w_S != 0, else zeros. On failure (None, None, 0, None, None, None)."""
+        flag, U, X, ee, _, step_cost = self.TO_System_Solve(ICS_state, init_TO_states, init_TO_controls, T, cfg=cfg,
+                                                            accept_maxiter=accept_maxiter)
+        if flag == 0:
+            return None, None, flag, None, None, None
+        T = int(T)
+        if self.w_S != 0:
+            dVdx = self.backward_pass(T + 1, X, U)
+        else:
+            dVdx = np.zeros((T + 1, self.conf.nb_state))
+        t0 = float(np.asarray(ICS_state, dtype=np.float64).reshape(-1)[-1])
+        X = np.concatenate((X, t0 + np.transpose(self.conf.dt * np.array([range(T + 1)]))), axis=1)
+        return U, X, flag, ee, step_cost, dVdx
+
+    # ------------------------------------------------------------------ Sobolev labels
     def backward_pass(self, T, TO_states, TO_controls, mu=1e-9):
         """TO.py:119-202 for one episode: T states s_0..s_{T-1} ([T, >= ns-1]; a time column is
         ignored), T-1 controls. Returns V_x [T, ns] (numpy float64, last column 0)."""

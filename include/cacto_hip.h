@@ -14,6 +14,10 @@
  *   cacto_rollout          RL_AC.create_TO_init loop RL.py:223-231 / PLOT.rollout plot_utils.py:245-279
  *   cacto_rollout_rewards  Env.step reward / get_end_effector_position over recorded trajectories
  *   cacto_ddp_backward     TO.backward_pass TO.py:119-202 (dV/dx Sobolev labels)
+ *   cacto_to_solve         TO.TO_System_Solve TO.py:37-100: the trajectory optimisation itself, as a
+ *                          batched iLQR on the same cost and dynamics (the reference: CasADi + IPOPT,
+ *                          one NLP per episode); cacto_to_backward_gains / cacto_to_forward are its
+ *                          two building blocks
  *   cacto_mlp_pack         (layout transform for the kernels; no reference counterpart)
  *   cacto_sys_set_critic_type  RL_AC.setup_model's critic_type choice RL.py:65-76 ('sine' /
  *                          'sine-elu', NeuralNetwork.py:80-108)
@@ -41,7 +45,10 @@
  *     and enqueues no host synchronisation, so sequences can be captured into a hipGraph.
  *     cacto_update_n[_per] also use a side stream owned by the handle, joined back into `stream`
  *     before they return; cacto_ddp_backward (car_park, revolute chains) grows a device workspace
- *     owned by the handle (a hipMalloc, so warm it up before capturing).
+ *     owned by the handle (a hipMalloc, so warm it up before capturing), and so does
+ *     cacto_to_backward_gains. cacto_to_solve with cfg.poll_every > 0 on car_park and the revolute
+ *     chains synchronises the stream every poll_every iterations (it reads a device counter of
+ *     finished episodes to stop early); with poll_every == 0 it never synchronises.
  *   - Return 0 on success, <0 on error; cacto_last_error() returns a thread-local message.
  *     No C++ exception crosses the ABI.
  *   - Handles (cacto_sys) are created/destroyed by the caller; concurrent calls on one handle are
@@ -397,6 +404,72 @@ int cacto_rollout_rewards(const cacto_sys* sys, const double* S_traj_d, const fl
  * (dynamics, reward) combination outside the six systems returns CACTO_EUNSUPPORTED. */
 int cacto_ddp_backward(const cacto_sys* sys, const double* S_traj_d, int64_t ldS, const double* U_traj_d,
                        int64_t ldU, const int32_t* nsteps_d, int n_ep, double mu, double* dVdx_d, void* stream);
+
+/* ---------------------------------------------------------------- trajectory optimisation - */
+
+/* TO_System_Solve (TO.py:37-100) as a batched iLQR: single shooting on the reference's problem
+ * (cost = -reward with the control bounds as the penalty w_b (u/u_max)^10, environment_TO.py; the
+ * environment's dynamics; fixed initial state), Gauss-Newton DDP with first-order dynamics and
+ * exact cost Hessians, a backtracking line search and Levenberg-Marquardt regularisation. All
+ * float64. Layouts as cacto_ddp_backward: S [n_ep, ldS, ns] with the time column, U [n_ep, ldU, na],
+ * nsteps_d[e] = Te (Te + 1 states, Te controls; needs Te < ldS and Te <= ldU); Te < 0 skips episode
+ * e: nothing of it is read or written. nx = ns - 1. The cost of UR5 is -reward plus the bound
+ * penalty scale w6 w_b sum (u/u_max)^10 that environment_TO.py:731-758 has and UR5.reward leaves
+ * to reward_batch; for the other systems it is -Env.reward. */
+
+enum cacto_to_status {
+  CACTO_TO_CONVERGED = 0, /* max_t |Q_u,t|_inf <= gtol */
+  CACTO_TO_MAXITER = 1,   /* max_iter backward passes without convergence */
+  CACTO_TO_FAILED = 2     /* the regulariser passed mu_max (or the warm start's cost is not finite) */
+};
+
+typedef struct {
+  int32_t max_iter; /* backward passes per episode */
+  int32_t max_ls;   /* step sizes alpha = 2^-j, j = 0..max_ls (<= 63) */
+  double gtol;      /* convergence: max_t |Q_u,t|_inf <= gtol */
+  double armijo;    /* accept when J - J(alpha) >= armijo * -(alpha dJ1 + alpha^2 dJ2) and J(alpha) <= J */
+  double mu_min, mu_up, mu_down, mu_max; /* mu <- max(mu mu_up, mu_min) on failure (> mu_max: FAILED);
+                                          * mu <- mu / mu_down on acceptance, 0 once below mu_min. Starts at 0. */
+  int32_t poll_every; /* > 0: the host reads the finished-episode counter every so many iterations */
+  int32_t pad;
+} cacto_to_cfg;
+
+/* One regularised backward pass along given trajectories (cost convention, l_xu = 0):
+ *   Qbar_uu = Q_uu + mu I, k = -Qbar_uu^-1 Q_u, K = -Qbar_uu^-1 Q_ux,
+ *   V_x = Q_x + K^T Q_uu k + K^T Q_u + Q_ux^T k, V_xx = Q_xx + K^T Q_uu K + K^T Q_ux + Q_ux^T K
+ *   (symmetrised); terminal node: terminal weights at S[Te].
+ * k_d [n_ep, ldU, na], K_d [n_ep, ldU, na, nx]; dJ_d [n_ep, 3] = (sum k^T Q_u, 1/2 sum k^T Q_uu k,
+ * max_t |Q_u,t|_inf) with the unregularised Q_uu; pd_d [n_ep] int32 = -1 when Qbar_uu was positive
+ * definite at every step, else the step at which its Cholesky met a pivot <= 0 or a non-finite one
+ * (the pass stops there: gains below that step and dJ are undefined). */
+int cacto_to_backward_gains(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d, int64_t ldU,
+                            const int32_t* nsteps_d, int n_ep, double mu, double* k_d, double* K_d, double* dJ_d,
+                            int32_t* pd_d, void* stream);
+
+/* One closed-loop roll-out: u_t = ubar_t + alpha k_t + K_t (x_t - xbar_t), x_{t+1} = Env.simulate
+ * (float64). S_new_d [n_ep, ldS, ns] (time column t0 + dt t), U_new_d [n_ep, ldU, na], cost_new_d
+ * [n_ep, ldS]: running cost at nodes 0..Te-1, terminal cost at node Te (TO_step_cost, TO.py:84-89).
+ * S_new_d / U_new_d may be S_d / U_d (in place). k_d, K_d NULL: the open-loop roll-out of U_d. */
+int cacto_to_forward(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d, int64_t ldU,
+                     const double* k_d, const double* K_d, const int32_t* nsteps_d, int n_ep, double alpha,
+                     double* S_new_d, double* U_new_d, double* cost_new_d, void* stream);
+
+size_t cacto_to_workspace_bytes(const cacto_sys* sys, int n_ep, int64_t ldS);
+
+/* The solver. S0_d [n_ep, ns] initial states (with time), U_init_d [n_ep, ldU, na] warm start.
+ * Outputs: S_d [n_ep, ldS, ns], U_d [n_ep, ldU, na], step_cost_d [n_ep, ldS], status_d [n_ep] int32
+ * (cacto_to_status), iters_d [n_ep] int32 (backward passes used), J_d [n_ep, 2] = (cost of the warm
+ * start's roll-out, final cost; J[1] <= J[0]). Rows past Te are untouched. Te == 0: S[0] = s0, its
+ * terminal cost, CONVERGED, 0 iterations. Requires w_terminal[6] == 0 (CACTO_EUNSUPPORTED otherwise;
+ * true of every shipped conf). ws_d: cacto_to_workspace_bytes(sys, n_ep, ldS) bytes. ldU <= ldS.
+ * Single integrator, car, double integrator: one persistent kernel, one thread per episode, no host
+ * round trip (poll_every is not used). car_park, manipulator, UR5: max_iter iterations of
+ * derivative kernels + a one-wave-per-episode backward pass + a line-search kernel, issued by the
+ * host; poll_every > 0 stops issuing once every episode has finished (see Conventions). */
+int cacto_to_solve(const cacto_sys* sys, const double* S0_d, const double* U_init_d, int64_t ldU,
+                   const int32_t* nsteps_d, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h, double* S_d,
+                   double* U_d, double* step_cost_d, int32_t* status_d, int32_t* iters_d, double* J_d, void* ws_d,
+                   size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- replay ------------------ */
 

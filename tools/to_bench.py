@@ -1,0 +1,92 @@
+"""Throughput of the batched iLQR trajectory optimiser (cacto_to_solve) on the double integrator:
+full-length episodes from Env.reset (the reference's main.py:225-230 draws), zero warm start, the
+full-solve settings of the tests (gtol 1e-4, max_iter 400, max_ls 10, armijo 1e-4, mu x10 / /10
+from 1e-6). Prints one JSON line: episodes/s, mean and max backward passes, the share per status.
+
+    python tools/to_bench.py [--episodes 4096] [--repeat 3] [--helper 8]
+
+--helper N also times tests/ilqr_ref.py (numpy, one core) on the first N of those episodes and
+reports its seconds per episode. Reported, not gated: there is no earlier figure to compare with,
+and the reference's IPOPT solve cannot run without CasADi.
+"""
+import argparse
+import json
+import os
+import random
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--system", default="double_integrator")
+    ap.add_argument("--episodes", type=int, default=4096)
+    ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--helper", type=int, default=0)
+    ap.add_argument("--poll-every", type=int, default=8)
+    ap.add_argument("--helper-only", action="store_true", help="time the helper alone (needs no GPU)")
+    args = ap.parse_args()
+
+    import ilqr_ref as R
+    from cacto_amd.confs import load_conf
+    from oracle import env as oenv
+
+    conf = load_conf(args.system)
+    rng = random.Random(0)
+    oe = oenv.make_env(conf)
+    S0 = np.array([oe.reset(rng) for _ in range(args.episodes)], dtype=np.float64)
+    Te = np.array([conf.NSTEPS - int(s[-1] / conf.dt) for s in S0], dtype=np.int32)
+    if args.helper_only:
+        print(json.dumps(dict(metric="to_helper_seconds_per_episode", system=args.system, **helper(R, args, S0, Te))))
+        return
+    import torch
+    from cacto_amd.environment import make_env
+    from cacto_amd.to import TO
+    to = TO(make_env(conf), conf)
+    cfg = dict(R.SOLVE_CFG, poll_every=args.poll_every)
+    dev = lambda a: torch.as_tensor(np.ascontiguousarray(a), device="cuda")  # noqa: E731
+    S0_d, Te_d = dev(S0), dev(Te)
+    U0_d = torch.zeros(args.episodes, int(Te.max()), conf.nb_action, dtype=torch.float64, device="cuda")
+    times = []
+    for _ in range(args.repeat + 1):        # the first run warms up (workspace, code objects)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = to.solve_batch(S0_d, U0_d, Te_d, cfg=cfg)
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t)
+    best = min(times[1:])
+    status, iters = out["status"].cpu().numpy(), out["iters"].cpu().numpy()
+    J = out["J"].cpu().numpy()
+    res = dict(metric="to_solve_episodes_per_s", system=args.system, episodes=args.episodes,
+               mean_steps=float(Te.mean()), seconds=best, seconds_all=times[1:], episodes_per_s=args.episodes / best,
+               iters_mean=float(iters.mean()), iters_max=int(iters.max()),
+               status_share=dict(converged=float((status == R.CONVERGED).mean()),
+                                 maxiter=float((status == R.MAXITER).mean()), failed=float((status == R.FAILED).mean())),
+               monotone=bool((J[:, 1] <= J[:, 0]).all()))
+    if args.helper > 0:
+        res.update(helper(R, args, S0, Te))
+        res["gpu_status_same_episodes"] = status[:args.helper].tolist()
+        res["gpu_iters_same_episodes"] = iters[:args.helper].tolist()
+    print(json.dumps(res))
+
+
+def helper(R, args, S0, Te):
+    P = R.Problem(args.system)
+    n = max(args.helper, 1)
+    t = time.perf_counter()
+    hs, hi = [], []
+    for e in range(n):
+        r = P.solve(S0[e], np.zeros((max(int(Te[e]), 1), P.m)), int(Te[e]))
+        hs.append(int(r["status"]))
+        hi.append(int(r["iters"]))
+    return dict(helper_seconds_per_episode=(time.perf_counter() - t) / n, helper_status=hs, helper_iters=hi,
+                helper_steps=[int(v) for v in Te[:n]])
+
+
+if __name__ == "__main__":
+    main()
