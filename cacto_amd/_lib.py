@@ -55,11 +55,12 @@ class ToCfg(C.Structure):
     _fields_ = [
         ("max_iter", C.c_int32), ("max_ls", C.c_int32), ("gtol", C.c_double), ("armijo", C.c_double),
         ("mu_min", C.c_double), ("mu_up", C.c_double), ("mu_down", C.c_double), ("mu_max", C.c_double),
-        ("poll_every", C.c_int32), ("pad", C.c_int32),
+        ("poll_every", C.c_int32), ("path", C.c_int32),
     ]
 
 
 CACTO_TO_CONVERGED, CACTO_TO_MAXITER, CACTO_TO_FAILED = 0, 1, 2
+CACTO_TO_PATH_DEFAULT, CACTO_TO_PATH_WAVE = 0, 1
 
 vp, i32, i64, dbl, flt, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_float, C.c_size_t
 _SIGS = {
@@ -114,6 +115,7 @@ _SIGS = {
     "cacto_to_backward_gains": (C.c_int, [vp, vp, i64, vp, i64, vp, C.c_int, C.c_double, vp, vp, vp, vp, vp]),
     "cacto_to_forward": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp, C.c_int, C.c_double, vp, vp, vp, vp]),
     "cacto_to_workspace_bytes": (sz, [vp, C.c_int, i64]),
+    "cacto_to_workspace_bytes_cfg": (sz, [vp, C.c_int, i64, C.POINTER(ToCfg)]),
     "cacto_to_solve": (C.c_int, [vp, vp, vp, i64, vp, C.c_int, i64, C.POINTER(ToCfg), vp, vp, vp, vp, vp, vp, vp, sz,
                                  vp]),
     "cacto_buffer_add": (C.c_int, [vp, vp, i64, i64, vp, i64, vp]),

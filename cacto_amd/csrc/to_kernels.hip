@@ -23,6 +23,9 @@
 // persistent kernel, one thread per episode, the whole iteration loop on the device. Trajectory
 // and gains live in the workspace in the [t][k][e] layout of DdpRec (a wave's lanes touch
 // consecutive addresses); episodes are handed out longest first so a wave's lanes have similar Te.
+// With cfg.path = CACTO_TO_PATH_WAVE: k_to_solve_wave, the same loop with one 64-lane workgroup
+// per episode (derivatives over the nodes, the recursion on one lane, every step size at once), for
+// per-episode calls and batches too small to fill the device with one thread per episode.
 // Split family (car_park, manipulator, UR5): per iteration the per-(episode, step) derivative
 // kernels of the label pass (fed a live copy of nsteps in which finished episodes are -1),
 // k_to_gains_wave (one wave per episode, operands in LDS, the M x M Cholesky on one lane) and
@@ -552,6 +555,209 @@ __global__ void __launch_bounds__(64) k_to_solve_thread(const SysDevice* __restr
   J_out[(size_t)e * 2 + 1] = J;
 }
 
+// Per-node record of the wave path: DdpRec's A, B, l_x, l_xx (here in the cost convention, the
+// signs already flipped) followed by l_u [M] and the diagonal of l_uu [M]. Layout [e][t][k]: one
+// episode's records are contiguous, a node's record is what the recursion reads in one go.
+template <int NJ>
+struct ToRec {
+  using RC = DdpRec<NJ>;
+  static constexpr int N = RC::N, M = RC::M;
+  static constexpr int LU = RC::R, LUU = LU + M, R = LUU + M;
+};
+
+// The record of node t of one closed-form episode (t == Te: l_x, l_xx of the terminal weights
+// only): the expressions and the order of to_backward_thread.
+template <int NJ>
+__device__ inline void to_node_record(const SysDevice& sd, const double* Minv, const Traj& cur, int t, int Te,
+                                      double* r) {
+  using TR = ToRec<NJ>;
+  using RC = DdpRec<NJ>;
+  constexpr int N = TR::N, M = TR::M;
+  const cacto_sys_params& p = sd.p;
+  double w[7], x[N], lx[N], lxx[N * N];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) w[k] = t == Te ? p.w_terminal[k] : p.w_running[k];
+#pragma unroll
+  for (int k = 0; k < N; ++k) x[k] = cur.S.at(t, k);
+  ddp_lx<NJ>(sd, w, x, lx, lxx);
+#pragma unroll
+  for (int k = 0; k < N; ++k) r[RC::LX + k] = -lx[k];
+#pragma unroll
+  for (int k = 0; k < N * N; ++k) r[RC::LXX + k] = -lxx[k];
+  if (t == Te) return;
+  double A[N * N], B[N * M];
+  ddp_jacobians<NJ>(sd, x, Minv, A, B);
+#pragma unroll
+  for (int k = 0; k < N * N; ++k) r[RC::A + k] = A[k];
+#pragma unroll
+  for (int k = 0; k < N * M; ++k) r[RC::B + k] = B[k];
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    double lu, luu;
+    to_lu(p, w[6], cur.U.at(t, j), j, &lu, &luu);
+    r[TR::LU + j] = lu;
+    r[TR::LUU + j] = luu;
+  }
+}
+
+// The Riccati recursion of one episode from its records, on one thread: to_backward_thread with
+// the derivatives read instead of evaluated. Returns -1, or the step at which Qbar_uu was not
+// positive definite. dJ [3] is reset here.
+template <int NJ>
+__device__ inline int to_backward_records(const double* rec, int Te, double mu, const Gains& g, double* dJ) {
+  using TR = ToRec<NJ>;
+  using RC = DdpRec<NJ>;
+  constexpr int N = TR::N, M = TR::M;
+  double Vx[N], Vxx[N * N];
+  {
+    const double* r = rec + (size_t)Te * TR::R;
+#pragma unroll
+    for (int k = 0; k < N; ++k) Vx[k] = r[RC::LX + k];
+#pragma unroll
+    for (int k = 0; k < N * N; ++k) Vxx[k] = r[RC::LXX + k];
+  }
+  dJ[0] = dJ[1] = dJ[2] = 0.0;
+  for (int i = Te - 1; i >= 0; --i) {
+    const double* r = rec + (size_t)i * TR::R;
+    double A[N * N], B[N * M], lx[N], lxx[N * N], lu[M], luu[M], kk[M], KK[M * N];
+#pragma unroll
+    for (int k = 0; k < N * N; ++k) {
+      A[k] = r[RC::A + k];
+      lxx[k] = r[RC::LXX + k];
+    }
+#pragma unroll
+    for (int k = 0; k < N * M; ++k) B[k] = r[RC::B + k];
+#pragma unroll
+    for (int k = 0; k < N; ++k) lx[k] = r[RC::LX + k];
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+      lu[j] = r[TR::LU + j];
+      luu[j] = r[TR::LUU + j];
+    }
+    if (!to_riccati_step<N, M>(A, B, lx, lxx, lu, luu, mu, Vx, Vxx, kk, KK, dJ)) return i;
+#pragma unroll
+    for (int j = 0; j < M; ++j) g.k.at(i, j) = kk[j];
+#pragma unroll
+    for (int q = 0; q < M * N; ++q) g.K.at(i, q) = KK[q];
+  }
+  return -1;
+}
+
+// The solver of the closed-form family with one 64-lane workgroup per episode (cfg.path =
+// CACTO_TO_PATH_WAVE): the algorithm of k_to_solve_thread, the whole loop on the device. Per pass
+// the lanes stride over the nodes for the derivative records, lane 0 runs the Riccati recursion
+// from them in to_backward_thread's operation order, lane j <= max_ls evaluates the cost of
+// alpha = 2^-j without storing it, and the lane of the smallest admissible j (by definition what
+// sequential backtracking picks) rolls that step out in place. mu, J, status and the iteration
+// count are held by every lane alike, so all branches on them are uniform. The trajectory and the
+// node costs live in the caller's S / U / step_cost (rows past Te are never touched); ws: gains k
+// [n_ep][ldS][na], K [n_ep][ldS][na*nx]; rec_ws: the records [n_ep][ldS][ToRec::R].
+template <int NJ>
+__global__ void __launch_bounds__(64) k_to_solve_wave(const SysDevice* __restrict__ sdp, const double* __restrict__ S0,
+                                                       const double* U_init, int64_t ldU,
+                                                       const int32_t* __restrict__ nsteps, int n_ep, int64_t ldS,
+                                                       ToCfgDev cfg, const int32_t* __restrict__ order, double* ws,
+                                                       double* rec_ws, double* S_out, double* U_out, double* cost_out,
+                                                       int32_t* __restrict__ status_out, int32_t* __restrict__ iters_out,
+                                                       double* __restrict__ J_out) {
+  using TR = ToRec<NJ>;
+  constexpr int N = DdpDims<NJ>::N, M = DdpDims<NJ>::M, ns = N + 1;
+  __shared__ double sPass[4];  // dJ [3] of the backward pass; the cost of the roll-out just stored
+  __shared__ int sPd;
+  const int lane = threadIdx.x;
+  const int e = order[blockIdx.x];
+  const int Te = nsteps[e];
+  if (Te < 0) return;  // every exit up to the loop is uniform over the workgroup
+  if (!to_valid_len(Te, ldS, ldU)) {
+    if (lane == 0) {
+      status_out[e] = CACTO_TO_FAILED;
+      iters_out[e] = 0;
+    }
+    return;
+  }
+  const SysDevice& sd = *sdp;
+  const size_t L = (size_t)ldS;
+  const Traj cur = api_traj<NJ>(S_out, ldS, U_out, ldU, e);
+  const View cost{cost_out + (size_t)e * ldS, 1, 1};
+  double* wk = ws + (size_t)e * L * (M + M * N);
+  const Gains g{View{wk, (size_t)M, 1}, View{wk + L * M, (size_t)M * N, 1}};
+  double* rec = rec_ws + (size_t)e * L * TR::R;
+  // the warm start: U_init rolled out from s0
+  if (lane == 0)
+#pragma unroll
+    for (int k = 0; k < ns; ++k) cur.S.at(0, k) = S0[(size_t)e * ns + k];
+  for (int t = lane; t < Te; t += 64)
+#pragma unroll
+    for (int j = 0; j < M; ++j) cur.U.at(t, j) = U_init[((size_t)e * ldU + t) * M + j];
+  __syncthreads();
+  if (lane == 0) {
+    const Gains none{View{nullptr, 0, 0}, View{nullptr, 0, 0}};
+    sPass[3] = to_forward_thread<NJ, true>(sd, cur, none, Te, 0.0, cur, cost);
+  }
+  __syncthreads();
+  double J = sPass[3];
+  const double J0 = J;
+  int status = CACTO_TO_MAXITER, iters = 0;
+  if (Te == 0) status = CACTO_TO_CONVERGED;
+  if (!isfinite(J)) status = CACTO_TO_FAILED;
+  if (status == CACTO_TO_MAXITER) {
+    double Minv[NJ > 0 ? M * M : 1], q0[NJ > 0 ? NJ : 1];
+    if constexpr (NJ > 0) {
+#pragma unroll
+      for (int i = 0; i < NJ; ++i) q0[i] = cur.S.at(0, i);
+      to_minv<NJ>(sd, q0, Minv);
+    }
+    double mu = 0.0, dJ[3];
+    const double alpha = ldexp(1.0, -lane);
+    for (int it = 0; it < cfg.max_iter; ++it) {
+      ++iters;
+      for (int t = lane; t <= Te; t += 64) to_node_record<NJ>(sd, Minv, cur, t, Te, rec + (size_t)t * TR::R);
+      __syncthreads();
+      if (lane == 0) {
+        double d[3];
+        sPd = to_backward_records<NJ>(rec, Te, mu, g, d);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) sPass[k] = d[k];
+      }
+      __syncthreads();
+      const int pd = sPd;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) dJ[k] = sPass[k];
+      bool raise = pd >= 0;
+      if (!raise) {
+        if (dJ[2] <= cfg.gtol) {
+          status = CACTO_TO_CONVERGED;
+          break;
+        }
+        bool ok = false;
+        if (lane <= cfg.max_ls) {
+          const double Jc = to_forward_thread<NJ, false>(sd, cur, g, Te, alpha, cur, cost);
+          ok = to_admissible(cfg, J, Jc, alpha, dJ);
+        }
+        const unsigned long long adm = __ballot(ok);
+        if (adm != 0ull) {
+          if (lane == __ffsll(adm) - 1) sPass[3] = to_forward_thread<NJ, true>(sd, cur, g, Te, alpha, cur, cost);
+          __syncthreads();
+          J = sPass[3];
+          to_lower_mu(cfg, &mu);
+        } else {
+          raise = true;
+        }
+      }
+      if (raise && to_raise_mu(cfg, &mu)) {
+        status = CACTO_TO_FAILED;
+        break;
+      }
+    }
+  }
+  if (lane == 0) {
+    status_out[e] = status;
+    iters_out[e] = iters;
+    J_out[(size_t)e * 2] = J0;
+    J_out[(size_t)e * 2 + 1] = J;
+  }
+}
+
 // The backward pass of the split family with gains: one wavefront per episode, every product's
 // outputs spread over the lanes, operands in LDS, the M x M Cholesky and its solves on lane 0.
 // rec: the derivative records of k_ddp_derivs / k_ddp_prim + k_ddp_tan + k_ddp_lx (the reward's:
@@ -871,6 +1077,8 @@ namespace {
 
 inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 
+inline bool to_path_ok(int path) { return path == CACTO_TO_PATH_DEFAULT || path == CACTO_TO_PATH_WAVE; }
+
 template <int NJ>
 constexpr bool to_split() {
   return NJ > 2 || NJ == -2;
@@ -960,13 +1168,15 @@ struct LaunchToForward {
 
 // Workspace of cacto_to_solve, in 256-byte aligned blocks.
 //   closed-form family: order [n_ep] + hist [ldS + 1] int32; trajectory, costs and gains [t][k][e]
+//                 (the wave path keeps its gains [e][t][k] at the head of that block and adds
+//                 the node records [n_ep, ldS, ToRec::R] behind it)
 //   split family: live [n_ep] int32 + done; mu, J [n_ep]; dJ [n_ep, 3]; pd [n_ep] int32; gains k
 //                 [n_ep, ldS, na], K [n_ep, ldS, na, nx]; the derivative records
 template <int NJ>
 struct ToWs {
   static constexpr int N = DdpDims<NJ>::N, M = DdpDims<NJ>::M;
   size_t off_i32, off_d, off_rec, bytes;
-  ToWs(int n_ep, int64_t ldS) {
+  ToWs(int n_ep, int64_t ldS, int path) {
     const size_t E = (size_t)n_ep, L = (size_t)ldS;
     off_i32 = 0;
     if constexpr (to_split<NJ>()) {
@@ -978,14 +1188,18 @@ struct ToWs {
       off_d = align256((E + L + 1) * sizeof(int32_t));
       off_rec = 0;
       bytes = off_d + align256(E * L * (size_t)(N + 1 + M + 1 + M + M * N) * sizeof(double));
+      if (path == CACTO_TO_PATH_WAVE) {
+        off_rec = bytes;
+        bytes += align256(E * L * (size_t)ToRec<NJ>::R * sizeof(double));
+      }
     }
   }
 };
 
 template <int NJ>
 struct LaunchToBytes {
-  static int run(int n_ep, int64_t ldS, size_t* out) {
-    if constexpr (DdpDims<NJ>::ok) *out = ToWs<NJ>(n_ep, ldS).bytes;
+  static int run(int n_ep, int64_t ldS, int path, size_t* out) {
+    if constexpr (DdpDims<NJ>::ok) *out = ToWs<NJ>(n_ep, ldS, path).bytes;
     return CACTO_OK;
   }
 };
@@ -997,8 +1211,10 @@ struct LaunchToSolve {
                  int32_t* iters, double* J, void* ws, size_t ws_bytes, hipStream_t st) {
     if (!to_supported<NJ>(sys, "cacto_to_solve")) return CACTO_EUNSUPPORTED;
     if constexpr (DdpDims<NJ>::ok) {
-      const ToWs<NJ> lay(n_ep, ldS);
-      CACTO_REQUIRE(ws_bytes >= lay.bytes, "cacto_to_solve: workspace smaller than cacto_to_workspace_bytes");
+      const ToWs<NJ> lay(n_ep, ldS, cfg->path);
+      CACTO_REQUIRE(ws_bytes >= lay.bytes,
+                    "cacto_to_solve: workspace smaller than cacto_to_workspace_bytes_cfg for this path "
+                    "(path 0: cacto_to_workspace_bytes)");
       const ToCfgDev c{cfg->max_iter, cfg->max_ls, cfg->gtol, cfg->armijo, cfg->mu_min, cfg->mu_up, cfg->mu_down, cfg->mu_max};
       char* base = static_cast<char*>(ws);
       constexpr int M = DdpDims<NJ>::M, N = DdpDims<NJ>::N;
@@ -1008,8 +1224,14 @@ struct LaunchToSolve {
         int32_t* hist = order + E;
         hipLaunchKernelGGL(k_to_order, dim3(1), dim3(256), 0, st, n, n_ep, ldS, order, hist);
         CACTO_CHECK_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_to_solve_thread<NJ>, dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S0, U_init, ldU, n,
-                           n_ep, ldS, c, order, reinterpret_cast<double*>(base + lay.off_d), S, U, cost, status, iters, J);
+        if (cfg->path == CACTO_TO_PATH_WAVE)
+          hipLaunchKernelGGL(k_to_solve_wave<NJ>, dim3(n_ep), dim3(64), 0, st, sys->dev, S0, U_init, ldU, n, n_ep, ldS, c,
+                             order, reinterpret_cast<double*>(base + lay.off_d),
+                             reinterpret_cast<double*>(base + lay.off_rec), S, U, cost, status, iters, J);
+        else
+          hipLaunchKernelGGL(k_to_solve_thread<NJ>, dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S0, U_init, ldU,
+                             n, n_ep, ldS, c, order, reinterpret_cast<double*>(base + lay.off_d), S, U, cost, status,
+                             iters, J);
         CACTO_CHECK_HIP(hipGetLastError());
       } else {
         int32_t* live = reinterpret_cast<int32_t*>(base + lay.off_i32);
@@ -1079,7 +1301,14 @@ extern "C" int cacto_to_forward(const cacto_sys* sys, const double* S_d, int64_t
 extern "C" size_t cacto_to_workspace_bytes(const cacto_sys* sys, int n_ep, int64_t ldS) {
   if (!sys || n_ep < 0 || ldS < 1) return 0;
   size_t out = 0;
-  if (dispatch_nj<LaunchToBytes>(sys->host.p, n_ep, ldS, &out) != CACTO_OK) return 0;
+  if (dispatch_nj<LaunchToBytes>(sys->host.p, n_ep, ldS, (int)CACTO_TO_PATH_DEFAULT, &out) != CACTO_OK) return 0;
+  return out;
+}
+
+extern "C" size_t cacto_to_workspace_bytes_cfg(const cacto_sys* sys, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h) {
+  if (!sys || !cfg_h || n_ep < 0 || ldS < 1 || !to_path_ok(cfg_h->path)) return 0;
+  size_t out = 0;
+  if (dispatch_nj<LaunchToBytes>(sys->host.p, n_ep, ldS, (int)cfg_h->path, &out) != CACTO_OK) return 0;
   return out;
 }
 
@@ -1088,6 +1317,8 @@ extern "C" int cacto_to_solve(const cacto_sys* sys, const double* S0_d, const do
                               double* U_d, double* step_cost_d, int32_t* status_d, int32_t* iters_d, double* J_d,
                               void* ws_d, size_t ws_bytes, void* stream) {
   CACTO_REQUIRE(cfg_h, "cacto_to_solve: null config");
+  // an unknown path is a property of the config alone: reported before the arguments are looked at
+  CACTO_REQUIRE(to_path_ok(cfg_h->path), "cacto_to_solve: bad config (path: CACTO_TO_PATH_DEFAULT or CACTO_TO_PATH_WAVE)");
   CACTO_REQUIRE(sys && S0_d && U_init_d && nsteps_d && S_d && U_d && step_cost_d && status_d && iters_d && J_d && ws_d &&
                     n_ep >= 0 && ldS >= 1 && ldU >= 0 && ldU <= ldS,
                 "cacto_to_solve: bad arguments (null pointer, n_ep < 0, ldS < 1, ldU < 0 or ldU > ldS)");

@@ -30,8 +30,12 @@ CONVERGED, MAXITER, FAILED = L.CACTO_TO_CONVERGED, L.CACTO_TO_MAXITER, L.CACTO_T
 
 # max_iter backward passes, step sizes 2^0..2^-max_ls, stop at max_t |Q_u|_inf <= gtol, the Armijo
 # fraction, mu x10 (from mu_min) on failure and /10 on success, poll the device every 8 iterations
+# path: which kernels solve the single integrator, the car and the double integrator. 0 / "default":
+# one thread per episode (large batches); 1 / "wave": one 64-lane workgroup per episode (per-episode
+# calls and batches of a few hundred). The other systems run one wave per episode either way.
 DEFAULT_CFG = dict(max_iter=400, max_ls=10, gtol=1e-4, armijo=1e-4, mu_min=1e-6, mu_up=10.0, mu_down=10.0,
-                   mu_max=1e10, poll_every=8)
+                   mu_max=1e10, poll_every=8, path=0)
+PATHS = {"default": L.CACTO_TO_PATH_DEFAULT, "wave": L.CACTO_TO_PATH_WAVE}
 
 
 def make_cfg(cfg=None):
@@ -40,6 +44,10 @@ def make_cfg(cfg=None):
     unknown = set(vals) - set(DEFAULT_CFG)
     if unknown:
         raise ValueError("unknown TO settings: %s" % sorted(unknown))
+    if isinstance(vals["path"], str):
+        if vals["path"] not in PATHS:
+            raise ValueError("unknown TO path %r (one of %s, or 0 / 1)" % (vals["path"], sorted(PATHS)))
+        vals["path"] = PATHS[vals["path"]]
     c = L.ToCfg()
     for k, v in vals.items():
         setattr(c, k, v)
@@ -70,11 +78,12 @@ class TO:
                        step_cost=torch.zeros(E, ldS, **f64),
                        status=torch.full((E,), -1, dtype=torch.int32, device=DEVICE),
                        iters=torch.zeros(E, dtype=torch.int32, device=DEVICE), J=torch.zeros(E, 2, **f64))
-        nbytes = int(L.lib().raw("cacto_to_workspace_bytes")(self.sys.handle, E, ldS))
+        c = cfg if isinstance(cfg, L.ToCfg) else make_cfg(cfg)
+        # 0 for a path the library does not know: cacto_to_solve then reports the bad config
+        nbytes = int(L.lib().raw("cacto_to_workspace_bytes_cfg")(self.sys.handle, E, ldS, C.byref(c)))
         ws = getattr(self, "_to_ws", None)
         if ws is None or ws.numel() < nbytes:
             ws = self._to_ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=DEVICE)
-        c = cfg if isinstance(cfg, L.ToCfg) else make_cfg(cfg)
         L.lib().call("cacto_to_solve", self.sys.handle, dptr(S0, torch.float64), dptr(U_init, torch.float64), ldU,
                      dptr(nsteps, torch.int32), E, ldS, C.byref(c), dptr(out["S"], torch.float64),
                      dptr(out["U"], torch.float64), dptr(out["step_cost"], torch.float64),

@@ -431,8 +431,15 @@ typedef struct {
   double mu_min, mu_up, mu_down, mu_max; /* mu <- max(mu mu_up, mu_min) on failure (> mu_max: FAILED);
                                           * mu <- mu / mu_down on acceptance, 0 once below mu_min. Starts at 0. */
   int32_t poll_every; /* > 0: the host reads the finished-episode counter every so many iterations */
-  int32_t pad;
+  int32_t path;       /* enum cacto_to_path; any other value: CACTO_EINVAL */
 } cacto_to_cfg;
+
+/* Which kernels cacto_to_solve runs; the algorithm, cost, dynamics and line-search rule are the same. */
+enum cacto_to_path {
+  CACTO_TO_PATH_DEFAULT = 0, /* single integrator, car, double integrator: one thread per episode */
+  CACTO_TO_PATH_WAVE = 1     /* those systems: one 64-lane workgroup per episode (small batches, per-episode
+                              * calls). car_park, manipulator, UR5 already run one wave per episode: as 0. */
+};
 
 /* One regularised backward pass along given trajectories (cost convention, l_xu = 0):
  *   Qbar_uu = Q_uu + mu I, k = -Qbar_uu^-1 Q_u, K = -Qbar_uu^-1 Q_ux,
@@ -454,16 +461,22 @@ int cacto_to_forward(const cacto_sys* sys, const double* S_d, int64_t ldS, const
                      const double* k_d, const double* K_d, const int32_t* nsteps_d, int n_ep, double alpha,
                      double* S_new_d, double* U_new_d, double* cost_new_d, void* stream);
 
+/* Workspace of cacto_to_solve: for cfg.path = CACTO_TO_PATH_DEFAULT, and for the path of a given
+ * config (CACTO_TO_PATH_WAVE adds the per-node derivative records of the closed-form family).
+ * 0 on bad arguments or an unknown path. */
 size_t cacto_to_workspace_bytes(const cacto_sys* sys, int n_ep, int64_t ldS);
+size_t cacto_to_workspace_bytes_cfg(const cacto_sys* sys, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h);
 
 /* The solver. S0_d [n_ep, ns] initial states (with time), U_init_d [n_ep, ldU, na] warm start.
  * Outputs: S_d [n_ep, ldS, ns], U_d [n_ep, ldU, na], step_cost_d [n_ep, ldS], status_d [n_ep] int32
  * (cacto_to_status), iters_d [n_ep] int32 (backward passes used), J_d [n_ep, 2] = (cost of the warm
  * start's roll-out, final cost; J[1] <= J[0]). Rows past Te are untouched. Te == 0: S[0] = s0, its
  * terminal cost, CONVERGED, 0 iterations. Requires w_terminal[6] == 0 (CACTO_EUNSUPPORTED otherwise;
- * true of every shipped conf). ws_d: cacto_to_workspace_bytes(sys, n_ep, ldS) bytes. ldU <= ldS.
- * Single integrator, car, double integrator: one persistent kernel, one thread per episode, no host
- * round trip (poll_every is not used). car_park, manipulator, UR5: max_iter iterations of
+ * true of every shipped conf). ws_d: cacto_to_workspace_bytes_cfg(sys, n_ep, ldS, cfg_h) bytes
+ * (path 0: cacto_to_workspace_bytes). ldU <= ldS.
+ * Single integrator, car, double integrator: one persistent kernel, no host round trip (poll_every
+ * is not used): one thread per episode, or with cfg.path = CACTO_TO_PATH_WAVE one 64-lane workgroup
+ * per episode (derivatives over the nodes, every step size of the line search at once). car_park, manipulator, UR5: max_iter iterations of
  * derivative kernels + a one-wave-per-episode backward pass + a line-search kernel, issued by the
  * host; poll_every > 0 stops issuing once every episode has finished (see Conventions). */
 int cacto_to_solve(const cacto_sys* sys, const double* S0_d, const double* U_init_d, int64_t ldU,

@@ -3,7 +3,11 @@ full-length episodes from Env.reset (the reference's main.py:225-230 draws), zer
 full-solve settings of the tests (gtol 1e-4, max_iter 400, max_ls 10, armijo 1e-4, mu x10 / /10
 from 1e-6). Prints one JSON line: episodes/s, mean and max backward passes, the share per status.
 
-    python tools/to_bench.py [--episodes 4096] [--repeat 3] [--helper 8]
+    python tools/to_bench.py [--system double_integrator] [--episodes 4096] [--path default|wave] [--repeat 3]
+                             [--helper 8]
+
+--path wave runs the one-wave-per-episode kernel of the closed-form family (cacto_to_cfg.path):
+the path for per-episode calls (--episodes 1) and batches of the reference's size (EP_UPDATE: 200).
 
 --helper N also times tests/ilqr_ref.py (numpy, one core) on the first N of those episodes and
 reports its seconds per episode. Reported, not gated: there is no earlier figure to compare with,
@@ -29,6 +33,7 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--helper", type=int, default=0)
     ap.add_argument("--poll-every", type=int, default=8)
+    ap.add_argument("--path", default="default", choices=["default", "wave"])
     ap.add_argument("--helper-only", action="store_true", help="time the helper alone (needs no GPU)")
     args = ap.parse_args()
 
@@ -48,10 +53,10 @@ def main():
     from cacto_amd.environment import make_env
     from cacto_amd.to import TO
     to = TO(make_env(conf), conf)
-    cfg = dict(R.SOLVE_CFG, poll_every=args.poll_every)
+    cfg = dict(R.SOLVE_CFG, poll_every=args.poll_every, path=args.path)
     dev = lambda a: torch.as_tensor(np.ascontiguousarray(a), device="cuda")  # noqa: E731
     S0_d, Te_d = dev(S0), dev(Te)
-    U0_d = torch.zeros(args.episodes, int(Te.max()), conf.nb_action, dtype=torch.float64, device="cuda")
+    U0_d = torch.zeros(args.episodes, max(int(Te.max()), 1), conf.nb_action, dtype=torch.float64, device="cuda")
     times = []
     for _ in range(args.repeat + 1):        # the first run warms up (workspace, code objects)
         torch.cuda.synchronize()
@@ -62,7 +67,7 @@ def main():
     best = min(times[1:])
     status, iters = out["status"].cpu().numpy(), out["iters"].cpu().numpy()
     J = out["J"].cpu().numpy()
-    res = dict(metric="to_solve_episodes_per_s", system=args.system, episodes=args.episodes,
+    res = dict(metric="to_solve_episodes_per_s", system=args.system, path=args.path, episodes=args.episodes,
                mean_steps=float(Te.mean()), seconds=best, seconds_all=times[1:], episodes_per_s=args.episodes / best,
                iters_mean=float(iters.mean()), iters_max=int(iters.max()),
                status_share=dict(converged=float((status == R.CONVERGED).mean()),
