@@ -59,6 +59,12 @@ class ToCfg(C.Structure):
     ]
 
 
+class ToPlan(C.Structure):
+    """cacto_to_plan: what cacto_to_solve runs for a system and a config (cacto_to_solve_plan)."""
+    _fields_ = [("on_device", C.c_int32), ("block_threads", C.c_int32), ("lds_bytes", C.c_int32),
+                ("launches_per_iter", C.c_int32)]
+
+
 CACTO_TO_CONVERGED, CACTO_TO_MAXITER, CACTO_TO_FAILED = 0, 1, 2
 CACTO_TO_PATH_DEFAULT, CACTO_TO_PATH_WAVE = 0, 1
 
@@ -118,6 +124,7 @@ _SIGS = {
     "cacto_to_workspace_bytes_cfg": (sz, [vp, C.c_int, i64, C.POINTER(ToCfg)]),
     "cacto_to_solve": (C.c_int, [vp, vp, vp, i64, vp, C.c_int, i64, C.POINTER(ToCfg), vp, vp, vp, vp, vp, vp, vp, sz,
                                  vp]),
+    "cacto_to_solve_plan": (C.c_int, [vp, C.POINTER(ToCfg), C.POINTER(ToPlan)]),
     "cacto_buffer_add": (C.c_int, [vp, vp, i64, i64, vp, i64, vp]),
     "cacto_rl_solve_add": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp, C.c_int, C.c_int, i64, C.c_int, C.c_int, vp,
                                      i64, i64, vp, vp]),

@@ -385,6 +385,41 @@ struct DdpRec {
   static constexpr int A = 0, B = N * N, LX = B + N * M, LXX = LX + N, R = LXX + N * N;
 };
 
+// The body of k_ddp_derivs as a device function of one node, shared with the persistent solver of
+// to_kernels.hip; always inlined, so the kernel here is compiled as it was with the body written
+// out in it. xs / us: the node's state and control rows; rec: element 0 of the node's DdpRec
+// record, element k at [k * es] (es = n_ep in the [t][k][e] layout of the kernels here, 1 in a
+// per-episode [t][k] one): l_x, l_xx of the node, and A, B unless it is the terminal one.
+template <int NJ>
+__device__ __forceinline__ void ddp_derivs_node(const SysDevice& sd, const double* xs, const double* us, bool terminal,
+                                       double* rec, size_t es) {
+  using RC = DdpRec<NJ>;
+  constexpr int N = RC::N, M = RC::M;
+  double x[N], w[7];
+#pragma unroll
+  for (int k = 0; k < N; ++k) x[k] = xs[k];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) w[k] = terminal ? sd.p.w_terminal[k] : sd.p.w_running[k];
+  double lx[N], lxx[N * N];
+  ddp_lx<NJ>(sd, w, x, lx, lxx);
+#pragma unroll
+  for (int k = 0; k < N; ++k) rec[(size_t)(RC::LX + k) * es] = lx[k];
+#pragma unroll
+  for (int k = 0; k < N * N; ++k) rec[(size_t)(RC::LXX + k) * es] = lxx[k];
+  if (terminal) return;
+  double u[M], A[N * N], B[N * M];
+#pragma unroll
+  for (int k = 0; k < M; ++k) u[k] = us[k];
+  if constexpr (NJ > 2)
+    ddp_chain_jacobians<NJ>(sd, x, u, A, B);
+  else
+    ddp_jacobians<NJ>(sd, x, nullptr, A, B);
+#pragma unroll
+  for (int k = 0; k < N * N; ++k) rec[(size_t)(RC::A + k) * es] = A[k];
+#pragma unroll
+  for (int k = 0; k < N * M; ++k) rec[(size_t)(RC::B + k) * es] = B[k];
+}
+
 // One thread per (episode, step): the steps are independent given the trajectory, so the
 // hyper-dual work runs over every step of every episode at once (grid.y = step).
 template <int NJ>
@@ -393,37 +428,14 @@ __global__ void __launch_bounds__(64) k_ddp_derivs(const SysDevice* __restrict__
                                                     const int32_t* __restrict__ nsteps, int n_ep,
                                                     double* __restrict__ ws) {
   using RC = DdpRec<NJ>;
-  constexpr int N = RC::N, M = RC::M, ns = Dims<NJ>::NS, na = Dims<NJ>::NA;
+  constexpr int ns = Dims<NJ>::NS, na = Dims<NJ>::NA;
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   const int t = blockIdx.y;
   if (e >= n_ep) return;
   const int Te = nsteps[e];
   if (t > Te) return;  // also Te < 0: a dropped episode (main.py:236), skipped
-  const SysDevice& sd = *sdp;
-  double x[N], w[7];
-#pragma unroll
-  for (int k = 0; k < N; ++k) x[k] = S[((size_t)e * ldS + t) * ns + k];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) w[k] = t == Te ? sd.p.w_terminal[k] : sd.p.w_running[k];
-  double* rec = ws + (size_t)t * RC::R * n_ep + e;
-  double lx[N], lxx[N * N];
-  ddp_lx<NJ>(sd, w, x, lx, lxx);
-#pragma unroll
-  for (int k = 0; k < N; ++k) rec[(size_t)(RC::LX + k) * n_ep] = lx[k];
-#pragma unroll
-  for (int k = 0; k < N * N; ++k) rec[(size_t)(RC::LXX + k) * n_ep] = lxx[k];
-  if (t == Te) return;
-  double u[M], A[N * N], B[N * M];
-#pragma unroll
-  for (int k = 0; k < M; ++k) u[k] = U[((size_t)e * ldU + t) * na + k];
-  if constexpr (NJ > 2)
-    ddp_chain_jacobians<NJ>(sd, x, u, A, B);
-  else
-    ddp_jacobians<NJ>(sd, x, nullptr, A, B);
-#pragma unroll
-  for (int k = 0; k < N * N; ++k) rec[(size_t)(RC::A + k) * n_ep] = A[k];
-#pragma unroll
-  for (int k = 0; k < N * M; ++k) rec[(size_t)(RC::B + k) * n_ep] = B[k];
+  ddp_derivs_node<NJ>(*sdp, S + ((size_t)e * ldS + t) * ns, U + ((size_t)e * ldU + t) * na, t == Te,
+                      ws + (size_t)t * RC::R * n_ep + e, (size_t)n_ep);
 }
 
 // k_ddp_derivs for the revolute chains as three kernels, each with the registers of its own part

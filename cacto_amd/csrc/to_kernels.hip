@@ -26,11 +26,14 @@
 // With cfg.path = CACTO_TO_PATH_WAVE: k_to_solve_wave, the same loop with one 64-lane workgroup
 // per episode (derivatives over the nodes, the recursion on one lane, every step size at once), for
 // per-episode calls and batches too small to fill the device with one thread per episode.
-// Split family (car_park, manipulator, UR5): per iteration the per-(episode, step) derivative
+// Split family (car_park, manipulator, UR5), path 0: per iteration the per-(episode, step) derivative
 // kernels of the label pass (fed a live copy of nsteps in which finished episodes are -1),
 // k_to_gains_wave (one wave per episode, operands in LDS, the M x M Cholesky on one lane) and
 // k_to_linesearch (one thread per (episode, j): every step size at once, then the largest
-// admissible one — by definition what sequential backtracking picks).
+// admissible one — by definition what sequential backtracking picks), issued by the host. car_park
+// with cfg.path = CACTO_TO_PATH_WAVE: k_to_solve_split, the bodies of those kernels as device
+// functions run by one workgroup per episode, the whole loop on the device (the same numbers bit
+// for bit); the manipulator and UR5 run the host-issued loop under either path.
 #include "ddp_device.h"
 
 namespace cacto {
@@ -758,10 +761,183 @@ __global__ void __launch_bounds__(64) k_to_solve_wave(const SysDevice* __restric
   }
 }
 
-// The backward pass of the split family with gains: one wavefront per episode, every product's
-// outputs spread over the lanes, operands in LDS, the M x M Cholesky and its solves on lane 0.
-// rec: the derivative records of k_ddp_derivs / k_ddp_prim + k_ddp_tan + k_ddp_lx (the reward's:
-// l_x, l_xx change sign on load). mu_ep: per-episode mu (the solver) or nullptr (mu).
+// LDS of the backward pass of one split-family episode (operands, products, gains of one step)
+template <int NJ>
+struct ToGainsLds {
+  static constexpr int N = DdpRec<NJ>::N, M = DdpRec<NJ>::M;
+  double sA[N * N], sB[N * M], sLx[N], sLxx[N * N], sVx[N], sVxx[N * N], sU[M];
+  double sVA[N * N], sVB[N * M], sQx[N], sQu[M], sQxx[N * N], sQux[M * N], sQuu[M * M];
+  double sk[M], sK[M * N], sTk[M], sT[M * N], sW[N * N];
+  int sFail;
+};
+
+// The backward pass of one split-family episode with gains, run by a whole workgroup of BT threads
+// (lane: the thread's index in it): every product's outputs spread over the threads (one thread
+// forms one output, always in the same summation order, so the width does not change a number),
+// operands in LDS, the M x M Cholesky and its solves on thread 0. Every thread of the workgroup must
+// call it: the step loop's barriers are workgroup barriers and every branch around them is uniform.
+// rec: the episode's derivative records (the reward's: l_x, l_xx change sign on load), element k of
+// node t at rec[t * ts + k * es]. Ue, ke, Ke: the episode's controls [.][na] and gains [.][na],
+// [.][na][N]. Returns, on thread 0, pd = -1 or the step at which Qbar_uu was not positive definite,
+// and dJ [3]; the other threads' values mean nothing. The LDS is free again once every thread has left
+// and passed a barrier. No pointer here is __restrict__: the persistent solver reads what its own
+// workgroup wrote earlier in the same kernel.
+struct ToPass {
+  int pd;
+  double dJ[3];
+};
+template <int NJ, int BT>
+__device__ __forceinline__ ToPass to_gains_episode(ToGainsLds<NJ>& L, const cacto_sys_params& p, const double* Ue, int Te, double mu,
+                                        const double* rec_e, size_t ts, size_t es, double* ke, double* Ke, int lane) {
+  using RC = DdpRec<NJ>;
+  constexpr int N = RC::N, M = RC::M, na = Dims<NJ>::NA;
+  const double w6 = p.w_running[6];
+  {
+    const double* rec = rec_e + (size_t)Te * ts;
+    for (int k = lane; k < N; k += BT) L.sVx[k] = -rec[(size_t)(RC::LX + k) * es];
+    for (int k = lane; k < N * N; k += BT) L.sVxx[k] = -rec[(size_t)(RC::LXX + k) * es];
+    if (lane == 0) L.sFail = 0;
+  }
+  double d0 = 0.0, d1 = 0.0, d2 = 0.0;  // lane 0's
+  int pd = -1;
+  __syncthreads();
+  for (int i = Te - 1; i >= 0; --i) {
+    const double* rec = rec_e + (size_t)i * ts;
+    for (int k = lane; k < N * N; k += BT) {
+      L.sA[k] = rec[(size_t)(RC::A + k) * es];
+      L.sLxx[k] = -rec[(size_t)(RC::LXX + k) * es];
+    }
+    for (int k = lane; k < N * M; k += BT) L.sB[k] = rec[(size_t)(RC::B + k) * es];
+    for (int k = lane; k < N; k += BT) L.sLx[k] = -rec[(size_t)(RC::LX + k) * es];
+    for (int k = lane; k < M; k += BT) L.sU[k] = Ue[(size_t)i * na + k];
+    __syncthreads();
+    // V_xx A, V_xx B, Q_x = l_x + A^T V_x, Q_u = l_u + B^T V_x
+    for (int o = lane; o < N * N + N * M + N + M; o += BT) {
+      double s = 0.0;
+      if (o < N * N) {
+        const int r = o / N, c = o - r * N;
+#pragma unroll
+        for (int k = 0; k < N; ++k) s += L.sVxx[r * N + k] * L.sA[k * N + c];
+        L.sVA[o] = s;
+      } else if (o < N * N + N * M) {
+        const int q = o - N * N, r = q / M, c = q - r * M;
+#pragma unroll
+        for (int k = 0; k < N; ++k) s += L.sVxx[r * N + k] * L.sB[k * M + c];
+        L.sVB[q] = s;
+      } else if (o < N * N + N * M + N) {
+        const int r = o - N * N - N * M;
+#pragma unroll
+        for (int k = 0; k < N; ++k) s += L.sA[k * N + r] * L.sVx[k];
+        L.sQx[r] = L.sLx[r] + s;
+      } else {
+        const int j = o - N * N - N * M - N;
+        double lu, luu;
+        to_lu(p, w6, L.sU[j], j, &lu, &luu);
+#pragma unroll
+        for (int k = 0; k < N; ++k) s += L.sB[k * M + j] * L.sVx[k];
+        L.sQu[j] = lu + s;
+      }
+    }
+    __syncthreads();
+    // Q_xx = l_xx + A^T V_xx A, Q_ux = B^T V_xx A, Q_uu = l_uu + B^T V_xx B
+    for (int o = lane; o < N * N + M * N + M * M; o += BT) {
+      double s = 0.0;
+      if (o < N * N) {
+        const int r = o / N, c = o - r * N;
+#pragma unroll
+        for (int k = 0; k < N; ++k) s += L.sA[k * N + r] * L.sVA[k * N + c];
+        L.sQxx[o] = L.sLxx[o] + s;
+      } else if (o < N * N + M * N) {
+        const int q = o - N * N, j = q / N, c = q - j * N;
+#pragma unroll
+        for (int k = 0; k < N; ++k) s += L.sB[k * M + j] * L.sVA[k * N + c];
+        L.sQux[q] = s;
+      } else {
+        const int q = o - N * N - M * N, r = q / M, c = q - r * M;
+#pragma unroll
+        for (int k = 0; k < N; ++k) s += L.sB[k * M + r] * L.sVB[k * M + c];
+        double lu, luu = 0.0;
+        if (r == c) to_lu(p, w6, L.sU[r], r, &lu, &luu);
+        L.sQuu[q] = luu + s;
+      }
+    }
+    __syncthreads();
+    if (lane == 0) {
+      double Lm[M * M], kk[M];
+#pragma unroll
+      for (int q = 0; q < M * M; ++q) Lm[q] = L.sQuu[q] + (q % (M + 1) == 0 ? mu : 0.0);
+      if (!to_chol<M>(Lm)) {
+        L.sFail = 1;
+        pd = i;
+      } else {
+#pragma unroll
+        for (int j = 0; j < M; ++j) kk[j] = -L.sQu[j];
+        to_chol_solve<M>(Lm, kk, 1);
+#pragma unroll 1
+        for (int c = 0; c < N; ++c) {
+          double col[M];
+#pragma unroll
+          for (int j = 0; j < M; ++j) col[j] = -L.sQux[j * N + c];
+          to_chol_solve<M>(Lm, col, 1);
+#pragma unroll
+          for (int j = 0; j < M; ++j) L.sK[j * N + c] = col[j];
+        }
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+          double s = 0.0;
+#pragma unroll
+          for (int c = 0; c < M; ++c) s += L.sQuu[j * M + c] * kk[c];
+          L.sTk[j] = s;
+          L.sk[j] = kk[j];
+          d0 += kk[j] * L.sQu[j];
+          d1 += kk[j] * s;
+          d2 = fmax(d2, fabs(L.sQu[j]));
+        }
+      }
+    }
+    __syncthreads();
+    if (L.sFail) break;  // uniform
+    // T = Q_uu K; the gains to memory
+    for (int o = lane; o < M * N; o += BT) {
+      const int j = o / N, c = o - j * N;
+      double s = 0.0;
+#pragma unroll
+      for (int q = 0; q < M; ++q) s += L.sQuu[j * M + q] * L.sK[q * N + c];
+      L.sT[o] = s;
+      Ke[(size_t)i * na * N + o] = L.sK[o];
+    }
+    for (int j = lane; j < M; j += BT) ke[(size_t)i * na + j] = L.sk[j];
+    __syncthreads();
+    // V_x, and V_xx before symmetrisation
+    for (int o = lane; o < N * N + N; o += BT) {
+      if (o < N * N) {
+        const int r = o / N, c = o - r * N;
+        double s = L.sQxx[o];
+#pragma unroll
+        for (int j = 0; j < M; ++j)
+          s += L.sK[j * N + r] * (L.sT[j * N + c] + L.sQux[j * N + c]) + L.sQux[j * N + r] * L.sK[j * N + c];
+        L.sW[o] = s;
+      } else {
+        const int r = o - N * N;
+        double s = L.sQx[r];
+#pragma unroll
+        for (int j = 0; j < M; ++j) s += L.sK[j * N + r] * (L.sTk[j] + L.sQu[j]) + L.sQux[j * N + r] * L.sk[j];
+        L.sVx[r] = s;
+      }
+    }
+    __syncthreads();
+    for (int o = lane; o < N * N; o += BT) {
+      const int r = o / N, c = o - r * N;
+      L.sVxx[o] = 0.5 * (L.sW[o] + L.sW[c * N + r]);
+    }
+    __syncthreads();
+  }
+  return ToPass{pd, {d0, 0.5 * d1, d2}};
+}
+
+// cacto_to_backward_gains and the host-issued solver of the split family: one wavefront per
+// episode. rec_ws: the derivative records of k_ddp_derivs / k_ddp_prim + k_ddp_tan + k_ddp_lx,
+// [t][k][e]. mu_ep: per-episode mu (the solver) or nullptr (mu).
 template <int NJ>
 __global__ void __launch_bounds__(64) k_to_gains_wave(const SysDevice* __restrict__ sdp, const double* __restrict__ U,
                                                       int64_t ldU, const int32_t* __restrict__ nsteps, int n_ep,
@@ -770,165 +946,20 @@ __global__ void __launch_bounds__(64) k_to_gains_wave(const SysDevice* __restric
                                                       double* __restrict__ K_out, double* __restrict__ dJ_out,
                                                       int32_t* __restrict__ pd_out) {
   using RC = DdpRec<NJ>;
-  constexpr int N = RC::N, M = RC::M, na = Dims<NJ>::NA;
-  __shared__ double sA[N * N], sB[N * M], sLx[N], sLxx[N * N], sVx[N], sVxx[N * N], sU[M];
-  __shared__ double sVA[N * N], sVB[N * M], sQx[N], sQu[M], sQxx[N * N], sQux[M * N], sQuu[M * M];
-  __shared__ double sk[M], sK[M * N], sTk[M], sT[M * N], sW[N * N];
-  __shared__ int sFail;
+  constexpr int N = RC::N, na = Dims<NJ>::NA;
+  __shared__ ToGainsLds<NJ> lds;
   const int e = blockIdx.x, lane = threadIdx.x;
-  const cacto_sys_params& p = sdp->p;
-  const double w6 = p.w_running[6];
   const int Te = nsteps[e];
   if (!to_valid_len(Te, ldS, ldU)) return;  // uniform over the workgroup
   if (mu_ep) mu = mu_ep[e];
-  const double* Ue = U + (size_t)e * ldU * na;
-  double* ke = k_out + (size_t)e * ldU * na;
-  double* Ke = K_out + (size_t)e * ldU * na * N;
-  {
-    const double* rec = rec_ws + (size_t)Te * RC::R * n_ep + e;
-    for (int k = lane; k < N; k += 64) sVx[k] = -rec[(size_t)(RC::LX + k) * n_ep];
-    for (int k = lane; k < N * N; k += 64) sVxx[k] = -rec[(size_t)(RC::LXX + k) * n_ep];
-    if (lane == 0) sFail = 0;
-  }
-  double d0 = 0.0, d1 = 0.0, d2 = 0.0;  // lane 0's
-  int pd = -1;
-  __syncthreads();
-  for (int i = Te - 1; i >= 0; --i) {
-    const double* rec = rec_ws + (size_t)i * RC::R * n_ep + e;
-    for (int k = lane; k < N * N; k += 64) {
-      sA[k] = rec[(size_t)(RC::A + k) * n_ep];
-      sLxx[k] = -rec[(size_t)(RC::LXX + k) * n_ep];
-    }
-    for (int k = lane; k < N * M; k += 64) sB[k] = rec[(size_t)(RC::B + k) * n_ep];
-    for (int k = lane; k < N; k += 64) sLx[k] = -rec[(size_t)(RC::LX + k) * n_ep];
-    for (int k = lane; k < M; k += 64) sU[k] = Ue[(size_t)i * na + k];
-    __syncthreads();
-    // V_xx A, V_xx B, Q_x = l_x + A^T V_x, Q_u = l_u + B^T V_x
-    for (int o = lane; o < N * N + N * M + N + M; o += 64) {
-      double s = 0.0;
-      if (o < N * N) {
-        const int r = o / N, c = o - r * N;
-#pragma unroll
-        for (int k = 0; k < N; ++k) s += sVxx[r * N + k] * sA[k * N + c];
-        sVA[o] = s;
-      } else if (o < N * N + N * M) {
-        const int q = o - N * N, r = q / M, c = q - r * M;
-#pragma unroll
-        for (int k = 0; k < N; ++k) s += sVxx[r * N + k] * sB[k * M + c];
-        sVB[q] = s;
-      } else if (o < N * N + N * M + N) {
-        const int r = o - N * N - N * M;
-#pragma unroll
-        for (int k = 0; k < N; ++k) s += sA[k * N + r] * sVx[k];
-        sQx[r] = sLx[r] + s;
-      } else {
-        const int j = o - N * N - N * M - N;
-        double lu, luu;
-        to_lu(p, w6, sU[j], j, &lu, &luu);
-#pragma unroll
-        for (int k = 0; k < N; ++k) s += sB[k * M + j] * sVx[k];
-        sQu[j] = lu + s;
-      }
-    }
-    __syncthreads();
-    // Q_xx = l_xx + A^T V_xx A, Q_ux = B^T V_xx A, Q_uu = l_uu + B^T V_xx B
-    for (int o = lane; o < N * N + M * N + M * M; o += 64) {
-      double s = 0.0;
-      if (o < N * N) {
-        const int r = o / N, c = o - r * N;
-#pragma unroll
-        for (int k = 0; k < N; ++k) s += sA[k * N + r] * sVA[k * N + c];
-        sQxx[o] = sLxx[o] + s;
-      } else if (o < N * N + M * N) {
-        const int q = o - N * N, j = q / N, c = q - j * N;
-#pragma unroll
-        for (int k = 0; k < N; ++k) s += sB[k * M + j] * sVA[k * N + c];
-        sQux[q] = s;
-      } else {
-        const int q = o - N * N - M * N, r = q / M, c = q - r * M;
-#pragma unroll
-        for (int k = 0; k < N; ++k) s += sB[k * M + r] * sVB[k * M + c];
-        double lu, luu = 0.0;
-        if (r == c) to_lu(p, w6, sU[r], r, &lu, &luu);
-        sQuu[q] = luu + s;
-      }
-    }
-    __syncthreads();
-    if (lane == 0) {
-      double Lm[M * M], kk[M];
-#pragma unroll
-      for (int q = 0; q < M * M; ++q) Lm[q] = sQuu[q] + (q % (M + 1) == 0 ? mu : 0.0);
-      if (!to_chol<M>(Lm)) {
-        sFail = 1;
-        pd = i;
-      } else {
-#pragma unroll
-        for (int j = 0; j < M; ++j) kk[j] = -sQu[j];
-        to_chol_solve<M>(Lm, kk, 1);
-#pragma unroll 1
-        for (int c = 0; c < N; ++c) {
-          double col[M];
-#pragma unroll
-          for (int j = 0; j < M; ++j) col[j] = -sQux[j * N + c];
-          to_chol_solve<M>(Lm, col, 1);
-#pragma unroll
-          for (int j = 0; j < M; ++j) sK[j * N + c] = col[j];
-        }
-#pragma unroll
-        for (int j = 0; j < M; ++j) {
-          double s = 0.0;
-#pragma unroll
-          for (int c = 0; c < M; ++c) s += sQuu[j * M + c] * kk[c];
-          sTk[j] = s;
-          sk[j] = kk[j];
-          d0 += kk[j] * sQu[j];
-          d1 += kk[j] * s;
-          d2 = fmax(d2, fabs(sQu[j]));
-        }
-      }
-    }
-    __syncthreads();
-    if (sFail) break;  // uniform
-    // T = Q_uu K; the gains to memory
-    for (int o = lane; o < M * N; o += 64) {
-      const int j = o / N, c = o - j * N;
-      double s = 0.0;
-#pragma unroll
-      for (int q = 0; q < M; ++q) s += sQuu[j * M + q] * sK[q * N + c];
-      sT[o] = s;
-      Ke[(size_t)i * na * N + o] = sK[o];
-    }
-    for (int j = lane; j < M; j += 64) ke[(size_t)i * na + j] = sk[j];
-    __syncthreads();
-    // V_x, and V_xx before symmetrisation
-    for (int o = lane; o < N * N + N; o += 64) {
-      if (o < N * N) {
-        const int r = o / N, c = o - r * N;
-        double s = sQxx[o];
-#pragma unroll
-        for (int j = 0; j < M; ++j)
-          s += sK[j * N + r] * (sT[j * N + c] + sQux[j * N + c]) + sQux[j * N + r] * sK[j * N + c];
-        sW[o] = s;
-      } else {
-        const int r = o - N * N;
-        double s = sQx[r];
-#pragma unroll
-        for (int j = 0; j < M; ++j) s += sK[j * N + r] * (sTk[j] + sQu[j]) + sQux[j * N + r] * sk[j];
-        sVx[r] = s;
-      }
-    }
-    __syncthreads();
-    for (int o = lane; o < N * N; o += 64) {
-      const int r = o / N, c = o - r * N;
-      sVxx[o] = 0.5 * (sW[o] + sW[c * N + r]);
-    }
-    __syncthreads();
-  }
+  const ToPass bp = to_gains_episode<NJ, 64>(lds, sdp->p, U + (size_t)e * ldU * na, Te, mu, rec_ws + e,
+                                             (size_t)RC::R * n_ep, (size_t)n_ep, k_out + (size_t)e * ldU * na,
+                                             K_out + (size_t)e * ldU * na * N, lane);
   if (lane == 0) {
-    pd_out[e] = pd;
-    dJ_out[(size_t)e * 3] = d0;
-    dJ_out[(size_t)e * 3 + 1] = 0.5 * d1;
-    dJ_out[(size_t)e * 3 + 2] = d2;
+    pd_out[e] = bp.pd;
+    dJ_out[(size_t)e * 3] = bp.dJ[0];
+    dJ_out[(size_t)e * 3 + 1] = bp.dJ[1];
+    dJ_out[(size_t)e * 3 + 2] = bp.dJ[2];
   }
 }
 
@@ -942,6 +973,21 @@ struct ToState {
   int32_t* done;
 };
 
+// The warm start of one episode on one thread: s0 and U_init copied into cur and rolled out in
+// place (node costs to cost). Returns the roll-out's cost.
+template <int NJ>
+__device__ __forceinline__ double to_warm_start_thread(const SysDevice& sd, const double* S0, const double* U_init, int64_t ldU,
+                                              int e, int Te, const Traj& cur, const View& cost) {
+  constexpr int ns = Dims<NJ>::NS, na = Dims<NJ>::NA;
+#pragma unroll
+  for (int k = 0; k < ns; ++k) cur.S.at(0, k) = S0[(size_t)e * ns + k];
+  for (int t = 0; t < Te; ++t)
+#pragma unroll
+    for (int j = 0; j < na; ++j) cur.U.at(t, j) = U_init[((size_t)e * ldU + t) * na + j];
+  const Gains none{View{nullptr, 0, 0}, View{nullptr, 0, 0}};
+  return to_forward_thread<NJ, true>(sd, cur, none, Te, 0.0, cur, cost);
+}
+
 // Warm start of the split family: U_init rolled out from s0 into the caller's S / U / step_cost.
 template <int NJ>
 __global__ void __launch_bounds__(64) k_to_init(const SysDevice* __restrict__ sdp, const double* __restrict__ S0,
@@ -950,7 +996,6 @@ __global__ void __launch_bounds__(64) k_to_init(const SysDevice* __restrict__ sd
                                                 double* S_out, double* U_out, double* cost_out,
                                                 int32_t* __restrict__ status_out, int32_t* __restrict__ iters_out,
                                                 double* __restrict__ J_out) {
-  constexpr int ns = Dims<NJ>::NS, na = Dims<NJ>::NA;
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n_ep) return;
   const int Te = nsteps[e];
@@ -966,14 +1011,8 @@ __global__ void __launch_bounds__(64) k_to_init(const SysDevice* __restrict__ sd
     atomicAdd(st.done, 1);
     return;
   }
-  const Traj cur = api_traj<NJ>(S_out, ldS, U_out, ldU, e);
-#pragma unroll
-  for (int k = 0; k < ns; ++k) cur.S.at(0, k) = S0[(size_t)e * ns + k];
-  for (int t = 0; t < Te; ++t)
-#pragma unroll
-    for (int j = 0; j < na; ++j) cur.U.at(t, j) = U_init[((size_t)e * ldU + t) * na + j];
-  const Gains none{View{nullptr, 0, 0}, View{nullptr, 0, 0}};
-  const double J = to_forward_thread<NJ, true>(*sdp, cur, none, Te, 0.0, cur, View{cost_out + (size_t)e * ldS, 1, 1});
+  const double J = to_warm_start_thread<NJ>(*sdp, S0, U_init, ldU, e, Te, api_traj<NJ>(S_out, ldS, U_out, ldU, e),
+                                            View{cost_out + (size_t)e * ldS, 1, 1});
   st.J[e] = J;
   J_out[(size_t)e * 2] = J;
   J_out[(size_t)e * 2 + 1] = J;
@@ -986,6 +1025,43 @@ __global__ void __launch_bounds__(64) k_to_init(const SysDevice* __restrict__ sd
     st.live[e] = Te;
   else
     atomicAdd(st.done, 1);
+}
+
+// One candidate of the line search on one thread: the cost of alpha = 2^-j rolled out without
+// storing it, or NaN when the step is not admissible.
+template <int NJ>
+__device__ __forceinline__ double to_ls_candidate(const SysDevice& sd, const ToCfgDev& cfg, const Traj& cur, const Gains& g, int Te,
+                                         int j, double J, const double* dJ, const View& cost) {
+  const double alpha = ldexp(1.0, -j);
+  const double Jc = to_forward_thread<NJ, false>(sd, cur, g, Te, alpha, cur, cost);
+  return to_admissible(cfg, J, Jc, alpha, dJ) ? Jc : __builtin_nan("");
+}
+
+// The decision of one pass of one split-family episode. pd: the backward pass's verdict; search:
+// the pass was positive definite and not converged, and cand [0..max_ls] holds to_ls_candidate's
+// values. Updates mu and, with an accepted step (*sel = its j, else -1), J. Returns the status
+// the episode ends with, or -1 when it goes on.
+__device__ __forceinline__ int to_decide(const ToCfgDev& cfg, int pd, bool search, const double* cand, double* mu, double* J,
+                                int* sel_out) {
+  int sel = -1, finished = -1;
+  bool raise = pd >= 0;
+  if (!raise) {
+    if (!search) {
+      finished = CACTO_TO_CONVERGED;
+    } else {
+      for (int q = 0; q <= cfg.max_ls && sel < 0; ++q)
+        if (cand[q] == cand[q]) sel = q;
+      if (sel >= 0) {
+        *J = cand[sel];
+        to_lower_mu(cfg, mu);
+      } else {
+        raise = true;
+      }
+    }
+  }
+  if (raise && to_raise_mu(cfg, mu)) finished = CACTO_TO_FAILED;
+  *sel_out = sel;
+  return finished;
 }
 
 // One iteration's decision and line search of the split family. A workgroup of 64 threads holds
@@ -1025,37 +1101,18 @@ __global__ void __launch_bounds__(64) k_to_linesearch(const SysDevice* __restric
     g = api_gains<NJ>(k_in, K_in, ldU, e);
     cost = View{cost_out + (size_t)e * ldS, 1, 1};
   }
-  double Jc = 0.0;
-  bool ok = false;
-  if (search && j <= cfg.max_ls) {
-    Jc = to_forward_thread<NJ, false>(*sdp, cur, g, Te, alpha, cur, cost);
-    ok = to_admissible(cfg, J, Jc, alpha, dJ);
-  }
-  sJ[tid] = ok ? Jc : __builtin_nan("");
+  sJ[tid] = search && j <= cfg.max_ls ? to_ls_candidate<NJ>(*sdp, cfg, cur, g, Te, j, J, dJ, cost) : __builtin_nan("");
   __syncthreads();
   if (j == 0) {
     int sel = -1;
     if (live) {
       double mu = st.mu[e];
-      int finished = -1;
       iters_out[e] += 1;
-      bool raise = pd >= 0;
-      if (!raise) {
-        if (!search) {
-          finished = CACTO_TO_CONVERGED;
-        } else {
-          for (int q = 0; q <= cfg.max_ls && sel < 0; ++q)
-            if (sJ[grp * LSP + q] == sJ[grp * LSP + q]) sel = q;
-          if (sel >= 0) {
-            st.J[e] = sJ[grp * LSP + sel];
-            J_out[(size_t)e * 2 + 1] = sJ[grp * LSP + sel];
-            to_lower_mu(cfg, &mu);
-          } else {
-            raise = true;
-          }
-        }
+      const int finished = to_decide(cfg, pd, search, sJ + grp * LSP, &mu, &J, &sel);
+      if (sel >= 0) {
+        st.J[e] = J;
+        J_out[(size_t)e * 2 + 1] = J;
       }
-      if (raise && to_raise_mu(cfg, &mu)) finished = CACTO_TO_FAILED;
       st.mu[e] = mu;
       if (finished >= 0) {
         status_out[e] = finished;
@@ -1067,6 +1124,111 @@ __global__ void __launch_bounds__(64) k_to_linesearch(const SysDevice* __restric
   }
   __syncthreads();
   if (search && j == sSel[grp]) to_forward_thread<NJ, true>(*sdp, cur, g, Te, alpha, cur, cost);
+}
+
+// LDS of k_to_solve_split: the backward pass's operands, and the scalars the phases hand to every
+// thread (dJ [3] and the warm start's cost, the verdict, the candidates' costs).
+template <int NJ>
+struct ToSplitLds {
+  ToGainsLds<NJ> gains;
+  double pass[4];
+  double cand[64];
+  int pd;
+};
+
+// The solver of car_park with one workgroup of BT threads per episode (cfg.path =
+// CACTO_TO_PATH_WAVE): what k_to_init and max_iter rounds of k_ddp_derivs, k_to_gains_wave and
+// k_to_linesearch compute, the whole loop on the device, from the same device functions
+// (contraction is off, so the numbers are those of the host-issued loop bit for bit). Per pass:
+// the threads stride over the nodes for the derivative records; every wave runs the backward
+// pass's step loop and takes outputs in it (one output per thread, the same summation order per
+// output: the first of the two arrangements a wider workgroup allows, so its barriers are
+// workgroup barriers reached by all waves); thread j <= max_ls evaluates alpha = 2^-j; every
+// thread takes the decision from the candidates in LDS, and thread sel rolls the accepted step
+// out in place. Te, mu, J, the verdict, the status and the pass count are the same on every
+// thread, so every branch around a barrier is uniform. The phases hand records, gains and
+// trajectory to each other through global memory inside the workgroup: the barrier between them
+// is the ordering (nothing crosses a workgroup), and no pointer they go through is __restrict__.
+// The trajectory and the node costs live in the caller's S / U / step_cost (rows past Te, and a
+// skipped episode's, are never touched); ws: per episode the gains k [ldS][na], K [ldS][na*nx];
+// rec_ws: per episode the records [ldS][DdpRec::R], element stride 1.
+// The revolute chains are not instantiated: their derivative phase needs the tangent pass's LDS
+// slabs and the bodies of k_ddp_prim / k_ddp_tan / k_ddp_lx, and a build of this kernel with them
+// faulted on the GPU for a reason that has not been found.
+template <int NJ, int BT>
+__global__ void __launch_bounds__(BT) k_to_solve_split(const SysDevice* __restrict__ sdp, const double* __restrict__ S0,
+                                                        const double* U_init, int64_t ldU,
+                                                        const int32_t* __restrict__ nsteps, int n_ep, int64_t ldS,
+                                                        ToCfgDev cfg, double* ws, double* rec_ws, double* S_out,
+                                                        double* U_out, double* cost_out, int32_t* __restrict__ status_out,
+                                                        int32_t* __restrict__ iters_out, double* __restrict__ J_out) {
+  static_assert(NJ == -2, "k_to_solve_split: car_park only");
+  using RC = DdpRec<NJ>;
+  constexpr int N = RC::N, M = RC::M;
+  __shared__ ToSplitLds<NJ> lds;
+  const int tid = threadIdx.x, e = blockIdx.x;
+  const int Te = nsteps[e];
+  if (Te < 0) return;  // every exit up to the loop is uniform over the workgroup
+  if (!to_valid_len(Te, ldS, ldU)) {
+    if (tid == 0) {
+      status_out[e] = CACTO_TO_FAILED;
+      iters_out[e] = 0;
+    }
+    return;
+  }
+  const size_t L = (size_t)ldS;
+  const SysDevice& sd = *sdp;
+  const Traj cur = api_traj<NJ>(S_out, ldS, U_out, ldU, e);
+  const View cost{cost_out + (size_t)e * ldS, 1, 1};
+  double* wk = ws + (size_t)e * L * (M + M * N);
+  const Gains g{View{wk, (size_t)M, 1}, View{wk + L * M, (size_t)M * N, 1}};
+  double* rec = rec_ws + (size_t)e * L * RC::R;
+  if (tid == 0) lds.pass[3] = to_warm_start_thread<NJ>(sd, S0, U_init, ldU, e, Te, cur, cost);
+  __syncthreads();
+  double J = lds.pass[3];
+  const double J0 = J;
+  int status = CACTO_TO_MAXITER, iters = 0;
+  if (Te == 0) status = CACTO_TO_CONVERGED;
+  if (!isfinite(J)) status = CACTO_TO_FAILED;
+  if (status == CACTO_TO_MAXITER) {
+    double mu = 0.0;
+    for (int it = 0; it < cfg.max_iter; ++it) {
+      ++iters;
+      for (int t = tid; t <= Te; t += BT)
+        ddp_derivs_node<NJ>(sd, &cur.S.at(t, 0), t < Te ? &cur.U.at(t, 0) : nullptr, t == Te, rec + (size_t)t * RC::R, 1);
+      __syncthreads();
+      const ToPass bp = to_gains_episode<NJ, BT>(lds.gains, sd.p, cur.U.p, Te, mu, rec, (size_t)RC::R, 1, g.k.p, g.K.p, tid);
+      if (tid == 0) {
+        lds.pd = bp.pd;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) lds.pass[k] = bp.dJ[k];
+      }
+      __syncthreads();
+      const int pd = lds.pd;
+      double dJ[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) dJ[k] = lds.pass[k];
+      const bool search = pd < 0 && !(dJ[2] <= cfg.gtol);
+      if (tid < 64)
+        lds.cand[tid] =
+            search && tid <= cfg.max_ls ? to_ls_candidate<NJ>(sd, cfg, cur, g, Te, tid, J, dJ, cost) : __builtin_nan("");
+      __syncthreads();
+      int sel = -1;
+      const int finished = to_decide(cfg, pd, search, lds.cand, &mu, &J, &sel);
+      if (tid == sel) to_forward_thread<NJ, true>(sd, cur, g, Te, ldexp(1.0, -sel), cur, cost);
+      __syncthreads();
+      if (finished >= 0) {
+        status = finished;
+        break;
+      }
+    }
+  }
+  if (tid == 0) {
+    status_out[e] = status;
+    iters_out[e] = iters;
+    J_out[(size_t)e * 2] = J0;
+    J_out[(size_t)e * 2 + 1] = J;
+  }
 }
 
 }  // namespace cacto
@@ -1083,6 +1245,16 @@ template <int NJ>
 constexpr bool to_split() {
   return NJ > 2 || NJ == -2;
 }
+
+// car_park has a persistent one-workgroup-per-episode kernel for cfg.path = CACTO_TO_PATH_WAVE
+// (k_to_solve_split); the revolute chains run the host-issued loop under either path
+template <int NJ>
+constexpr bool to_persistent() {
+  return NJ == -2;
+}
+// Its threads per workgroup: car_park's phases hold no per-thread LDS and a 100-step episode's
+// nodes fit one stride
+constexpr int TO_SPLIT_THREADS = 256;
 
 // the (dynamics, reward) combinations of the six systems, as cacto_ddp_backward
 template <int NJ>
@@ -1171,7 +1343,9 @@ struct LaunchToForward {
 //                 (the wave path keeps its gains [e][t][k] at the head of that block and adds
 //                 the node records [n_ep, ldS, ToRec::R] behind it)
 //   split family: live [n_ep] int32 + done; mu, J [n_ep]; dJ [n_ep, 3]; pd [n_ep] int32; gains k
-//                 [n_ep, ldS, na], K [n_ep, ldS, na, nx]; the derivative records
+//                 [n_ep, ldS, na], K [n_ep, ldS, na, nx]; the derivative records [t][k][e]
+//                 (car_park's wave path: per episode the gains k [ldS, na], K [ldS, na, nx],
+//                 then per episode the records [ldS, .]; no solver state)
 template <int NJ>
 struct ToWs {
   static constexpr int N = DdpDims<NJ>::N, M = DdpDims<NJ>::M;
@@ -1180,9 +1354,14 @@ struct ToWs {
     const size_t E = (size_t)n_ep, L = (size_t)ldS;
     off_i32 = 0;
     if constexpr (to_split<NJ>()) {
-      off_d = align256((2 * E + 1) * sizeof(int32_t));  // live, pd, done
-      const size_t d = 2 * E + 3 * E + E * L * M + E * L * M * N;
-      off_rec = off_d + align256(d * sizeof(double));
+      if (to_persistent<NJ>() && path == CACTO_TO_PATH_WAVE) {
+        off_d = 0;
+        off_rec = align256(E * L * (size_t)(M + M * N) * sizeof(double));
+      } else {
+        off_d = align256((2 * E + 1) * sizeof(int32_t));  // live, pd, done
+        const size_t d = 2 * E + 3 * E + E * L * M + E * L * M * N;
+        off_rec = off_d + align256(d * sizeof(double));
+      }
       bytes = off_rec + align256(to_rec_doubles<NJ>(n_ep, ldS) * sizeof(double));
     } else {
       off_d = align256((E + L + 1) * sizeof(int32_t));
@@ -1233,6 +1412,14 @@ struct LaunchToSolve {
                              n, n_ep, ldS, c, order, reinterpret_cast<double*>(base + lay.off_d), S, U, cost, status,
                              iters, J);
         CACTO_CHECK_HIP(hipGetLastError());
+      } else if (to_persistent<NJ>() && cfg->path == CACTO_TO_PATH_WAVE) {
+        if constexpr (to_persistent<NJ>()) {
+          constexpr int BT = TO_SPLIT_THREADS;
+          hipLaunchKernelGGL((k_to_solve_split<NJ, BT>), dim3(n_ep), dim3(BT), 0, st, sys->dev, S0, U_init, ldU, n, n_ep,
+                             ldS, c, reinterpret_cast<double*>(base + lay.off_d),
+                             reinterpret_cast<double*>(base + lay.off_rec), S, U, cost, status, iters, J);
+          CACTO_CHECK_HIP(hipGetLastError());
+        }
       } else {
         int32_t* live = reinterpret_cast<int32_t*>(base + lay.off_i32);
         int32_t* pd = live + E;
@@ -1275,7 +1462,36 @@ struct LaunchToSolve {
   }
 };
 
+// cacto_to_solve_plan: what LaunchToSolve runs for a path
+template <int NJ>
+struct LaunchToPlan {
+  static int run(const cacto_sys* sys, int path, cacto_to_plan* out) {
+    if (!to_supported<NJ>(sys, "cacto_to_solve_plan")) return CACTO_EUNSUPPORTED;
+    if constexpr (DdpDims<NJ>::ok) {
+      const bool wave = path == CACTO_TO_PATH_WAVE;
+      if constexpr (!to_split<NJ>()) {
+        // k_to_solve_thread holds no LDS; k_to_solve_wave: sPass [4] and sPd, padded to 8 bytes
+        *out = cacto_to_plan{1, 64, wave ? (int32_t)(5 * sizeof(double)) : 0, 0};
+      } else if (to_persistent<NJ>() && wave) {
+        *out = cacto_to_plan{1, TO_SPLIT_THREADS, (int32_t)sizeof(ToSplitLds<NJ>), 0};
+      } else {
+        // the host-issued loop; the kernel described is its one-wave-per-episode backward pass
+        *out = cacto_to_plan{0, 64, (int32_t)sizeof(ToGainsLds<NJ>), NJ > 2 ? 5 : 3};
+      }
+    }
+    return CACTO_OK;
+  }
+};
+
 }  // namespace
+
+extern "C" int cacto_to_solve_plan(const cacto_sys* sys, const cacto_to_cfg* cfg_h, cacto_to_plan* out) {
+  CACTO_REQUIRE(cfg_h, "cacto_to_solve_plan: null config");
+  CACTO_REQUIRE(to_path_ok(cfg_h->path),
+                "cacto_to_solve_plan: bad config (path: CACTO_TO_PATH_DEFAULT or CACTO_TO_PATH_WAVE)");
+  CACTO_REQUIRE(sys && out, "cacto_to_solve_plan: bad arguments (null pointer)");
+  return dispatch_nj<LaunchToPlan>(sys->host.p, sys, (int)cfg_h->path, out);
+}
 
 extern "C" int cacto_to_backward_gains(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d,
                                        int64_t ldU, const int32_t* nsteps_d, int n_ep, double mu, double* k_d,

@@ -11,6 +11,7 @@ UR5.reward leaves out), the dynamics Env.simulate. It is a local method like IPO
 stationary point of the same problem, not necessarily the same one.
 
   solve_batch            the solver on device tensors
+  solve_plan             what solve_batch runs for a config (one kernel or a host-issued loop)
   backward_gains_batch   one regularised backward pass (gains k, K, expected decrease, PD verdict)
   forward_batch          one closed-loop roll-out with step size alpha
   TO_System_Solve        the reference's per-episode signature and return tuple (TO.py:100)
@@ -30,9 +31,12 @@ CONVERGED, MAXITER, FAILED = L.CACTO_TO_CONVERGED, L.CACTO_TO_MAXITER, L.CACTO_T
 
 # max_iter backward passes, step sizes 2^0..2^-max_ls, stop at max_t |Q_u|_inf <= gtol, the Armijo
 # fraction, mu x10 (from mu_min) on failure and /10 on success, poll the device every 8 iterations
-# path: which kernels solve the single integrator, the car and the double integrator. 0 / "default":
-# one thread per episode (large batches); 1 / "wave": one 64-lane workgroup per episode (per-episode
-# calls and batches of a few hundred). The other systems run one wave per episode either way.
+# path: which kernels solve. 0 / "default": one thread per episode for the single integrator, the car
+# and the double integrator (large batches), a loop issued by the host (which polls the device every
+# poll_every iterations) for car_park, the manipulator and UR5; 1 / "wave": one workgroup per episode
+# and the whole loop in one kernel for those three and car_park (per-episode calls and batches of a
+# few hundred; no host round trip, poll_every is not used), the host-issued loop for the manipulator
+# and UR5. TO.solve_plan tells what a config runs.
 DEFAULT_CFG = dict(max_iter=400, max_ls=10, gtol=1e-4, armijo=1e-4, mu_min=1e-6, mu_up=10.0, mu_down=10.0,
                    mu_max=1e10, poll_every=8, path=0)
 PATHS = {"default": L.CACTO_TO_PATH_DEFAULT, "wave": L.CACTO_TO_PATH_WAVE}
@@ -90,6 +94,16 @@ class TO:
                      dptr(out["status"], torch.int32), dptr(out["iters"], torch.int32), dptr(out["J"], torch.float64),
                      dptr(ws), nbytes, stream())
         return out
+
+    def solve_plan(self, cfg=None):
+        """cacto_to_solve_plan: what solve_batch runs for this system with cfg (a dict over
+        DEFAULT_CFG), as a dict: on_device (1: the whole loop is one kernel, nothing synchronises, the
+        call can be captured into a graph), block_threads and lds_bytes of the solving kernel,
+        launches_per_iter (kernel launches the host issues per iteration; 0 when on_device)."""
+        c = cfg if isinstance(cfg, L.ToCfg) else make_cfg(cfg)
+        plan = L.ToPlan()
+        L.lib().call("cacto_to_solve_plan", self.sys.handle, C.byref(c), C.byref(plan))
+        return {name: int(getattr(plan, name)) for name, _ in L.ToPlan._fields_}
 
     def backward_gains_batch(self, S_traj, U_traj, nsteps, mu=0.0):
         """cacto_to_backward_gains along S_traj [E, ldS, ns], U_traj [E, ldU, na]: a dict k [E, ldU,

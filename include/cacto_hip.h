@@ -46,9 +46,10 @@
  *     cacto_update_n[_per] also use a side stream owned by the handle, joined back into `stream`
  *     before they return; cacto_ddp_backward (car_park, revolute chains) grows a device workspace
  *     owned by the handle (a hipMalloc, so warm it up before capturing), and so does
- *     cacto_to_backward_gains. cacto_to_solve with cfg.poll_every > 0 on car_park and the revolute
- *     chains synchronises the stream every poll_every iterations (it reads a device counter of
- *     finished episodes to stop early); with poll_every == 0 it never synchronises.
+ *     cacto_to_backward_gains. cacto_to_solve with cfg.poll_every > 0 on the revolute chains
+ *     (either path) and on car_park with cfg.path = CACTO_TO_PATH_DEFAULT synchronises the stream
+ *     every poll_every iterations (it reads a device counter of finished episodes to stop early);
+ *     with poll_every == 0, or where cacto_to_solve_plan says on_device, it never synchronises.
  *   - Return 0 on success, <0 on error; cacto_last_error() returns a thread-local message.
  *     No C++ exception crosses the ABI.
  *   - Handles (cacto_sys) are created/destroyed by the caller; concurrent calls on one handle are
@@ -434,11 +435,14 @@ typedef struct {
   int32_t path;       /* enum cacto_to_path; any other value: CACTO_EINVAL */
 } cacto_to_cfg;
 
-/* Which kernels cacto_to_solve runs; the algorithm, cost, dynamics and line-search rule are the same. */
+/* Which kernels cacto_to_solve runs; the algorithm, cost, dynamics and line-search rule are the
+ * same, and for car_park, the manipulator and UR5 so is every output, bit for bit. */
 enum cacto_to_path {
-  CACTO_TO_PATH_DEFAULT = 0, /* single integrator, car, double integrator: one thread per episode */
-  CACTO_TO_PATH_WAVE = 1     /* those systems: one 64-lane workgroup per episode (small batches, per-episode
-                              * calls). car_park, manipulator, UR5 already run one wave per episode: as 0. */
+  CACTO_TO_PATH_DEFAULT = 0, /* single integrator, car, double integrator: one persistent kernel, one thread
+                              * per episode. car_park, manipulator, UR5: a loop issued by the host */
+  CACTO_TO_PATH_WAVE = 1     /* single integrator, car, double integrator, car_park: one persistent kernel,
+                              * one workgroup per episode (small batches, per-episode calls); no host round
+                              * trip, poll_every is not used. Manipulator, UR5: as 0 */
 };
 
 /* One regularised backward pass along given trajectories (cost convention, l_xu = 0):
@@ -462,7 +466,8 @@ int cacto_to_forward(const cacto_sys* sys, const double* S_d, int64_t ldS, const
                      double* S_new_d, double* U_new_d, double* cost_new_d, void* stream);
 
 /* Workspace of cacto_to_solve: for cfg.path = CACTO_TO_PATH_DEFAULT, and for the path of a given
- * config (CACTO_TO_PATH_WAVE adds the per-node derivative records of the closed-form family).
+ * config (CACTO_TO_PATH_WAVE adds the per-node derivative records of the closed-form family; for
+ * car_park it keeps gains and records per episode and no solver state).
  * 0 on bad arguments or an unknown path. */
 size_t cacto_to_workspace_bytes(const cacto_sys* sys, int n_ep, int64_t ldS);
 size_t cacto_to_workspace_bytes_cfg(const cacto_sys* sys, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h);
@@ -476,13 +481,33 @@ size_t cacto_to_workspace_bytes_cfg(const cacto_sys* sys, int n_ep, int64_t ldS,
  * (path 0: cacto_to_workspace_bytes). ldU <= ldS.
  * Single integrator, car, double integrator: one persistent kernel, no host round trip (poll_every
  * is not used): one thread per episode, or with cfg.path = CACTO_TO_PATH_WAVE one 64-lane workgroup
- * per episode (derivatives over the nodes, every step size of the line search at once). car_park, manipulator, UR5: max_iter iterations of
- * derivative kernels + a one-wave-per-episode backward pass + a line-search kernel, issued by the
- * host; poll_every > 0 stops issuing once every episode has finished (see Conventions). */
+ * per episode (derivatives over the nodes, every step size of the line search at once).
+ * car_park, manipulator, UR5, path 0: max_iter iterations of derivative kernels + a
+ * one-wave-per-episode backward pass + a line-search kernel, issued by the host; poll_every > 0
+ * stops issuing once every episode has finished (see Conventions). car_park with cfg.path =
+ * CACTO_TO_PATH_WAVE: one persistent kernel, one workgroup of 256 threads per episode running the
+ * same device functions (derivatives over the nodes, the backward pass over all its waves, every
+ * step size at once) — the same outputs bit for bit, no host round trip, nothing synchronised,
+ * poll_every not used. The manipulator and UR5 run the host-issued loop under either path. */
 int cacto_to_solve(const cacto_sys* sys, const double* S0_d, const double* U_init_d, int64_t ldU,
                    const int32_t* nsteps_d, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h, double* S_d,
                    double* U_d, double* step_cost_d, int32_t* status_d, int32_t* iters_d, double* J_d, void* ws_d,
                    size_t ws_bytes, void* stream);
+
+/* What cacto_to_solve runs for a system and a config (the role cacto_rollout_sched's arguments play
+ * for the rollout: TO.py:37-100 has one host-side IPOPT call per episode and nothing to plan), so a
+ * caller can tell before capturing a call into a hipGraph whether it is one kernel. */
+typedef struct {
+  int32_t on_device;         /* 1: the whole iteration loop runs in one kernel, no host round trip and
+                              * no synchronisation (poll_every is not used) */
+  int32_t block_threads;     /* threads per workgroup of the solving kernel (on_device == 0: of the
+                              * one-wave-per-episode backward pass of the host-issued loop) */
+  int32_t lds_bytes;         /* that kernel's static LDS */
+  int32_t launches_per_iter; /* kernel launches the host issues per iteration; 0 when on_device */
+} cacto_to_plan;
+
+/* CACTO_EINVAL for a null argument or an unknown cfg_h->path; no device work, nothing enqueued. */
+int cacto_to_solve_plan(const cacto_sys* sys, const cacto_to_cfg* cfg_h, cacto_to_plan* out);
 
 /* ---------------------------------------------------------------- replay ------------------ */
 

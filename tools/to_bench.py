@@ -6,8 +6,11 @@ from 1e-6). Prints one JSON line: episodes/s, mean and max backward passes, the 
     python tools/to_bench.py [--system double_integrator] [--episodes 4096] [--path default|wave] [--repeat 3]
                              [--helper 8]
 
---path wave runs the one-wave-per-episode kernel of the closed-form family (cacto_to_cfg.path):
+--path wave runs the one-workgroup-per-episode persistent kernel (cacto_to_cfg.path; not the
+manipulator and UR5, which have none):
 the path for per-episode calls (--episodes 1) and batches of the reference's size (EP_UPDATE: 200).
+The result carries the plan of the config (cacto_to_solve_plan: on_device, block_threads, lds_bytes,
+launches_per_iter) beside the figures.
 
 --helper N also times tests/ilqr_ref.py (numpy, one core) on the first N of those episodes and
 reports its seconds per episode. Reported, not gated: there is no earlier figure to compare with,
@@ -54,6 +57,10 @@ def main():
     from cacto_amd.to import TO
     to = TO(make_env(conf), conf)
     cfg = dict(R.SOLVE_CFG, poll_every=args.poll_every, path=args.path)
+    from cacto_amd import _lib
+    # a library of an older revision (CACTO_HIP_LIB with CACTO_LIB_PARTIAL=1, cacto_amd/_lib.py: A/B runs)
+    # has no plan entry
+    plan = to.solve_plan(cfg) if hasattr(_lib.lib().dll, "cacto_to_solve_plan") else None
     dev = lambda a: torch.as_tensor(np.ascontiguousarray(a), device="cuda")  # noqa: E731
     S0_d, Te_d = dev(S0), dev(Te)
     U0_d = torch.zeros(args.episodes, max(int(Te.max()), 1), conf.nb_action, dtype=torch.float64, device="cuda")
@@ -72,7 +79,7 @@ def main():
                iters_mean=float(iters.mean()), iters_max=int(iters.max()),
                status_share=dict(converged=float((status == R.CONVERGED).mean()),
                                  maxiter=float((status == R.MAXITER).mean()), failed=float((status == R.FAILED).mean())),
-               monotone=bool((J[:, 1] <= J[:, 0]).all()))
+               monotone=bool((J[:, 1] <= J[:, 0]).all()), plan=plan)
     if args.helper > 0:
         res.update(helper(R, args, S0, Te))
         res["gpu_status_same_episodes"] = status[:args.helper].tolist()
