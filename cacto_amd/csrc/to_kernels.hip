@@ -19,21 +19,30 @@
 // The derivatives are those of cacto_ddp_backward (ddp_device.h; they are the reward's, so the
 // signs flip on the way in). Everything is float64 VALU and LDS; there is no matrix-core work here.
 //
-// Closed-form family (single integrator, car, double integrator): k_to_solve_thread, one
-// persistent kernel, one thread per episode, the whole iteration loop on the device. Trajectory
-// and gains live in the workspace in the [t][k][e] layout of DdpRec (a wave's lanes touch
-// consecutive addresses); episodes are handed out longest first so a wave's lanes have similar Te.
-// With cfg.path = CACTO_TO_PATH_WAVE: k_to_solve_wave, the same loop with one 64-lane workgroup
-// per episode (derivatives over the nodes, the recursion on one lane, every step size at once), for
-// per-episode calls and batches too small to fill the device with one thread per episode.
-// Split family (car_park, manipulator, UR5), path 0: per iteration the per-(episode, step) derivative
-// kernels of the label pass (fed a live copy of nsteps in which finished episodes are -1),
-// k_to_gains_wave (one wave per episode, operands in LDS, the M x M Cholesky on one lane) and
-// k_to_linesearch (one thread per (episode, j): every step size at once, then the largest
-// admissible one — by definition what sequential backtracking picks), issued by the host. car_park
-// with cfg.path = CACTO_TO_PATH_WAVE: k_to_solve_split, the bodies of those kernels as device
-// functions run by one workgroup per episode, the whole loop on the device (the same numbers bit
-// for bit); the manipulator and UR5 run the host-issued loop under either path.
+//
+// The file, in order:
+//   the pieces of a pass  to_riccati_step / to_gains_episode (the same algebra on one thread / spread
+//                         over a workgroup), to_node_record + to_backward_thread (a closed-form
+//                         episode's records and its recursion), to_forward_thread (a roll-out);
+//   the loop              ToIter, one episode's status / pass count / mu / J / J0, and its transitions
+//                         to_enter, to_iter_begin, to_verdict, to_decide, to_iter_store: the entry
+//                         checks, the stopping rule and the mu schedule are there and nowhere else;
+//                         the warm start and the line search's candidate beside them;
+//   the route and the map to_route<NJ>(path) names the solver of a (system, path); ToWs<NJ> carves
+//                         the workspace for it and hands the kernels their pointers and views;
+//   the four solvers      each runs that loop and differs in who computes a pass and where the state
+//                         lives between passes:
+//     k_to_solve_thread   single integrator, car, double integrator, path 0: one thread per episode,
+//                         episodes handed out longest first (k_to_order); sequential backtracking;
+//     k_to_solve_wave     the same systems, path 1: one 64-lane workgroup per episode, records over
+//                         the lanes, the recursion on lane 0, every step size at once;
+//     host-issued         car_park, manipulator, UR5, path 0 (the chains also path 1): k_to_init,
+//                         then per pass the label pass's derivative kernels, k_to_gains_wave and
+//                         k_to_linesearch, the state in global memory (ToState) between launches;
+//     k_to_solve_split    car_park, path 1: those kernels' bodies run by one 256-thread workgroup
+//                         per episode.
+//   The library is built with -ffp-contract=off and the solvers share these functions, so the two
+//   solvers of a system give the same numbers bit for bit.
 #include "ddp_device.h"
 
 namespace cacto {
@@ -243,59 +252,108 @@ __device__ inline bool to_riccati_step(const double* A, const double* B, const d
   return true;
 }
 
-// M^-1 of a constant-M chain (the double integrator), once per episode
+// M^-1 of a constant-M chain (the double integrator) at the episode's first node, once per episode
 template <int NJ>
-__device__ inline void to_minv(const SysDevice& sd, const double* q0, double* Minv) {
-  if constexpr (NJ > 0) {
-    double Mm[NJ * NJ];
-    chain_mass<NJ>(sd, q0, Mm);
-    small_inverse<NJ>(Mm, Minv);
+struct ToMinv {
+  double a[NJ > 0 ? NJ * NJ : 1];
+  __device__ __forceinline__ ToMinv(const SysDevice& sd, const Traj& cur) {
+    if constexpr (NJ > 0) {
+      double q0[NJ], Mm[NJ * NJ];
+#pragma unroll
+      for (int i = 0; i < NJ; ++i) q0[i] = cur.S.at(0, i);
+      chain_mass<NJ>(sd, q0, Mm);
+      small_inverse<NJ>(Mm, a);
+    }
+  }
+};
+
+// Per-node record of a closed-form episode: DdpRec's A, B, l_x, l_xx (here in the cost
+// convention, the signs already flipped) followed by l_u [M] and the diagonal of l_uu [M]. The
+// wave solver keeps them [e][t][k]: one episode's records are contiguous, a node's record is what
+// the recursion reads in one go.
+template <int NJ>
+struct ToRec {
+  using RC = DdpRec<NJ>;
+  static constexpr int N = RC::N, M = RC::M;
+  static constexpr int LU = RC::R, LUU = LU + M, R = LUU + M;
+};
+
+// The record of node t of one closed-form episode (terminal, t == Te: l_x, l_xx of the terminal
+// weights only). A caller that knows terminal at compile time keeps the weights uniform.
+template <int NJ>
+__device__ inline void to_node_record(const SysDevice& sd, const double* Minv, const Traj& cur, int t, bool terminal,
+                                      double* r) {
+  using TR = ToRec<NJ>;
+  using RC = DdpRec<NJ>;
+  constexpr int N = TR::N, M = TR::M;
+  const cacto_sys_params& p = sd.p;
+  double w[7], x[N], lx[N], lxx[N * N];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) w[k] = terminal ? p.w_terminal[k] : p.w_running[k];
+#pragma unroll
+  for (int k = 0; k < N; ++k) x[k] = cur.S.at(t, k);
+  ddp_lx<NJ>(sd, w, x, lx, lxx);
+#pragma unroll
+  for (int k = 0; k < N; ++k) r[RC::LX + k] = -lx[k];
+#pragma unroll
+  for (int k = 0; k < N * N; ++k) r[RC::LXX + k] = -lxx[k];
+  if (terminal) return;
+  double A[N * N], B[N * M];
+  ddp_jacobians<NJ>(sd, x, Minv, A, B);
+#pragma unroll
+  for (int k = 0; k < N * N; ++k) r[RC::A + k] = A[k];
+#pragma unroll
+  for (int k = 0; k < N * M; ++k) r[RC::B + k] = B[k];
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    double lu, luu;
+    to_lu(p, w[6], cur.U.at(t, j), j, &lu, &luu);
+    r[TR::LU + j] = lu;
+    r[TR::LUU + j] = luu;
   }
 }
 
-// The backward pass of one closed-form episode on one thread. Returns -1, or the step at which
-// Qbar_uu was not positive definite. dJ [3] is reset here.
-template <int NJ>
-__device__ inline int to_backward_thread(const SysDevice& sd, const double* Minv, const Traj& cur, int Te, double mu,
-                                         const Gains& g, double* dJ) {
-  constexpr int N = DdpDims<NJ>::N, M = DdpDims<NJ>::M;
-  const cacto_sys_params& p = sd.p;
-  double w_run[7], w_term[7];
+// The backward pass of one closed-form episode on one thread. node(t, terminal, buf) is node t's
+// record: evaluated into buf [ToRec::R] on the spot (k_to_solve_thread, k_to_gains_thread) or read from
+// where the lanes of k_to_solve_wave left it. Returns -1, or the step at which Qbar_uu was not
+// positive definite. dJ [3] is reset here.
+template <int NJ, class Node>
+__device__ inline int to_backward_thread(Node node, int Te, double mu, const Gains& g, double* dJ) {
+  using TR = ToRec<NJ>;
+  using RC = DdpRec<NJ>;
+  constexpr int N = TR::N, M = TR::M;
+  double buf[TR::R], Vx[N], Vxx[N * N];
+  {
+    const double* r = node(Te, true, buf);
 #pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    w_run[k] = p.w_running[k];
-    w_term[k] = p.w_terminal[k];
+    for (int k = 0; k < N; ++k) Vx[k] = r[RC::LX + k];
+#pragma unroll
+    for (int k = 0; k < N * N; ++k) Vxx[k] = r[RC::LXX + k];
   }
-  double Vx[N], Vxx[N * N], x[N];
-#pragma unroll
-  for (int k = 0; k < N; ++k) x[k] = cur.S.at(Te, k);
-  ddp_lx<NJ>(sd, w_term, x, Vx, Vxx);
-#pragma unroll
-  for (int k = 0; k < N; ++k) Vx[k] = -Vx[k];
-#pragma unroll
-  for (int k = 0; k < N * N; ++k) Vxx[k] = -Vxx[k];
   dJ[0] = dJ[1] = dJ[2] = 0.0;
   for (int i = Te - 1; i >= 0; --i) {
-    double u[M], A[N * N], B[N * M], lx[N], lxx[N * N], lu[M], luu[M], kk[M], KK[M * N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) x[k] = cur.S.at(i, k);
-#pragma unroll
-    for (int k = 0; k < M; ++k) u[k] = cur.U.at(i, k);
-    ddp_jacobians<NJ>(sd, x, Minv, A, B);
-    ddp_lx<NJ>(sd, w_run, x, lx, lxx);
-#pragma unroll
-    for (int k = 0; k < N; ++k) lx[k] = -lx[k];
-#pragma unroll
-    for (int k = 0; k < N * N; ++k) lxx[k] = -lxx[k];
-#pragma unroll
-    for (int j = 0; j < M; ++j) to_lu(p, w_run[6], u[j], j, &lu[j], &luu[j]);
-    if (!to_riccati_step<N, M>(A, B, lx, lxx, lu, luu, mu, Vx, Vxx, kk, KK, dJ)) return i;
+    const double* r = node(i, false, buf);
+    double kk[M], KK[M * N];
+    if (!to_riccati_step<N, M>(r + RC::A, r + RC::B, r + RC::LX, r + RC::LXX, r + TR::LU, r + TR::LUU, mu, Vx, Vxx, kk,
+                               KK, dJ))
+      return i;
 #pragma unroll
     for (int j = 0; j < M; ++j) g.k.at(i, j) = kk[j];
 #pragma unroll
     for (int q = 0; q < M * N; ++q) g.K.at(i, q) = KK[q];
   }
   return -1;
+}
+// ... with every node evaluated on this thread
+template <int NJ>
+__device__ inline int to_backward_eval(const SysDevice& sd, const double* Minv, const Traj& cur, int Te, double mu,
+                                       const Gains& g, double* dJ) {
+  return to_backward_thread<NJ>(
+      [&](int t, bool terminal, double* buf) -> const double* {
+        to_node_record<NJ>(sd, Minv, cur, t, terminal, buf);
+        return buf;
+      },
+      Te, mu, g, dJ);
 }
 
 // One roll-out of one episode on one thread: closed loop around (cur, g) with step size alpha, or
@@ -378,21 +436,15 @@ __global__ void __launch_bounds__(64) k_to_gains_thread(const SysDevice* __restr
                                                          const int32_t* __restrict__ nsteps, int n_ep, double mu,
                                                          double* k_out, double* K_out, double* __restrict__ dJ_out,
                                                          int32_t* __restrict__ pd_out) {
-  constexpr int M = DdpDims<NJ>::M;
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n_ep) return;
   const int Te = nsteps[e];
   if (!to_valid_len(Te, ldS, ldU)) return;
   const SysDevice& sd = *sdp;
   const Traj cur = api_traj<NJ>(const_cast<double*>(S), ldS, const_cast<double*>(U), ldU, e);
-  double Minv[NJ > 0 ? M * M : 1], q0[NJ > 0 ? NJ : 1];
-  if constexpr (NJ > 0) {
-#pragma unroll
-    for (int i = 0; i < NJ; ++i) q0[i] = cur.S.at(0, i);
-    to_minv<NJ>(sd, q0, Minv);
-  }
+  const ToMinv<NJ> Minv(sd, cur);
   double dJ[3];
-  const int pd = to_backward_thread<NJ>(sd, Minv, cur, Te, mu, api_gains<NJ>(k_out, K_out, ldU, e), dJ);
+  const int pd = to_backward_eval<NJ>(sd, Minv.a, cur, Te, mu, api_gains<NJ>(k_out, K_out, ldU, e), dJ);
   pd_out[e] = pd;
 #pragma unroll
   for (int k = 0; k < 3; ++k) dJ_out[(size_t)e * 3 + k] = dJ[k];
@@ -419,6 +471,23 @@ struct ToCfgDev {
   double gtol, armijo, mu_min, mu_up, mu_down, mu_max;
 };
 
+// ---------------------------------------------------------------------------------------------
+// The iteration loop every solver runs, as the state of one episode and its transitions:
+//   to_enter -> to_iter_begin(warm start's cost) -> while running and pass < max_iter:
+//     backward pass -> to_verdict -> [TO_SEARCH: line search] -> to_decide
+//   -> to_iter_store
+// A solver's lanes that hold the state hold it alike, so every branch on it is uniform.
+// ---------------------------------------------------------------------------------------------
+struct ToOut {  // cacto_to_solve's per-episode results
+  int32_t *status, *iters;
+  double* J;  // [n_ep][2]: the warm start's cost, the final cost
+};
+struct ToIter {
+  int status, iters;  // status MAXITER: still running
+  double mu, J, J0;
+  __device__ __forceinline__ bool running() const { return status == CACTO_TO_MAXITER; }
+};
+
 // mu after a failed factorisation or line search; true: past mu_max
 __device__ __forceinline__ bool to_raise_mu(const ToCfgDev& c, double* mu) {
   *mu = fmax(*mu * c.mu_up, c.mu_min);
@@ -431,6 +500,247 @@ __device__ __forceinline__ void to_lower_mu(const ToCfgDev& c, double* mu) {
 __device__ __forceinline__ bool to_admissible(const ToCfgDev& c, double J, double Jc, double alpha, const double* dJ) {
   return isfinite(Jc) && (J - Jc >= c.armijo * -(alpha * dJ[0] + alpha * alpha * dJ[1])) && Jc <= J;
 }
+
+// Entry. false: there is nothing to optimise — the episode is skipped (Te < 0: no output is
+// touched), or its length does not fit the caller's buffers (FAILED after 0 passes, written by
+// the thread(s) with writer set).
+__device__ __forceinline__ bool to_enter(int Te, int64_t ldS, int64_t ldU, const ToOut& out, int e, bool writer) {
+  if (Te < 0) return false;
+  if (to_valid_len(Te, ldS, ldU)) return true;
+  if (writer) {
+    out.status[e] = CACTO_TO_FAILED;
+    out.iters[e] = 0;
+  }
+  return false;
+}
+// The state before the first pass, from the warm start's cost
+__device__ __forceinline__ ToIter to_iter_begin(int Te, double J) {
+  ToIter s{CACTO_TO_MAXITER, 0, 0.0, J, J};
+  if (Te == 0) s.status = CACTO_TO_CONVERGED;
+  if (!isfinite(J)) s.status = CACTO_TO_FAILED;
+  return s;
+}
+// What a backward pass that returned pd (-1, or the step that was not positive definite) and dJ
+// asks for: mu raised, nothing more (the stopping rule), or a line search along its gains
+enum ToVerdict { TO_RAISE, TO_STOP, TO_SEARCH };
+__device__ __forceinline__ ToVerdict to_verdict(const ToCfgDev& c, int pd, const double* dJ) {
+  if (pd >= 0) return TO_RAISE;
+  return dJ[2] <= c.gtol ? TO_STOP : TO_SEARCH;
+}
+// The end of a pass: after that verdict and, with TO_SEARCH, a line search that picked
+// alpha = 2^-sel, whose roll-out costs Jsel, or nothing (sel < 0). A pass that gave no step
+// raises mu (the retry counts as a pass; FAILED past mu_max), an accepted step lowers it.
+__device__ __forceinline__ void to_decide(const ToCfgDev& c, ToIter& s, ToVerdict v, int sel, double Jsel) {
+  ++s.iters;
+  if (v == TO_STOP) {
+    s.status = CACTO_TO_CONVERGED;
+  } else if (v == TO_SEARCH && sel >= 0) {
+    s.J = Jsel;
+    to_lower_mu(c, &s.mu);
+  } else if (to_raise_mu(c, &s.mu)) {
+    s.status = CACTO_TO_FAILED;
+  }
+}
+__device__ __forceinline__ void to_iter_store(const ToIter& s, const ToOut& out, int e) {
+  out.status[e] = s.status;
+  out.iters[e] = s.iters;
+  out.J[(size_t)e * 2] = s.J0;
+  out.J[(size_t)e * 2 + 1] = s.J;
+}
+
+// The host-issued solver keeps the state in global memory between its launches: live (Te while
+// the episode is being optimised, -1 once finished or skipped: the derivative and gains kernels
+// skip it), mu, J; pass count, status and J0 in the outputs; done counts the finished episodes
+// (the host's poll).
+struct ToState {
+  int32_t* live;
+  double* mu;
+  double* J;
+  int32_t* done;
+};
+__device__ __forceinline__ ToIter to_state_load(const ToState& st, const ToOut& out, int e) {
+  return ToIter{CACTO_TO_MAXITER, out.iters[e], st.mu[e], st.J[e], out.J[(size_t)e * 2]};
+}
+__device__ __forceinline__ void to_state_store(const ToIter& s, int Te, const ToState& st, const ToOut& out, int e) {
+  to_iter_store(s, out, e);
+  st.mu[e] = s.mu;
+  st.J[e] = s.J;
+  st.live[e] = s.running() ? Te : -1;
+  if (!s.running()) atomicAdd(st.done, 1);
+}
+
+// The warm start of one episode, in place in cur: the copy of s0 and of the controls of nodes
+// first, first + stride, ... of U_init, then (on one thread, after the copy) the roll-out, which
+// leaves the node costs in cost and returns their sum.
+template <int NJ>
+__device__ __forceinline__ void to_warm_copy(const double* S0, const double* U_init, int64_t ldU, int e, int Te,
+                                             const Traj& cur, int first, int stride) {
+  constexpr int ns = Dims<NJ>::NS, na = Dims<NJ>::NA;
+  if (first == 0)
+#pragma unroll
+    for (int k = 0; k < ns; ++k) cur.S.at(0, k) = S0[(size_t)e * ns + k];
+  for (int t = first; t < Te; t += stride)
+#pragma unroll
+    for (int j = 0; j < na; ++j) cur.U.at(t, j) = U_init[((size_t)e * ldU + t) * na + j];
+}
+template <int NJ>
+__device__ __forceinline__ double to_warm_rollout(const SysDevice& sd, int Te, const Traj& cur, const View& cost) {
+  const Gains none{View{nullptr, 0, 0}, View{nullptr, 0, 0}};
+  return to_forward_thread<NJ, true>(sd, cur, none, Te, 0.0, cur, cost);
+}
+template <int NJ>
+__device__ __forceinline__ double to_warm_start_thread(const SysDevice& sd, const double* S0, const double* U_init, int64_t ldU,
+                                                       int e, int Te, const Traj& cur, const View& cost) {
+  to_warm_copy<NJ>(S0, U_init, ldU, e, Te, cur, 0, 1);
+  return to_warm_rollout<NJ>(sd, Te, cur, cost);
+}
+
+// One candidate of the line search on one thread: the cost of alpha = 2^-j rolled out without
+// storing it, or NaN when the step is not admissible.
+template <int NJ>
+__device__ __forceinline__ double to_ls_candidate(const SysDevice& sd, const ToCfgDev& cfg, const Traj& cur, const Gains& g, int Te,
+                                                  int j, double J, const double* dJ, const View& cost) {
+  const double alpha = ldexp(1.0, -j);
+  const double Jc = to_forward_thread<NJ, false>(sd, cur, g, Te, alpha, cur, cost);
+  return to_admissible(cfg, J, Jc, alpha, dJ) ? Jc : __builtin_nan("");
+}
+// The smallest admissible j among to_ls_candidate's values cand [0..max_ls] — by definition what
+// sequential backtracking picks — or -1 (always, where no search was asked for: all are NaN)
+__device__ __forceinline__ int to_pick(const ToCfgDev& cfg, const double* cand) {
+  for (int q = 0; q <= cfg.max_ls; ++q)
+    if (cand[q] == cand[q]) return q;
+  return -1;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Which solver runs a (system, path), and the one map of cacto_to_solve's workspace
+// ---------------------------------------------------------------------------------------------
+// The systems whose node derivatives come as records of the label pass's kernels (car_park,
+// manipulator, UR5); the others (single integrator, car, double integrator) have closed forms
+template <int NJ>
+constexpr bool to_split() {
+  return NJ > 2 || NJ == -2;
+}
+// Of those, car_park has a persistent kernel; the revolute chains have none
+template <int NJ>
+constexpr bool to_persistent() {
+  return NJ == -2;
+}
+enum ToSolver {
+  TO_SOLVER_THREAD,  // k_to_solve_thread
+  TO_SOLVER_WAVE,    // k_to_solve_wave
+  TO_SOLVER_HOST,    // k_to_init, then per pass the derivative kernels, k_to_gains_wave, k_to_linesearch
+  TO_SOLVER_SPLIT,   // k_to_solve_split
+};
+template <int NJ>
+constexpr ToSolver to_route(int path) {
+  const bool wave = path == CACTO_TO_PATH_WAVE;
+  if (!to_split<NJ>()) return wave ? TO_SOLVER_WAVE : TO_SOLVER_THREAD;
+  return wave && to_persistent<NJ>() ? TO_SOLVER_SPLIT : TO_SOLVER_HOST;
+}
+// Threads per workgroup of k_to_solve_split: car_park's phases hold no per-thread LDS and a
+// 100-step episode's nodes fit one stride
+constexpr int TO_SPLIT_THREADS = 256;
+
+inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
+
+// doubles of derivative records (and, revolute chains, the primal workspace) for ldS steps
+template <int NJ>
+size_t to_rec_doubles(int n_ep, int64_t ldS) {
+  size_t n = (size_t)ldS * DdpRec<NJ>::R * n_ep;
+  if constexpr (NJ > 2) n += (size_t)ldS * DdpPrim<NJ>::R * n_ep;
+  return n;
+}
+
+// The workspace of cacto_to_solve as a solver sees it: 256-byte aligned blocks, carved in the
+// constructor and nowhere else (ws may be null: bytes alone is wanted). E = n_ep, L = ldS.
+//   thread  order [E] + hist [L + 1] | lanes: S [L][ns][E], U [L][na][E], cost [L][E], k [L][na][E],
+//           K [L][na*nx][E], handed out by lanes_views
+//   wave    order [E] + hist [L + 1] | a block of the thread solver's size, at its head per episode the
+//           gains k [L][na], K [L][na*nx] | per episode the records [L][ToRec::R]
+//   split   per episode the gains k [L][na], K [L][na*nx] | per episode the records [L][DdpRec::R]
+//   host    live [E], pd [E], done | mu [E], J [E], dJ [E][3], k [E][L][na], K [E][L][na*nx] (indexed
+//           with ldU <= L by the kernels) | the records [t][k][e] (+ the chains' primal workspace)
+// The wave and split solvers keep trajectory and node costs in the caller's S / U / step_cost.
+template <int NJ>
+struct ToWs {
+  static constexpr int N = DdpDims<NJ>::N, M = DdpDims<NJ>::M;
+  size_t E, L, bytes;
+  int32_t *order, *hist;  // k_to_order's output and scratch
+  double* lanes;
+  double *k, *K, *rec;
+  ToState st;
+  int32_t* pd;
+  double* dJ;
+
+  ToWs(void* ws, int n_ep, int64_t ldS, ToSolver solver) : E((size_t)n_ep), L((size_t)ldS), bytes(0) {
+    order = hist = st.live = st.done = pd = nullptr;
+    lanes = k = K = rec = st.mu = st.J = dJ = nullptr;
+    const size_t g = E * L * M, G = g * N;
+    if (solver == TO_SOLVER_THREAD || solver == TO_SOLVER_WAVE) {
+      order = take<int32_t>(ws, E);
+      hist = take<int32_t>(ws, L + 1);
+      close();
+      if (solver == TO_SOLVER_THREAD) {
+        lanes = take<double>(ws, lanes_doubles(E, L));
+        close();
+      } else {
+        k = take<double>(ws, lanes_doubles(E, L));
+        close();
+        rec = take<double>(ws, E * L * ToRec<NJ>::R);
+        close();
+      }
+    } else {
+      if (solver == TO_SOLVER_SPLIT) {
+        k = take<double>(ws, g + G);
+      } else {
+        st.live = take<int32_t>(ws, E);
+        pd = take<int32_t>(ws, E);
+        st.done = take<int32_t>(ws, 1);
+        close();
+        st.mu = take<double>(ws, E);
+        st.J = take<double>(ws, E);
+        dJ = take<double>(ws, 3 * E);
+        k = take<double>(ws, g);
+        K = take<double>(ws, G);
+      }
+      close();
+      rec = take<double>(ws, to_rec_doubles<NJ>(n_ep, ldS));
+      close();
+    }
+  }
+  // The thread solver's block, [t][k][e] (a wave's lanes touch consecutive addresses), and episode
+  // e's views into it. k_to_solve_thread is given the block as one __restrict__ pointer, not this
+  // struct: with the five arrays as pointers the compiler cannot tell from its other arguments it
+  // ran a third slower at 4096 episodes (2.9 s against 2.1 s on the double integrator).
+  static constexpr size_t lanes_doubles(size_t E, size_t L) { return E * L * (size_t)(N + 1 + M + 1 + M + M * N); }
+  __device__ static __forceinline__ void lanes_views(double* blk, size_t E, size_t L, int e, Traj* cur, View* cost, Gains* g) {
+    double* S = blk + e;
+    double* U = S + L * (N + 1) * E;
+    double* C = U + L * M * E;
+    double* k = C + L * E;
+    double* K = k + L * M * E;
+    *cur = Traj{View{S, (N + 1) * E, E}, View{U, M * E, E}};
+    *cost = View{C, E, E};
+    *g = Gains{View{k, M * E, E}, View{K, (size_t)M * N * E, E}};
+  }
+  // episode e's gains (k [L][na], then K [L][na*nx], from this->k) and records (R doubles per
+  // node), wave and split solvers
+  __device__ __forceinline__ Gains episode_gains(int e) const {
+    double* p = k + (size_t)e * L * (M + M * N);
+    return Gains{View{p, (size_t)M, 1}, View{p + L * M, (size_t)M * N, 1}};
+  }
+  __device__ __forceinline__ double* episode_rec(int e, int R) const { return rec + (size_t)e * L * R; }
+
+ private:
+  template <class T>
+  T* take(void* ws, size_t n) {
+    T* p = ws ? reinterpret_cast<T*>(static_cast<char*>(ws) + bytes) : nullptr;
+    bytes += n * sizeof(T);
+    return p;
+  }
+  void close() { bytes = align256(bytes); }
+};
 
 // Episodes sorted by decreasing length (counting sort over Te; one workgroup). order [n_ep],
 // hist [ldS + 1] scratch. The place of an episode among those of its own length depends on the
@@ -462,16 +772,17 @@ __global__ void __launch_bounds__(256) k_to_order(const int32_t* __restrict__ ns
   }
 }
 
-// The solver of the closed-form family: one thread per episode, the whole loop on the device.
-// ws: trajectory S [ldS][ns][n_ep], U [ldS][na][n_ep], node costs [ldS][n_ep], gains k
-// [ldS][na][n_ep], K [ldS][na*nx][n_ep]. The line search evaluates the candidates' costs without
-// storing them and rolls the accepted one out again in place.
+// The thread solver (closed-form systems, path 0): one thread per episode, the whole loop on the
+// device; trajectory, node costs and gains in the workspace (ToWs::lanes_views), copied out at the
+// end. Its own phases: the backward pass with every node evaluated on the spot, and sequential
+// backtracking that stops at the first admissible step — a candidate's cost is evaluated without
+// storing it, and the accepted one is rolled out again in place.
 template <int NJ>
 __global__ void __launch_bounds__(64) k_to_solve_thread(const SysDevice* __restrict__ sdp, const double* __restrict__ S0,
                                                          const double* __restrict__ U_init, int64_t ldU,
                                                          const int32_t* __restrict__ nsteps, int n_ep, int64_t ldS,
                                                          ToCfgDev cfg, const int32_t* __restrict__ order,
-                                                         double* __restrict__ ws, double* __restrict__ S_out,
+                                                         double* __restrict__ lanes, double* __restrict__ S_out,
                                                          double* __restrict__ U_out, double* __restrict__ cost_out,
                                                          int32_t* __restrict__ status_out, int32_t* __restrict__ iters_out,
                                                          double* __restrict__ J_out) {
@@ -480,68 +791,23 @@ __global__ void __launch_bounds__(64) k_to_solve_thread(const SysDevice* __restr
   if (slot >= n_ep) return;
   const int e = order[slot];
   const int Te = nsteps[e];
-  if (Te < 0) return;
-  if (!to_valid_len(Te, ldS, ldU)) {
-    status_out[e] = CACTO_TO_FAILED;
-    iters_out[e] = 0;
-    return;
-  }
+  const ToOut out{status_out, iters_out, J_out};
+  if (!to_enter(Te, ldS, ldU, out, e, true)) return;
   const SysDevice& sd = *sdp;
-  const size_t E = (size_t)n_ep, L = (size_t)ldS;
-  double* wS = ws + e;
-  double* wU = wS + L * ns * E;
-  double* wC = wU + L * M * E;
-  double* wk = wC + L * E;
-  double* wK = wk + L * M * E;
-  const Traj cur{View{wS, ns * E, E}, View{wU, M * E, E}};
-  const Gains g{View{wk, M * E, E}, View{wK, (size_t)M * N * E, E}};
-  const View cost{wC, E, E};
-  // the warm start: U_init rolled out from s0
-#pragma unroll
-  for (int k = 0; k < ns; ++k) cur.S.at(0, k) = S0[(size_t)e * ns + k];
-  for (int t = 0; t < Te; ++t)
-#pragma unroll
-    for (int j = 0; j < M; ++j) cur.U.at(t, j) = U_init[((size_t)e * ldU + t) * M + j];
-  const Gains none{View{nullptr, 0, 0}, View{nullptr, 0, 0}};
-  double J = to_forward_thread<NJ, true>(sd, cur, none, Te, 0.0, cur, cost);
-  const double J0 = J;
-  int status = CACTO_TO_MAXITER, iters = 0;
-  if (Te == 0) status = CACTO_TO_CONVERGED;
-  if (!isfinite(J)) status = CACTO_TO_FAILED;
-  if (status == CACTO_TO_MAXITER) {
-    double Minv[NJ > 0 ? M * M : 1], q0[NJ > 0 ? NJ : 1];
-    if constexpr (NJ > 0) {
-#pragma unroll
-      for (int i = 0; i < NJ; ++i) q0[i] = cur.S.at(0, i);
-      to_minv<NJ>(sd, q0, Minv);
-    }
-    double mu = 0.0, dJ[3];
-    for (int it = 0; it < cfg.max_iter; ++it) {
-      ++iters;
-      const int pd = to_backward_thread<NJ>(sd, Minv, cur, Te, mu, g, dJ);
-      bool raise = pd >= 0;
-      if (!raise) {
-        if (dJ[2] <= cfg.gtol) {
-          status = CACTO_TO_CONVERGED;
-          break;
-        }
-        int sel = -1;
-        for (int j = 0; j <= cfg.max_ls && sel < 0; ++j) {
-          const double alpha = ldexp(1.0, -j);
-          const double Jc = to_forward_thread<NJ, false>(sd, cur, g, Te, alpha, cur, cost);
-          if (to_admissible(cfg, J, Jc, alpha, dJ)) sel = j;
-        }
-        if (sel >= 0) {
-          J = to_forward_thread<NJ, true>(sd, cur, g, Te, ldexp(1.0, -sel), cur, cost);
-          to_lower_mu(cfg, &mu);
-        } else {
-          raise = true;
-        }
-      }
-      if (raise && to_raise_mu(cfg, &mu)) {
-        status = CACTO_TO_FAILED;
-        break;
-      }
+  Traj cur;
+  View cost;
+  Gains g;
+  ToWs<NJ>::lanes_views(lanes, (size_t)n_ep, (size_t)ldS, e, &cur, &cost, &g);
+  ToIter s = to_iter_begin(Te, to_warm_start_thread<NJ>(sd, S0, U_init, ldU, e, Te, cur, cost));
+  if (s.running()) {
+    const ToMinv<NJ> Minv(sd, cur);
+    double dJ[3];
+    for (int it = 0; it < cfg.max_iter && s.running(); ++it) {
+      const ToVerdict v = to_verdict(cfg, to_backward_eval<NJ>(sd, Minv.a, cur, Te, s.mu, g, dJ), dJ);
+      int sel = -1;
+      for (int j = 0; v == TO_SEARCH && j <= cfg.max_ls && sel < 0; ++j)
+        if (!isnan(to_ls_candidate<NJ>(sd, cfg, cur, g, Te, j, s.J, dJ, cost))) sel = j;
+      to_decide(cfg, s, v, sel, sel >= 0 ? to_forward_thread<NJ, true>(sd, cur, g, Te, ldexp(1.0, -sel), cur, cost) : s.J);
     }
   }
   for (int t = 0; t <= Te; ++t) {
@@ -552,213 +818,73 @@ __global__ void __launch_bounds__(64) k_to_solve_thread(const SysDevice* __restr
 #pragma unroll
       for (int j = 0; j < M; ++j) U_out[((size_t)e * ldU + t) * M + j] = cur.U.at(t, j);
   }
-  status_out[e] = status;
-  iters_out[e] = iters;
-  J_out[(size_t)e * 2] = J0;
-  J_out[(size_t)e * 2 + 1] = J;
+  to_iter_store(s, out, e);
 }
 
-// Per-node record of the wave path: DdpRec's A, B, l_x, l_xx (here in the cost convention, the
-// signs already flipped) followed by l_u [M] and the diagonal of l_uu [M]. Layout [e][t][k]: one
-// episode's records are contiguous, a node's record is what the recursion reads in one go.
-template <int NJ>
-struct ToRec {
-  using RC = DdpRec<NJ>;
-  static constexpr int N = RC::N, M = RC::M;
-  static constexpr int LU = RC::R, LUU = LU + M, R = LUU + M;
+// LDS of k_to_solve_wave: what lane 0 (the backward pass) and the lane of the accepted step hand
+// to the others
+struct ToWaveLds {
+  double pass[4];  // dJ [3] of the backward pass; the cost of the roll-out just stored
+  int pd;
 };
 
-// The record of node t of one closed-form episode (t == Te: l_x, l_xx of the terminal weights
-// only): the expressions and the order of to_backward_thread.
-template <int NJ>
-__device__ inline void to_node_record(const SysDevice& sd, const double* Minv, const Traj& cur, int t, int Te,
-                                      double* r) {
-  using TR = ToRec<NJ>;
-  using RC = DdpRec<NJ>;
-  constexpr int N = TR::N, M = TR::M;
-  const cacto_sys_params& p = sd.p;
-  double w[7], x[N], lx[N], lxx[N * N];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) w[k] = t == Te ? p.w_terminal[k] : p.w_running[k];
-#pragma unroll
-  for (int k = 0; k < N; ++k) x[k] = cur.S.at(t, k);
-  ddp_lx<NJ>(sd, w, x, lx, lxx);
-#pragma unroll
-  for (int k = 0; k < N; ++k) r[RC::LX + k] = -lx[k];
-#pragma unroll
-  for (int k = 0; k < N * N; ++k) r[RC::LXX + k] = -lxx[k];
-  if (t == Te) return;
-  double A[N * N], B[N * M];
-  ddp_jacobians<NJ>(sd, x, Minv, A, B);
-#pragma unroll
-  for (int k = 0; k < N * N; ++k) r[RC::A + k] = A[k];
-#pragma unroll
-  for (int k = 0; k < N * M; ++k) r[RC::B + k] = B[k];
-#pragma unroll
-  for (int j = 0; j < M; ++j) {
-    double lu, luu;
-    to_lu(p, w[6], cur.U.at(t, j), j, &lu, &luu);
-    r[TR::LU + j] = lu;
-    r[TR::LUU + j] = luu;
-  }
-}
-
-// The Riccati recursion of one episode from its records, on one thread: to_backward_thread with
-// the derivatives read instead of evaluated. Returns -1, or the step at which Qbar_uu was not
-// positive definite. dJ [3] is reset here.
-template <int NJ>
-__device__ inline int to_backward_records(const double* rec, int Te, double mu, const Gains& g, double* dJ) {
-  using TR = ToRec<NJ>;
-  using RC = DdpRec<NJ>;
-  constexpr int N = TR::N, M = TR::M;
-  double Vx[N], Vxx[N * N];
-  {
-    const double* r = rec + (size_t)Te * TR::R;
-#pragma unroll
-    for (int k = 0; k < N; ++k) Vx[k] = r[RC::LX + k];
-#pragma unroll
-    for (int k = 0; k < N * N; ++k) Vxx[k] = r[RC::LXX + k];
-  }
-  dJ[0] = dJ[1] = dJ[2] = 0.0;
-  for (int i = Te - 1; i >= 0; --i) {
-    const double* r = rec + (size_t)i * TR::R;
-    double A[N * N], B[N * M], lx[N], lxx[N * N], lu[M], luu[M], kk[M], KK[M * N];
-#pragma unroll
-    for (int k = 0; k < N * N; ++k) {
-      A[k] = r[RC::A + k];
-      lxx[k] = r[RC::LXX + k];
-    }
-#pragma unroll
-    for (int k = 0; k < N * M; ++k) B[k] = r[RC::B + k];
-#pragma unroll
-    for (int k = 0; k < N; ++k) lx[k] = r[RC::LX + k];
-#pragma unroll
-    for (int j = 0; j < M; ++j) {
-      lu[j] = r[TR::LU + j];
-      luu[j] = r[TR::LUU + j];
-    }
-    if (!to_riccati_step<N, M>(A, B, lx, lxx, lu, luu, mu, Vx, Vxx, kk, KK, dJ)) return i;
-#pragma unroll
-    for (int j = 0; j < M; ++j) g.k.at(i, j) = kk[j];
-#pragma unroll
-    for (int q = 0; q < M * N; ++q) g.K.at(i, q) = KK[q];
-  }
-  return -1;
-}
-
-// The solver of the closed-form family with one 64-lane workgroup per episode (cfg.path =
-// CACTO_TO_PATH_WAVE): the algorithm of k_to_solve_thread, the whole loop on the device. Per pass
-// the lanes stride over the nodes for the derivative records, lane 0 runs the Riccati recursion
-// from them in to_backward_thread's operation order, lane j <= max_ls evaluates the cost of
-// alpha = 2^-j without storing it, and the lane of the smallest admissible j (by definition what
-// sequential backtracking picks) rolls that step out in place. mu, J, status and the iteration
-// count are held by every lane alike, so all branches on them are uniform. The trajectory and the
-// node costs live in the caller's S / U / step_cost (rows past Te are never touched); ws: gains k
-// [n_ep][ldS][na], K [n_ep][ldS][na*nx]; rec_ws: the records [n_ep][ldS][ToRec::R].
+// The wave solver (closed-form systems, path 1): one 64-lane workgroup per episode, for
+// per-episode calls and batches too small to fill the device with one thread per episode. The
+// trajectory and the node costs live in the caller's S / U / step_cost (rows past Te are never
+// touched); gains and node records in the workspace (ToWs: episode_*). Its own phases: the lanes
+// stride over the nodes for the records and lane 0 runs the recursion from them; lane
+// j <= max_ls evaluates the cost of alpha = 2^-j without storing it, and the lane of the
+// smallest admissible j rolls that step out in place.
 template <int NJ>
 __global__ void __launch_bounds__(64) k_to_solve_wave(const SysDevice* __restrict__ sdp, const double* __restrict__ S0,
                                                        const double* U_init, int64_t ldU,
                                                        const int32_t* __restrict__ nsteps, int n_ep, int64_t ldS,
-                                                       ToCfgDev cfg, const int32_t* __restrict__ order, double* ws,
-                                                       double* rec_ws, double* S_out, double* U_out, double* cost_out,
-                                                       int32_t* __restrict__ status_out, int32_t* __restrict__ iters_out,
-                                                       double* __restrict__ J_out) {
+                                                       ToCfgDev cfg, ToWs<NJ> lay, double* S_out, double* U_out,
+                                                       double* cost_out, int32_t* __restrict__ status_out,
+                                                       int32_t* __restrict__ iters_out, double* __restrict__ J_out) {
   using TR = ToRec<NJ>;
-  constexpr int N = DdpDims<NJ>::N, M = DdpDims<NJ>::M, ns = N + 1;
-  __shared__ double sPass[4];  // dJ [3] of the backward pass; the cost of the roll-out just stored
-  __shared__ int sPd;
+  __shared__ ToWaveLds lds;
   const int lane = threadIdx.x;
-  const int e = order[blockIdx.x];
+  const int e = lay.order[blockIdx.x];
   const int Te = nsteps[e];
-  if (Te < 0) return;  // every exit up to the loop is uniform over the workgroup
-  if (!to_valid_len(Te, ldS, ldU)) {
-    if (lane == 0) {
-      status_out[e] = CACTO_TO_FAILED;
-      iters_out[e] = 0;
-    }
-    return;
-  }
+  const ToOut out{status_out, iters_out, J_out};
+  if (!to_enter(Te, ldS, ldU, out, e, lane == 0)) return;  // uniform over the workgroup
   const SysDevice& sd = *sdp;
-  const size_t L = (size_t)ldS;
   const Traj cur = api_traj<NJ>(S_out, ldS, U_out, ldU, e);
   const View cost{cost_out + (size_t)e * ldS, 1, 1};
-  double* wk = ws + (size_t)e * L * (M + M * N);
-  const Gains g{View{wk, (size_t)M, 1}, View{wk + L * M, (size_t)M * N, 1}};
-  double* rec = rec_ws + (size_t)e * L * TR::R;
-  // the warm start: U_init rolled out from s0
-  if (lane == 0)
-#pragma unroll
-    for (int k = 0; k < ns; ++k) cur.S.at(0, k) = S0[(size_t)e * ns + k];
-  for (int t = lane; t < Te; t += 64)
-#pragma unroll
-    for (int j = 0; j < M; ++j) cur.U.at(t, j) = U_init[((size_t)e * ldU + t) * M + j];
+  const Gains g = lay.episode_gains(e);
+  double* rec = lay.episode_rec(e, TR::R);
+  to_warm_copy<NJ>(S0, U_init, ldU, e, Te, cur, lane, 64);
   __syncthreads();
-  if (lane == 0) {
-    const Gains none{View{nullptr, 0, 0}, View{nullptr, 0, 0}};
-    sPass[3] = to_forward_thread<NJ, true>(sd, cur, none, Te, 0.0, cur, cost);
-  }
+  if (lane == 0) lds.pass[3] = to_warm_rollout<NJ>(sd, Te, cur, cost);
   __syncthreads();
-  double J = sPass[3];
-  const double J0 = J;
-  int status = CACTO_TO_MAXITER, iters = 0;
-  if (Te == 0) status = CACTO_TO_CONVERGED;
-  if (!isfinite(J)) status = CACTO_TO_FAILED;
-  if (status == CACTO_TO_MAXITER) {
-    double Minv[NJ > 0 ? M * M : 1], q0[NJ > 0 ? NJ : 1];
-    if constexpr (NJ > 0) {
-#pragma unroll
-      for (int i = 0; i < NJ; ++i) q0[i] = cur.S.at(0, i);
-      to_minv<NJ>(sd, q0, Minv);
-    }
-    double mu = 0.0, dJ[3];
-    const double alpha = ldexp(1.0, -lane);
-    for (int it = 0; it < cfg.max_iter; ++it) {
-      ++iters;
-      for (int t = lane; t <= Te; t += 64) to_node_record<NJ>(sd, Minv, cur, t, Te, rec + (size_t)t * TR::R);
+  ToIter s = to_iter_begin(Te, lds.pass[3]);
+  if (s.running()) {
+    const ToMinv<NJ> Minv(sd, cur);
+    for (int it = 0; it < cfg.max_iter && s.running(); ++it) {
+      for (int t = lane; t <= Te; t += 64) to_node_record<NJ>(sd, Minv.a, cur, t, t == Te, rec + (size_t)t * TR::R);
       __syncthreads();
       if (lane == 0) {
         double d[3];
-        sPd = to_backward_records<NJ>(rec, Te, mu, g, d);
+        lds.pd = to_backward_thread<NJ>([rec](int t, bool, double*) { return (const double*)(rec + (size_t)t * TR::R); }, Te,
+                                        s.mu, g, d);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) sPass[k] = d[k];
+        for (int k = 0; k < 3; ++k) lds.pass[k] = d[k];
       }
       __syncthreads();
-      const int pd = sPd;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) dJ[k] = sPass[k];
-      bool raise = pd >= 0;
-      if (!raise) {
-        if (dJ[2] <= cfg.gtol) {
-          status = CACTO_TO_CONVERGED;
-          break;
-        }
-        bool ok = false;
-        if (lane <= cfg.max_ls) {
-          const double Jc = to_forward_thread<NJ, false>(sd, cur, g, Te, alpha, cur, cost);
-          ok = to_admissible(cfg, J, Jc, alpha, dJ);
-        }
-        const unsigned long long adm = __ballot(ok);
-        if (adm != 0ull) {
-          if (lane == __ffsll(adm) - 1) sPass[3] = to_forward_thread<NJ, true>(sd, cur, g, Te, alpha, cur, cost);
-          __syncthreads();
-          J = sPass[3];
-          to_lower_mu(cfg, &mu);
-        } else {
-          raise = true;
-        }
+      const double dJ[3] = {lds.pass[0], lds.pass[1], lds.pass[2]};
+      const ToVerdict v = to_verdict(cfg, lds.pd, dJ);
+      int sel = -1;
+      if (v == TO_SEARCH) {
+        const bool ok = lane <= cfg.max_ls && !isnan(to_ls_candidate<NJ>(sd, cfg, cur, g, Te, lane, s.J, dJ, cost));
+        sel = __ffsll(__ballot(ok)) - 1;
+        if (lane == sel) lds.pass[3] = to_forward_thread<NJ, true>(sd, cur, g, Te, ldexp(1.0, -sel), cur, cost);
+        __syncthreads();
       }
-      if (raise && to_raise_mu(cfg, &mu)) {
-        status = CACTO_TO_FAILED;
-        break;
-      }
+      to_decide(cfg, s, v, sel, lds.pass[3]);
     }
   }
-  if (lane == 0) {
-    status_out[e] = status;
-    iters_out[e] = iters;
-    J_out[(size_t)e * 2] = J0;
-    J_out[(size_t)e * 2 + 1] = J;
-  }
+  if (lane == 0) to_iter_store(s, out, e);
 }
 
 // LDS of the backward pass of one split-family episode (operands, products, gains of one step)
@@ -963,32 +1089,10 @@ __global__ void __launch_bounds__(64) k_to_gains_wave(const SysDevice* __restric
   }
 }
 
-// Solver state of the split family, per episode: live (Te while the episode is being optimised,
-// -1 once finished or skipped: the derivative and gains kernels skip it), mu, J; done counts the
-// finished episodes (the host's poll).
-struct ToState {
-  int32_t* live;
-  double* mu;
-  double* J;
-  int32_t* done;
-};
-
-// The warm start of one episode on one thread: s0 and U_init copied into cur and rolled out in
-// place (node costs to cost). Returns the roll-out's cost.
-template <int NJ>
-__device__ __forceinline__ double to_warm_start_thread(const SysDevice& sd, const double* S0, const double* U_init, int64_t ldU,
-                                              int e, int Te, const Traj& cur, const View& cost) {
-  constexpr int ns = Dims<NJ>::NS, na = Dims<NJ>::NA;
-#pragma unroll
-  for (int k = 0; k < ns; ++k) cur.S.at(0, k) = S0[(size_t)e * ns + k];
-  for (int t = 0; t < Te; ++t)
-#pragma unroll
-    for (int j = 0; j < na; ++j) cur.U.at(t, j) = U_init[((size_t)e * ldU + t) * na + j];
-  const Gains none{View{nullptr, 0, 0}, View{nullptr, 0, 0}};
-  return to_forward_thread<NJ, true>(sd, cur, none, Te, 0.0, cur, cost);
-}
-
-// Warm start of the split family: U_init rolled out from s0 into the caller's S / U / step_cost.
+// The host-issued solver (car_park, manipulator and UR5 on path 0; the chains also on path 1):
+// k_to_init, then per pass the derivative kernels of the label pass (fed ToState::live as nsteps),
+// k_to_gains_wave and k_to_linesearch, the state in ToState in between. k_to_init: the warm
+// start, rolled out into the caller's S / U / step_cost, one thread per episode.
 template <int NJ>
 __global__ void __launch_bounds__(64) k_to_init(const SysDevice* __restrict__ sdp, const double* __restrict__ S0,
                                                 const double* __restrict__ U_init, int64_t ldU,
@@ -999,75 +1103,21 @@ __global__ void __launch_bounds__(64) k_to_init(const SysDevice* __restrict__ sd
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n_ep) return;
   const int Te = nsteps[e];
-  st.mu[e] = 0.0;
-  st.live[e] = -1;
-  if (Te < 0) {
+  const ToOut out{status_out, iters_out, J_out};
+  if (!to_enter(Te, ldS, ldU, out, e, true)) {
+    st.live[e] = -1;
     atomicAdd(st.done, 1);
     return;
   }
-  if (!to_valid_len(Te, ldS, ldU)) {
-    status_out[e] = CACTO_TO_FAILED;
-    iters_out[e] = 0;
-    atomicAdd(st.done, 1);
-    return;
-  }
-  const double J = to_warm_start_thread<NJ>(*sdp, S0, U_init, ldU, e, Te, api_traj<NJ>(S_out, ldS, U_out, ldU, e),
-                                            View{cost_out + (size_t)e * ldS, 1, 1});
-  st.J[e] = J;
-  J_out[(size_t)e * 2] = J;
-  J_out[(size_t)e * 2 + 1] = J;
-  iters_out[e] = 0;
-  int status = CACTO_TO_MAXITER;
-  if (Te == 0) status = CACTO_TO_CONVERGED;
-  if (!isfinite(J)) status = CACTO_TO_FAILED;
-  status_out[e] = status;
-  if (status == CACTO_TO_MAXITER)
-    st.live[e] = Te;
-  else
-    atomicAdd(st.done, 1);
+  const ToIter s = to_iter_begin(Te, to_warm_start_thread<NJ>(*sdp, S0, U_init, ldU, e, Te, api_traj<NJ>(S_out, ldS, U_out, ldU, e),
+                                                              View{cost_out + (size_t)e * ldS, 1, 1}));
+  to_state_store(s, Te, st, out, e);
 }
 
-// One candidate of the line search on one thread: the cost of alpha = 2^-j rolled out without
-// storing it, or NaN when the step is not admissible.
-template <int NJ>
-__device__ __forceinline__ double to_ls_candidate(const SysDevice& sd, const ToCfgDev& cfg, const Traj& cur, const Gains& g, int Te,
-                                         int j, double J, const double* dJ, const View& cost) {
-  const double alpha = ldexp(1.0, -j);
-  const double Jc = to_forward_thread<NJ, false>(sd, cur, g, Te, alpha, cur, cost);
-  return to_admissible(cfg, J, Jc, alpha, dJ) ? Jc : __builtin_nan("");
-}
-
-// The decision of one pass of one split-family episode. pd: the backward pass's verdict; search:
-// the pass was positive definite and not converged, and cand [0..max_ls] holds to_ls_candidate's
-// values. Updates mu and, with an accepted step (*sel = its j, else -1), J. Returns the status
-// the episode ends with, or -1 when it goes on.
-__device__ __forceinline__ int to_decide(const ToCfgDev& cfg, int pd, bool search, const double* cand, double* mu, double* J,
-                                int* sel_out) {
-  int sel = -1, finished = -1;
-  bool raise = pd >= 0;
-  if (!raise) {
-    if (!search) {
-      finished = CACTO_TO_CONVERGED;
-    } else {
-      for (int q = 0; q <= cfg.max_ls && sel < 0; ++q)
-        if (cand[q] == cand[q]) sel = q;
-      if (sel >= 0) {
-        *J = cand[sel];
-        to_lower_mu(cfg, mu);
-      } else {
-        raise = true;
-      }
-    }
-  }
-  if (raise && to_raise_mu(cfg, mu)) finished = CACTO_TO_FAILED;
-  *sel_out = sel;
-  return finished;
-}
-
-// One iteration's decision and line search of the split family. A workgroup of 64 threads holds
+// One pass's decision and line search of the host-issued solver. A workgroup of 64 threads holds
 // 64 / LSP episodes (LSP: the power of two >= max_ls + 1), thread (episode, j) evaluates the cost
 // of alpha = 2^-j without storing the trajectory, the episode's first thread picks the smallest
-// admissible j and updates the episode's state, and thread j rolls the accepted step out in place.
+// admissible j and stores the episode's state, and thread j rolls the accepted step out in place.
 template <int NJ>
 __global__ void __launch_bounds__(64) k_to_linesearch(const SysDevice* __restrict__ sdp, double* S, int64_t ldS, double* U,
                                                        int64_t ldU, double* k_in, double* K_in,
@@ -1080,50 +1130,37 @@ __global__ void __launch_bounds__(64) k_to_linesearch(const SysDevice* __restric
   const int G = 64 / LSP, tid = threadIdx.x;
   const int grp = tid / LSP, j = tid - grp * LSP;
   const int e = blockIdx.x * G + grp;
-  const bool have = e < n_ep;
-  const int Te = have ? st.live[e] : -1;
+  const int Te = e < n_ep ? st.live[e] : -1;
   const bool live = Te >= 0;
+  const ToOut out{status_out, iters_out, J_out};
   double dJ[3] = {0.0, 0.0, 0.0}, J = 0.0;
-  int pd = -1;
-  if (live) {
-    pd = pd_in[e];
-    J = st.J[e];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) dJ[k] = dJ_in[(size_t)e * 3 + k];
-  }
-  const bool search = live && pd < 0 && !(dJ[2] <= cfg.gtol);
-  const double alpha = ldexp(1.0, -j);
   Traj cur{};
   Gains g{};
   View cost{};
+  ToVerdict v = TO_STOP;
   if (live) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dJ[k] = dJ_in[(size_t)e * 3 + k];
+    v = to_verdict(cfg, pd_in[e], dJ);
+    J = st.J[e];
     cur = api_traj<NJ>(S, ldS, U, ldU, e);
     g = api_gains<NJ>(k_in, K_in, ldU, e);
     cost = View{cost_out + (size_t)e * ldS, 1, 1};
   }
+  const bool search = live && v == TO_SEARCH;
   sJ[tid] = search && j <= cfg.max_ls ? to_ls_candidate<NJ>(*sdp, cfg, cur, g, Te, j, J, dJ, cost) : __builtin_nan("");
   __syncthreads();
   if (j == 0) {
-    int sel = -1;
+    const int sel = to_pick(cfg, sJ + grp * LSP);
     if (live) {
-      double mu = st.mu[e];
-      iters_out[e] += 1;
-      const int finished = to_decide(cfg, pd, search, sJ + grp * LSP, &mu, &J, &sel);
-      if (sel >= 0) {
-        st.J[e] = J;
-        J_out[(size_t)e * 2 + 1] = J;
-      }
-      st.mu[e] = mu;
-      if (finished >= 0) {
-        status_out[e] = finished;
-        st.live[e] = -1;
-        atomicAdd(st.done, 1);
-      }
+      ToIter s = to_state_load(st, out, e);
+      to_decide(cfg, s, v, sel, sJ[grp * LSP + max(sel, 0)]);
+      to_state_store(s, Te, st, out, e);
     }
     sSel[grp] = sel;
   }
   __syncthreads();
-  if (search && j == sSel[grp]) to_forward_thread<NJ, true>(*sdp, cur, g, Te, alpha, cur, cost);
+  if (search && j == sSel[grp]) to_forward_thread<NJ, true>(*sdp, cur, g, Te, ldexp(1.0, -j), cur, cost);
 }
 
 // LDS of k_to_solve_split: the backward pass's operands, and the scalars the phases hand to every
@@ -1136,22 +1173,19 @@ struct ToSplitLds {
   int pd;
 };
 
-// The solver of car_park with one workgroup of BT threads per episode (cfg.path =
-// CACTO_TO_PATH_WAVE): what k_to_init and max_iter rounds of k_ddp_derivs, k_to_gains_wave and
-// k_to_linesearch compute, the whole loop on the device, from the same device functions
-// (contraction is off, so the numbers are those of the host-issued loop bit for bit). Per pass:
-// the threads stride over the nodes for the derivative records; every wave runs the backward
-// pass's step loop and takes outputs in it (one output per thread, the same summation order per
-// output: the first of the two arrangements a wider workgroup allows, so its barriers are
-// workgroup barriers reached by all waves); thread j <= max_ls evaluates alpha = 2^-j; every
-// thread takes the decision from the candidates in LDS, and thread sel rolls the accepted step
-// out in place. Te, mu, J, the verdict, the status and the pass count are the same on every
-// thread, so every branch around a barrier is uniform. The phases hand records, gains and
-// trajectory to each other through global memory inside the workgroup: the barrier between them
-// is the ordering (nothing crosses a workgroup), and no pointer they go through is __restrict__.
-// The trajectory and the node costs live in the caller's S / U / step_cost (rows past Te, and a
-// skipped episode's, are never touched); ws: per episode the gains k [ldS][na], K [ldS][na*nx];
-// rec_ws: per episode the records [ldS][DdpRec::R], element stride 1.
+// The split solver (car_park, path 1): one workgroup of BT threads per episode, the whole loop on
+// the device, with the phases of the host-issued solver as device functions (contraction is off,
+// so the numbers are that solver's bit for bit). Its own phases: the threads stride over the
+// nodes for the derivative records; every wave runs the backward pass's step loop and takes
+// outputs in it (one output per thread, the same summation order per output: the first of the
+// two arrangements a wider workgroup allows, so its barriers are workgroup barriers reached by
+// all waves); thread j <= max_ls evaluates alpha = 2^-j into LDS, every thread takes the pick
+// from there, and thread sel rolls the accepted step out in place. The phases hand records,
+// gains and trajectory to each other through global memory inside the workgroup: the barrier
+// between them is the ordering (nothing crosses a workgroup), and no pointer they go through is
+// __restrict__. The trajectory and the node costs live in the caller's S / U / step_cost (rows
+// past Te, and a skipped episode's, are never touched); gains and records in the workspace
+// (ToWs: episode_*, the records' element stride 1).
 // The revolute chains are not instantiated: their derivative phase needs the tangent pass's LDS
 // slabs and the bodies of k_ddp_prim / k_ddp_tan / k_ddp_lx, and a build of this kernel with them
 // faulted on the GPU for a reason that has not been found.
@@ -1159,76 +1193,47 @@ template <int NJ, int BT>
 __global__ void __launch_bounds__(BT) k_to_solve_split(const SysDevice* __restrict__ sdp, const double* __restrict__ S0,
                                                         const double* U_init, int64_t ldU,
                                                         const int32_t* __restrict__ nsteps, int n_ep, int64_t ldS,
-                                                        ToCfgDev cfg, double* ws, double* rec_ws, double* S_out,
-                                                        double* U_out, double* cost_out, int32_t* __restrict__ status_out,
+                                                        ToCfgDev cfg, ToWs<NJ> lay, double* S_out, double* U_out,
+                                                        double* cost_out, int32_t* __restrict__ status_out,
                                                         int32_t* __restrict__ iters_out, double* __restrict__ J_out) {
   static_assert(NJ == -2, "k_to_solve_split: car_park only");
   using RC = DdpRec<NJ>;
-  constexpr int N = RC::N, M = RC::M;
   __shared__ ToSplitLds<NJ> lds;
   const int tid = threadIdx.x, e = blockIdx.x;
   const int Te = nsteps[e];
-  if (Te < 0) return;  // every exit up to the loop is uniform over the workgroup
-  if (!to_valid_len(Te, ldS, ldU)) {
-    if (tid == 0) {
-      status_out[e] = CACTO_TO_FAILED;
-      iters_out[e] = 0;
-    }
-    return;
-  }
-  const size_t L = (size_t)ldS;
+  const ToOut out{status_out, iters_out, J_out};
+  if (!to_enter(Te, ldS, ldU, out, e, tid == 0)) return;  // uniform over the workgroup
   const SysDevice& sd = *sdp;
   const Traj cur = api_traj<NJ>(S_out, ldS, U_out, ldU, e);
   const View cost{cost_out + (size_t)e * ldS, 1, 1};
-  double* wk = ws + (size_t)e * L * (M + M * N);
-  const Gains g{View{wk, (size_t)M, 1}, View{wk + L * M, (size_t)M * N, 1}};
-  double* rec = rec_ws + (size_t)e * L * RC::R;
+  const Gains g = lay.episode_gains(e);
+  double* rec = lay.episode_rec(e, RC::R);
   if (tid == 0) lds.pass[3] = to_warm_start_thread<NJ>(sd, S0, U_init, ldU, e, Te, cur, cost);
   __syncthreads();
-  double J = lds.pass[3];
-  const double J0 = J;
-  int status = CACTO_TO_MAXITER, iters = 0;
-  if (Te == 0) status = CACTO_TO_CONVERGED;
-  if (!isfinite(J)) status = CACTO_TO_FAILED;
-  if (status == CACTO_TO_MAXITER) {
-    double mu = 0.0;
-    for (int it = 0; it < cfg.max_iter; ++it) {
-      ++iters;
-      for (int t = tid; t <= Te; t += BT)
-        ddp_derivs_node<NJ>(sd, &cur.S.at(t, 0), t < Te ? &cur.U.at(t, 0) : nullptr, t == Te, rec + (size_t)t * RC::R, 1);
-      __syncthreads();
-      const ToPass bp = to_gains_episode<NJ, BT>(lds.gains, sd.p, cur.U.p, Te, mu, rec, (size_t)RC::R, 1, g.k.p, g.K.p, tid);
-      if (tid == 0) {
-        lds.pd = bp.pd;
+  ToIter s = to_iter_begin(Te, lds.pass[3]);
+  for (int it = 0; it < cfg.max_iter && s.running(); ++it) {
+    for (int t = tid; t <= Te; t += BT)
+      ddp_derivs_node<NJ>(sd, &cur.S.at(t, 0), t < Te ? &cur.U.at(t, 0) : nullptr, t == Te, rec + (size_t)t * RC::R, 1);
+    __syncthreads();
+    const ToPass bp = to_gains_episode<NJ, BT>(lds.gains, sd.p, cur.U.p, Te, s.mu, rec, (size_t)RC::R, 1, g.k.p, g.K.p, tid);
+    if (tid == 0) {
+      lds.pd = bp.pd;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) lds.pass[k] = bp.dJ[k];
-      }
-      __syncthreads();
-      const int pd = lds.pd;
-      double dJ[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) dJ[k] = lds.pass[k];
-      const bool search = pd < 0 && !(dJ[2] <= cfg.gtol);
-      if (tid < 64)
-        lds.cand[tid] =
-            search && tid <= cfg.max_ls ? to_ls_candidate<NJ>(sd, cfg, cur, g, Te, tid, J, dJ, cost) : __builtin_nan("");
-      __syncthreads();
-      int sel = -1;
-      const int finished = to_decide(cfg, pd, search, lds.cand, &mu, &J, &sel);
-      if (tid == sel) to_forward_thread<NJ, true>(sd, cur, g, Te, ldexp(1.0, -sel), cur, cost);
-      __syncthreads();
-      if (finished >= 0) {
-        status = finished;
-        break;
-      }
+      for (int k = 0; k < 3; ++k) lds.pass[k] = bp.dJ[k];
     }
+    __syncthreads();
+    const double dJ[3] = {lds.pass[0], lds.pass[1], lds.pass[2]};
+    const ToVerdict v = to_verdict(cfg, lds.pd, dJ);
+    if (tid < 64)
+      lds.cand[tid] = v == TO_SEARCH && tid <= cfg.max_ls ? to_ls_candidate<NJ>(sd, cfg, cur, g, Te, tid, s.J, dJ, cost)
+                                                          : __builtin_nan("");
+    __syncthreads();
+    const int sel = to_pick(cfg, lds.cand);
+    to_decide(cfg, s, v, sel, lds.cand[max(sel, 0)]);
+    if (tid == sel) to_forward_thread<NJ, true>(sd, cur, g, Te, ldexp(1.0, -sel), cur, cost);
+    __syncthreads();
   }
-  if (tid == 0) {
-    status_out[e] = status;
-    iters_out[e] = iters;
-    J_out[(size_t)e * 2] = J0;
-    J_out[(size_t)e * 2 + 1] = J;
-  }
+  if (tid == 0) to_iter_store(s, out, e);
 }
 
 }  // namespace cacto
@@ -1237,24 +1242,7 @@ using namespace cacto;
 
 namespace {
 
-inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-
 inline bool to_path_ok(int path) { return path == CACTO_TO_PATH_DEFAULT || path == CACTO_TO_PATH_WAVE; }
-
-template <int NJ>
-constexpr bool to_split() {
-  return NJ > 2 || NJ == -2;
-}
-
-// car_park has a persistent one-workgroup-per-episode kernel for cfg.path = CACTO_TO_PATH_WAVE
-// (k_to_solve_split); the revolute chains run the host-issued loop under either path
-template <int NJ>
-constexpr bool to_persistent() {
-  return NJ == -2;
-}
-// Its threads per workgroup: car_park's phases hold no per-thread LDS and a 100-step episode's
-// nodes fit one stride
-constexpr int TO_SPLIT_THREADS = 256;
 
 // the (dynamics, reward) combinations of the six systems, as cacto_ddp_backward
 template <int NJ>
@@ -1270,14 +1258,6 @@ bool to_supported(const cacto_sys* sys, const char* who) {
   }
   if (!ok) set_error(std::string(who) + ": unsupported (dynamics, reward) combination");
   return ok;
-}
-
-// doubles of derivative records (and, revolute chains, the primal workspace) for ldS steps
-template <int NJ>
-size_t to_rec_doubles(int n_ep, int64_t ldS) {
-  size_t n = (size_t)ldS * DdpRec<NJ>::R * n_ep;
-  if constexpr (NJ > 2) n += (size_t)ldS * DdpPrim<NJ>::R * n_ep;
-  return n;
 }
 
 // the derivative kernels of the label pass over (episode, step)
@@ -1338,51 +1318,15 @@ struct LaunchToForward {
   }
 };
 
-// Workspace of cacto_to_solve, in 256-byte aligned blocks.
-//   closed-form family: order [n_ep] + hist [ldS + 1] int32; trajectory, costs and gains [t][k][e]
-//                 (the wave path keeps its gains [e][t][k] at the head of that block and adds
-//                 the node records [n_ep, ldS, ToRec::R] behind it)
-//   split family: live [n_ep] int32 + done; mu, J [n_ep]; dJ [n_ep, 3]; pd [n_ep] int32; gains k
-//                 [n_ep, ldS, na], K [n_ep, ldS, na, nx]; the derivative records [t][k][e]
-//                 (car_park's wave path: per episode the gains k [ldS, na], K [ldS, na, nx],
-//                 then per episode the records [ldS, .]; no solver state)
-template <int NJ>
-struct ToWs {
-  static constexpr int N = DdpDims<NJ>::N, M = DdpDims<NJ>::M;
-  size_t off_i32, off_d, off_rec, bytes;
-  ToWs(int n_ep, int64_t ldS, int path) {
-    const size_t E = (size_t)n_ep, L = (size_t)ldS;
-    off_i32 = 0;
-    if constexpr (to_split<NJ>()) {
-      if (to_persistent<NJ>() && path == CACTO_TO_PATH_WAVE) {
-        off_d = 0;
-        off_rec = align256(E * L * (size_t)(M + M * N) * sizeof(double));
-      } else {
-        off_d = align256((2 * E + 1) * sizeof(int32_t));  // live, pd, done
-        const size_t d = 2 * E + 3 * E + E * L * M + E * L * M * N;
-        off_rec = off_d + align256(d * sizeof(double));
-      }
-      bytes = off_rec + align256(to_rec_doubles<NJ>(n_ep, ldS) * sizeof(double));
-    } else {
-      off_d = align256((E + L + 1) * sizeof(int32_t));
-      off_rec = 0;
-      bytes = off_d + align256(E * L * (size_t)(N + 1 + M + 1 + M + M * N) * sizeof(double));
-      if (path == CACTO_TO_PATH_WAVE) {
-        off_rec = bytes;
-        bytes += align256(E * L * (size_t)ToRec<NJ>::R * sizeof(double));
-      }
-    }
-  }
-};
-
 template <int NJ>
 struct LaunchToBytes {
   static int run(int n_ep, int64_t ldS, int path, size_t* out) {
-    if constexpr (DdpDims<NJ>::ok) *out = ToWs<NJ>(n_ep, ldS, path).bytes;
+    if constexpr (DdpDims<NJ>::ok) *out = ToWs<NJ>(nullptr, n_ep, ldS, to_route<NJ>(path)).bytes;
     return CACTO_OK;
   }
 };
 
+// The solvers' launches. A solver is instantiated for the systems to_route can give it.
 template <int NJ>
 struct LaunchToSolve {
   static int run(const cacto_sys* sys, const double* S0, const double* U_init, int64_t ldU, const int32_t* n, int n_ep,
@@ -1390,52 +1334,36 @@ struct LaunchToSolve {
                  int32_t* iters, double* J, void* ws, size_t ws_bytes, hipStream_t st) {
     if (!to_supported<NJ>(sys, "cacto_to_solve")) return CACTO_EUNSUPPORTED;
     if constexpr (DdpDims<NJ>::ok) {
-      const ToWs<NJ> lay(n_ep, ldS, cfg->path);
+      const ToSolver solver = to_route<NJ>(cfg->path);
+      const ToWs<NJ> lay(ws, n_ep, ldS, solver);
       CACTO_REQUIRE(ws_bytes >= lay.bytes,
                     "cacto_to_solve: workspace smaller than cacto_to_workspace_bytes_cfg for this path "
                     "(path 0: cacto_to_workspace_bytes)");
       const ToCfgDev c{cfg->max_iter, cfg->max_ls, cfg->gtol, cfg->armijo, cfg->mu_min, cfg->mu_up, cfg->mu_down, cfg->mu_max};
-      char* base = static_cast<char*>(ws);
-      constexpr int M = DdpDims<NJ>::M, N = DdpDims<NJ>::N;
-      const size_t E = (size_t)n_ep, L = (size_t)ldS;
       if constexpr (!to_split<NJ>()) {
-        int32_t* order = reinterpret_cast<int32_t*>(base + lay.off_i32);
-        int32_t* hist = order + E;
-        hipLaunchKernelGGL(k_to_order, dim3(1), dim3(256), 0, st, n, n_ep, ldS, order, hist);
+        hipLaunchKernelGGL(k_to_order, dim3(1), dim3(256), 0, st, n, n_ep, ldS, lay.order, lay.hist);
         CACTO_CHECK_HIP(hipGetLastError());
-        if (cfg->path == CACTO_TO_PATH_WAVE)
+        if (solver == TO_SOLVER_WAVE)
           hipLaunchKernelGGL(k_to_solve_wave<NJ>, dim3(n_ep), dim3(64), 0, st, sys->dev, S0, U_init, ldU, n, n_ep, ldS, c,
-                             order, reinterpret_cast<double*>(base + lay.off_d),
-                             reinterpret_cast<double*>(base + lay.off_rec), S, U, cost, status, iters, J);
+                             lay, S, U, cost, status, iters, J);
         else
           hipLaunchKernelGGL(k_to_solve_thread<NJ>, dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S0, U_init, ldU,
-                             n, n_ep, ldS, c, order, reinterpret_cast<double*>(base + lay.off_d), S, U, cost, status,
+                             n, n_ep, ldS, c, (const int32_t*)lay.order, lay.lanes, S, U, cost, status,
                              iters, J);
         CACTO_CHECK_HIP(hipGetLastError());
-      } else if (to_persistent<NJ>() && cfg->path == CACTO_TO_PATH_WAVE) {
+      } else if (solver == TO_SOLVER_SPLIT) {
         if constexpr (to_persistent<NJ>()) {
           constexpr int BT = TO_SPLIT_THREADS;
           hipLaunchKernelGGL((k_to_solve_split<NJ, BT>), dim3(n_ep), dim3(BT), 0, st, sys->dev, S0, U_init, ldU, n, n_ep,
-                             ldS, c, reinterpret_cast<double*>(base + lay.off_d),
-                             reinterpret_cast<double*>(base + lay.off_rec), S, U, cost, status, iters, J);
+                             ldS, c, lay, S, U, cost, status, iters, J);
           CACTO_CHECK_HIP(hipGetLastError());
         }
       } else {
-        int32_t* live = reinterpret_cast<int32_t*>(base + lay.off_i32);
-        int32_t* pd = live + E;
-        int32_t* done = pd + E;
-        double* mu = reinterpret_cast<double*>(base + lay.off_d);
-        double* Jc = mu + E;
-        double* dJ = Jc + E;
-        double* kg = dJ + 3 * E;
-        double* Kg = kg + E * L * M;
-        double* rec = reinterpret_cast<double*>(base + lay.off_rec);
-        const ToState state{live, mu, Jc, done};
         // the gains kernel indexes the gains with ldU; the workspace holds ldS rows of them
         CACTO_REQUIRE(ldU <= ldS, "cacto_to_solve: ldU > ldS");
-        CACTO_CHECK_HIP(hipMemsetAsync(done, 0, sizeof(int32_t), st));
+        CACTO_CHECK_HIP(hipMemsetAsync(lay.st.done, 0, sizeof(int32_t), st));
         hipLaunchKernelGGL(k_to_init<NJ>, dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S0, U_init, ldU, n, n_ep,
-                           ldS, state, S, U, cost, status, iters, J);
+                           ldS, lay.st, S, U, cost, status, iters, J);
         CACTO_CHECK_HIP(hipGetLastError());
         int LSP = 1;
         while (LSP < c.max_ls + 1) LSP *= 2;
@@ -1443,17 +1371,17 @@ struct LaunchToSolve {
         for (int it = 0; it < c.max_iter; ++it) {
           if (cfg->poll_every > 0 && it % cfg->poll_every == 0) {
             int32_t d = 0;
-            CACTO_CHECK_HIP(hipMemcpyAsync(&d, done, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            CACTO_CHECK_HIP(hipMemcpyAsync(&d, lay.st.done, sizeof(int32_t), hipMemcpyDeviceToHost, st));
             CACTO_CHECK_HIP(hipStreamSynchronize(st));
             if (d >= n_ep) break;
           }
-          const int rc = to_launch_derivs<NJ>(sys, S, ldS, U, ldU, live, n_ep, rec, st);
+          const int rc = to_launch_derivs<NJ>(sys, S, ldS, U, ldU, lay.st.live, n_ep, lay.rec, st);
           if (rc != CACTO_OK) return rc;
-          hipLaunchKernelGGL(k_to_gains_wave<NJ>, dim3(n_ep), dim3(64), 0, st, sys->dev, U, ldU, live, n_ep, ldS, 0.0,
-                             (const double*)mu, rec, kg, Kg, dJ, pd);
+          hipLaunchKernelGGL(k_to_gains_wave<NJ>, dim3(n_ep), dim3(64), 0, st, sys->dev, U, ldU, lay.st.live, n_ep, ldS,
+                             0.0, (const double*)lay.st.mu, lay.rec, lay.k, lay.K, lay.dJ, lay.pd);
           CACTO_CHECK_HIP(hipGetLastError());
-          hipLaunchKernelGGL(k_to_linesearch<NJ>, dim3(ceil_div(n_ep, G)), dim3(64), 0, st, sys->dev, S, ldS, U, ldU, kg,
-                             Kg, dJ, pd, n_ep, c, LSP, state, cost, status, iters, J);
+          hipLaunchKernelGGL(k_to_linesearch<NJ>, dim3(ceil_div(n_ep, G)), dim3(64), 0, st, sys->dev, S, ldS, U, ldU, lay.k,
+                             lay.K, lay.dJ, lay.pd, n_ep, c, LSP, lay.st, cost, status, iters, J);
           CACTO_CHECK_HIP(hipGetLastError());
         }
       }
@@ -1468,15 +1396,12 @@ struct LaunchToPlan {
   static int run(const cacto_sys* sys, int path, cacto_to_plan* out) {
     if (!to_supported<NJ>(sys, "cacto_to_solve_plan")) return CACTO_EUNSUPPORTED;
     if constexpr (DdpDims<NJ>::ok) {
-      const bool wave = path == CACTO_TO_PATH_WAVE;
-      if constexpr (!to_split<NJ>()) {
-        // k_to_solve_thread holds no LDS; k_to_solve_wave: sPass [4] and sPd, padded to 8 bytes
-        *out = cacto_to_plan{1, 64, wave ? (int32_t)(5 * sizeof(double)) : 0, 0};
-      } else if (to_persistent<NJ>() && wave) {
-        *out = cacto_to_plan{1, TO_SPLIT_THREADS, (int32_t)sizeof(ToSplitLds<NJ>), 0};
-      } else {
-        // the host-issued loop; the kernel described is its one-wave-per-episode backward pass
-        *out = cacto_to_plan{0, 64, (int32_t)sizeof(ToGainsLds<NJ>), NJ > 2 ? 5 : 3};
+      switch (to_route<NJ>(path)) {
+        case TO_SOLVER_THREAD: *out = cacto_to_plan{1, 64, 0, 0}; break;
+        case TO_SOLVER_WAVE: *out = cacto_to_plan{1, 64, (int32_t)sizeof(ToWaveLds), 0}; break;
+        case TO_SOLVER_SPLIT: *out = cacto_to_plan{1, TO_SPLIT_THREADS, (int32_t)sizeof(ToSplitLds<NJ>), 0}; break;
+        // the kernel described is the one-wave-per-episode backward pass
+        case TO_SOLVER_HOST: *out = cacto_to_plan{0, 64, (int32_t)sizeof(ToGainsLds<NJ>), NJ > 2 ? 5 : 3}; break;
       }
     }
     return CACTO_OK;

@@ -113,11 +113,21 @@ def pack_params(conf):
     return p, table
 
 
+_DYING = []     # handles of Systems that died while the current stream was capturing
+
+
+def _destroy_dying():
+    if _DYING and not torch.cuda.is_current_stream_capturing():
+        while _DYING:
+            L.lib().raw("cacto_sys_destroy")(_DYING.pop())
+
+
 class System:
     """Numeric content of a conf module + the device copy the kernels read."""
 
     def __init__(self, conf):
         require_gpu()
+        _destroy_dying()
         self.conf = conf
         p, table = pack_params(conf)
         self.params = p
@@ -129,13 +139,18 @@ class System:
         self.ns, self.na = conf.nb_state, conf.nb_action
 
     def __del__(self):
+        # cacto_sys_destroy frees device memory and synchronises and destroys a stream: none of that
+        # is legal while a stream capture is open, and it would invalidate the capture. The garbage
+        # collector can run this anywhere, torch.cuda.graph no longer collects before it captures,
+        # so a handle that dies inside a capture waits for the next System to die or be made.
         h = getattr(self, "handle", None)
         if h is not None and h.value:
-            try:
-                L.lib().raw("cacto_sys_destroy")(h)
-            except Exception:
-                pass
             self.handle = None
+            _DYING.append(h)
+        try:
+            _destroy_dying()
+        except Exception:
+            pass
 
     def param_count(self, net):
         return int(L.lib().raw("cacto_mlp_param_count")(self.handle, net))

@@ -101,6 +101,24 @@ def test_car_lengths_that_straddle_the_stride_three_passes():
         _check_steps("car", P, out["S"][e], out["U"][e], out["step_cost"][e], T)
 
 
+@pytest.mark.parametrize("system", CLOSED)
+def test_thread_and_wave_solvers_are_one_loop(system):
+    """k_to_solve_thread and k_to_solve_wave run the same transitions (to_verdict, to_decide) over
+    the same device functions, and the library is built without contraction: three passes on the
+    lengths around the stride give the same outputs bit for bit under path 0 and path 1. What each
+    kernel still does its own way (sequential backtracking against every step size at once, nodes
+    evaluated in the recursion against records) must not change a number."""
+    S0, Te = W.stride_inputs(system)
+    _, a = _solve_given(system, S0, Te, dict(R.SOLVE_CFG, path=0, max_iter=3))
+    _, b = _solve_given(system, S0, Te, dict(CFG, max_iter=3))
+    assert sorted(a) == ["J", "S", "U", "iters", "status", "step_cost"]
+    print(system, "status", a["status"].tolist(), "iters", a["iters"].tolist())
+    # the batch reaches both ends of the loop: the stopping rule (Te = 1) and the pass limit
+    assert (a["status"] == R.CONVERGED).any() and (a["status"] == R.MAXITER).any()
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name
+
+
 # ---------------------------------------------------------------------- path 0 is untouched
 def test_default_path_is_untouched():
     system = "single_integrator"
@@ -143,6 +161,42 @@ def test_wave_path_is_deterministic_and_captures_into_a_graph():
     for name in eager:
         assert torch.equal(eager[name], out[name]), name
         assert np.array_equal(eager[name].cpu().numpy(), a[name]), name
+
+
+def test_a_system_collected_inside_a_capture_does_not_invalidate_it():
+    """The garbage collector may free a System (cacto_sys_destroy: hipFree, a stream synchronised
+    and destroyed) at any allocation, also between capture begin and end, where those calls
+    invalidate the capture. Its handle then has to wait until the capture is over."""
+    import gc
+    from cacto_amd import system as Y
+    from cacto_amd.confs import load_conf
+    P, to = _setup("single_integrator")
+    S0, Te = R.solve_inputs("single_integrator")
+    E, ldU = len(Te), int(Te.max())
+    cfg = dict(CFG, poll_every=0)
+    S0_d, U0_d, Te_d = _dev(S0), _dev(np.zeros((E, ldU, P.m))), _dev(Te)
+    eager = to.solve_batch(S0_d, U0_d, Te_d, cfg=cfg, out=_prefilled(E, ldU, P.n + 1, P.m))
+    out = _prefilled(E, ldU, P.n + 1, P.m)
+    gc.collect()                            # whatever earlier tests left goes now, outside the capture
+    assert not Y._DYING
+    cycle = [Y.System(load_conf("double_integrator", fresh=True))]
+    cycle.append(cycle)                     # only the collector frees it
+    del cycle
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            gc.collect()
+            assert len(Y._DYING) == 1
+            to.solve_batch(S0_d, U0_d, Te_d, cfg=cfg, out=out)
+    torch.cuda.current_stream().wait_stream(s)
+    g.replay()
+    torch.cuda.synchronize()
+    for name in eager:
+        assert torch.equal(eager[name], out[name]), name
+    Y.System(load_conf("double_integrator", fresh=True))        # the next System buries the dead one
+    assert not Y._DYING
 
 
 # ---------------------------------------------------------------------- FAILED, and the workspace
