@@ -99,12 +99,35 @@ class ReplayBuffer:
         if dVdx is not None and dVdx.shape != S_traj.shape:
             raise ValueError("add_episodes: dVdx must have the shape of S_traj")
         total = torch.empty(E, S_traj.shape[1], dtype=torch.float64, device=DEVICE) if want_total else None
-        L.lib().call("cacto_rl_solve_add", self.sys.handle, dptr(S_traj), S_traj.shape[1], dptr(rewards),
-                     rewards.shape[1], dptr(R_term), dptr(dVdx), dptr(off_d), E, int(nsteps.max()), n,
-                     int(getattr(self.conf, "nsteps_TD_N", 0)), int(bool(self.conf.MC)), dptr(self.storage), self.N,
-                     self.next_idx, dptr(total), stream())
-        self._advance(n)
+        self._rl_solve_add(S_traj, rewards, R_term, dVdx, off_d, int(nsteps.max()), n, total)
         return total
+
+    def _rl_solve_add(self, S_traj, rewards, R_term, dVdx, off_d, max_T, n, total=None):
+        """The one cacto_rl_solve_add call of the class: n rows of S_traj.shape[0] episodes at the
+        device offsets off_d into the ring at next_idx, then the bookkeeping of add (_advance)."""
+        L.lib().call("cacto_rl_solve_add", self.sys.handle, dptr(S_traj, torch.float64), S_traj.shape[1],
+                     dptr(rewards, torch.float64), rewards.shape[1], dptr(R_term), dptr(dVdx), dptr(off_d, torch.int64),
+                     S_traj.shape[0], int(max_T), int(n), int(getattr(self.conf, "nsteps_TD_N", 0)),
+                     int(bool(self.conf.MC)), dptr(self.storage), self.N, self.next_idx, dptr(total), stream())
+        self._advance(int(n))
+
+    def add_episodes_planned(self, S_traj, rewards, row_off_d, n_rows, max_T, dVdx=None):
+        """add_episodes with the row offsets already on the device (cacto_collect_plan's row_off
+        [E + 1] int64: an episode it dropped has an empty range and adds nothing) and their total
+        n_rows = row_off[E] on the host: no host prefix sum, no status copy. S_traj [E, ldS, ns],
+        rewards [E, ldR >= max_T + 1] (r_0..r_T per episode), dVdx [E, ldS, ns] or None (zeros),
+        all f64 on the device; max_T: a host bound of the episode lengths (ldS > max_T)."""
+        n_rows = int(n_rows)
+        if n_rows == 0:
+            return
+        if n_rows > self.N:
+            raise ValueError("cannot add more rows than REPLAY_SIZE at once")
+        E = S_traj.shape[0]
+        if S_traj.dim() != 3 or S_traj.shape[2] != self.ns or rewards.shape[0] != E or row_off_d.numel() != E + 1:
+            raise ValueError("add_episodes_planned: S_traj must be [E, T+1, ns], rewards [E, *], row_off [E + 1]")
+        if dVdx is not None and dVdx.shape != S_traj.shape:
+            raise ValueError("add_episodes_planned: dVdx must have the shape of S_traj")
+        self._rl_solve_add(S_traj, rewards, None, dVdx, row_off_d, max_T, n_rows)
 
     def add(self, obses_t, rewards, obses_t1, dVdxs, dones, terms):
         """replay_buffer.py:25-36."""

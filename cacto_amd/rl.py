@@ -607,24 +607,100 @@ class RL_AC:
 
     def _env_rl_episode(self, controls, T):
         """RL.py:157-165 on the device: s_{i+1}, r_i = Env.step(w_running, s_i, u_i),
-        ee_{i+1} = EE(s_{i+1}); r_T = reward(w_terminal, s_T). One launch per step, no host sync."""
-        ns = self.conf.nb_state
-        S = torch.empty(T + 1, ns, dtype=torch.float64, device=DEVICE)
-        S[0] = torch.as_tensor(np.asarray(self.state_arr[0], dtype=np.float64), device=DEVICE)
-        R = torch.empty(T + 1, dtype=torch.float64, device=DEVICE)
-        EE = torch.empty(T + 1, 3, dtype=torch.float64, device=DEVICE)
-        U = torch.as_tensor(controls, device=DEVICE)
-        W = torch.as_tensor(np.asarray(self.conf.cost_weights_running, dtype=np.float64), device=DEVICE)
-        h = self.sys.handle
-        for i in range(T):
-            L.lib().call("cacto_env_step", h, dptr(S[i:i + 1]), dptr(U[i:i + 1].contiguous()), dptr(W),
-                         dptr(S[i + 1:i + 2]), dptr(R[i:i + 1]), dptr(EE[i + 1:i + 2]), 1, stream())
-        Wt = torch.as_tensor(np.asarray(self.conf.cost_weights_terminal, dtype=np.float64), device=DEVICE)
-        zero = torch.zeros(1, self.conf.nb_action, dtype=torch.float64, device=DEVICE)
-        L.lib().call("cacto_env_step", h, dptr(S[T:T + 1]), dptr(zero), dptr(Wt), None, dptr(R[T:T + 1]), None, 1,
+        ee_{i+1} = EE(s_{i+1}); r_T = reward(w_terminal, s_T). One launch (env_rl_episodes with one
+        episode), one copy back."""
+        ns, na = self.conf.nb_state, self.conf.nb_action
+        S0 = torch.as_tensor(np.asarray(self.state_arr[0], dtype=np.float64).reshape(1, ns), device=DEVICE)
+        U = np.zeros((1, max(T, 1), na))
+        U[0, :T] = np.asarray(controls, dtype=np.float64).reshape(-1, na)[:T]
+        S, R, EE = self.env_rl_episodes(S0, torch.as_tensor(U, device=DEVICE),
+                                        torch.tensor([T], dtype=torch.int32, device=DEVICE), T + 1)
+        return S[0].cpu().numpy(), R[0].cpu().numpy(), EE[0].cpu().numpy()
+
+    def env_rl_episodes(self, S0, U, nsteps, ldS):
+        """cacto_env_rl_episodes: RL.py:157-165 for a batch in one launch. S0 [E, ns], U [E, ldU, na]
+        f64, nsteps [E] int32 (< 0 skips the episode), all on the device. Returns (S [E, ldS, ns],
+        R [E, ldS] with r_T at column T, EE [E, ldS, 3]); rows past an episode's length, and every
+        row of a skipped episode, are zero."""
+        E = S0.shape[0]
+        f64 = dict(dtype=torch.float64, device=DEVICE)
+        S = torch.zeros(E, ldS, self.conf.nb_state, **f64)
+        R = torch.zeros(E, ldS, **f64)
+        EE = torch.zeros(E, ldS, 3, **f64)
+        L.lib().call("cacto_env_rl_episodes", self.sys.handle, dptr(S0, torch.float64), dptr(U, torch.float64),
+                     U.shape[1], dptr(nsteps, torch.int32), E, ldS, dptr(S), dptr(R), dptr(EE), stream())
+        return S, R, EE
+
+    COUNTERS = ("rows", "kept", "zero_length", "nan_rollouts", "converged", "maxiter", "failed")
+
+    def compute_samples(self, ep, ICS_list, TrOp, buffer, cfg=None, accept_maxiter=False):
+        """compute_sample (main.py:174-195) for every initial state of an iteration, followed by the
+        buffer.add of main.py:240, on the device: one roll-out launch (create_TO_init), one
+        TrOp.solve_batch (TO_System_Solve), the filter of main.py:181-187 / :236 with the ring offsets
+        (cacto_collect_plan), the Sobolev labels when TrOp.w_S != 0 (TO.py:108-112), the env_RL
+        re-simulation when conf.env_RL (RL.py:157-165), RL_Solve fused with the ring write
+        (cacto_rl_solve_add), the episode returns and the EE positions. The number of library calls
+        does not depend on len(ICS_list); the host reads the eight counters before the ring write
+        and the kept lengths and returns after it.
+
+        Dropped, as the reference drops them: NSTEPS_SH == 0 (RL.py:206-207), a roll-out that hit
+        a NaN state (RL.py:229-231), a solve that did not converge (main.py:186-187; with
+        accept_maxiter a solve that stopped at max_iter counts as a success). The rows of the kept
+        episodes go into the ring contiguously, in order.
+
+        Returns a dict: kept (host int32 [E]: NSTEPS_SH, or -1 for a dropped episode), the counters
+        of COUNTERS (rows, kept as n_kept, ...), ep_return (host float64, kept episodes in order) and
+        dev, the device tensors S, U, step_cost, status, iters, dVdx (None with w_S == 0), EE_TO, and
+        with env_RL S_RL, R_RL, EE_RL."""
+        ICS = np.asarray(ICS_list, dtype=np.float64).reshape(len(ICS_list), -1)
+        E = ICS.shape[0]
+        ns_ = np.array([self.nsteps_sh(s) for s in ICS], dtype=np.int32)
+        res = dict(kept=np.full(E, -1, dtype=np.int32), ep_return=np.zeros(0), dev={})
+        res.update({("n_kept" if k == "kept" else k): 0 for k in self.COUNTERS})
+        res["zero_length"] = int((ns_ <= 0).sum())
+        T = int(ns_.max()) if E else 0
+        if T <= 0:
+            return res
+        na = self.conf.nb_action
+        inputs = self.rollout_inputs(ICS, ns_)
+        S0_d, n_d = inputs[0], inputs[1]
+        roll = self.rollout_batch(ICS, ns_, T, ep=ep, want=("S", "A"), inputs=inputs)
+        warm = roll["A"].double() if ep != 0 else torch.zeros(E, T, na, dtype=torch.float64, device=DEVICE)
+        live = torch.where((roll["status"] == 0) & (n_d > 0), n_d, torch.full_like(n_d, -1))
+        sol = TrOp.solve_batch(S0_d, warm, live, cfg=cfg)
+        kept_d = torch.empty(E, dtype=torch.int32, device=DEVICE)
+        off_d = torch.empty(E + 1, dtype=torch.int64, device=DEVICE)
+        counts_d = torch.empty(8, dtype=torch.int64, device=DEVICE)
+        L.lib().call("cacto_collect_plan", dptr(n_d, torch.int32), dptr(roll["status"], torch.int32),
+                     dptr(sol["status"], torch.int32), int(bool(accept_maxiter)), E, dptr(kept_d), dptr(off_d),
+                     dptr(counts_d), stream())
+        counts = counts_d.cpu().tolist()
+        res.update({("n_kept" if k == "kept" else k): int(v) for k, v in zip(self.COUNTERS, counts)})
+        dev = res["dev"]
+        dev.update(S=sol["S"], U=sol["U"], step_cost=sol["step_cost"], status=sol["status"], iters=sol["iters"],
+                   dVdx=None)
+        rows = res["rows"]
+        if rows == 0:
+            return res
+        if rows > buffer.N:
+            raise ValueError("cannot add more rows than REPLAY_SIZE at once")
+        if TrOp.w_S != 0:
+            dev["dVdx"] = TrOp.backward_pass_batch(sol["S"], sol["U"], kept_d)
+        if self.conf.env_RL:
+            dev["S_RL"], dev["R_RL"], dev["EE_RL"] = self.env_rl_episodes(S0_d, sol["U"], kept_d, T + 1)
+            S_rows, R_rows, R_sum, negate = dev["S_RL"], dev["R_RL"], dev["R_RL"], 0
+        else:                                       # RL.py:166-167: the TO's states, rwrd = -TO_step_cost
+            S_rows, R_rows, R_sum, negate = sol["S"], -sol["step_cost"], sol["step_cost"], 1
+        buffer.add_episodes_planned(S_rows, R_rows, off_d, rows, T, dVdx=dev["dVdx"])
+        ret_d = torch.empty(E, dtype=torch.float64, device=DEVICE)
+        L.lib().call("cacto_episode_returns", dptr(R_sum, torch.float64), R_sum.shape[1], dptr(kept_d), E, negate,
+                     dptr(ret_d), stream())
+        dev["EE_TO"] = torch.empty(E, T + 1, 3, dtype=torch.float64, device=DEVICE)
+        L.lib().call("cacto_env_ee", self.sys.handle, dptr(sol["S"], torch.float64), dptr(dev["EE_TO"]), E * (T + 1),
                      stream())
-        L.lib().call("cacto_env_ee", h, dptr(S[0:1]), dptr(EE[0:1]), 1, stream())
-        return S.cpu().numpy(), R.cpu().numpy(), EE.cpu().numpy()
+        res["kept"] = kept_d.cpu().numpy()
+        res["ep_return"] = ret_d.cpu().numpy()[res["kept"] >= 0]
+        return res
 
     def RL_save_weights(self, update_step_counter='final'):
         """RL.py:191-195: Keras-2.11 .h5 files the reference can load."""

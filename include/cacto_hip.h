@@ -532,6 +532,43 @@ int cacto_rl_solve_add(const cacto_sys* sys, const double* S_traj_d, int64_t ldS
                        int n_ep, int max_T, int64_t total_rows, int nsteps_td, int mc, double* storage_d,
                        int64_t capacity, int64_t next_idx, double* total_d, void* stream);
 
+/* The sample-collection stage (compute_sample, main.py:174-195, for every initial state of an
+ * iteration, and the buffer.add of main.py:240). These three take the caller's stream, enqueue one
+ * kernel each and synchronise nothing; a bad argument is reported before anything is enqueued.
+ *
+ * cacto_env_rl_episodes — RL_Solve with env_RL = 1 (RL.py:157-165) for n_ep episodes, one thread per
+ * episode. With Te = nsteps_d[e]: S[e,0] = S0_d[e], EE[e,0] = EE(s_0); for t < Te
+ * S[e,t+1], R[e,t] = Env.step(cost_weights_running, S[e,t], U_d[e,t]) and EE[e,t+1] = EE(S[e,t+1]);
+ * R[e,Te] = reward(cost_weights_terminal, S[e,Te]) with no action. The device functions are those of
+ * cacto_env_step, so the numbers equal Te calls of it plus cacto_env_ee bit for bit.
+ *   S0_d [n_ep, ns], U_d [n_ep, ldU, na], nsteps_d [n_ep]; S_d [n_ep, ldS, ns], R_d [n_ep, ldS],
+ *   EE_d [n_ep, ldS, 3] (all f64; any output may be NULL). Needs Te < ldS and Te <= ldU.
+ * Te < 0 skips the episode (nothing read or written); rows past Te are untouched; Te == 0 writes
+ * row 0 only. */
+int cacto_env_rl_episodes(const cacto_sys* sys, const double* S0_d, const double* U_d, int64_t ldU,
+                          const int32_t* nsteps_d, int n_ep, int64_t ldS, double* S_d, double* R_d, double* EE_d,
+                          void* stream);
+
+/* The filter of main.py:181-187 and :236 with the row offsets cacto_rl_solve_add reads.
+ * kept_d[e] = nsteps_d[e] when nsteps_d[e] > 0 (RL.py:206-207), the roll-out status is 0
+ * (RL.py:229-231; rollout_status_d NULL: every roll-out counts as clean) and the TO status is
+ * CACTO_TO_CONVERGED, or CACTO_TO_MAXITER with accept_maxiter (to_status_d NULL: every solve counts as
+ * a success); otherwise -1. row_off_d [n_ep + 1]: the exclusive prefix sum, in episode order, of
+ * kept + 1 over kept episodes and 0 over dropped ones (a dropped episode has an empty row range).
+ * counts_d [8] = rows, kept, episodes with nsteps <= 0, NaN roll-outs (of those with nsteps > 0),
+ * CONVERGED, MAXITER, FAILED (of those that reached the solver: nsteps > 0 and a clean roll-out), 0.
+ * One workgroup, any n_ep >= 1. */
+int cacto_collect_plan(const int32_t* nsteps_d, const int32_t* rollout_status_d, const int32_t* to_status_d,
+                       int accept_maxiter, int n_ep, int32_t* kept_d, int64_t* row_off_d, int64_t* counts_d,
+                       void* stream);
+
+/* ep_return = sum(rwrd_arr) (main.py:190 / RL.py:188): ret_d[e] = 0.0 + x_0 + ... + x_Te added left to
+ * right, Te = kept_d[e] (needs Te < ldR), x_t = R_d[e, t], or -R_d[e, t] with negate (pass
+ * TO_step_cost for env_RL = 0: RL.py:167 negates each element first). ret_d[e] = 0 for kept_d[e] < 0.
+ * One thread per episode. */
+int cacto_episode_returns(const double* R_d, int64_t ldR, const int32_t* kept_d, int n_ep, int negate,
+                          double* ret_d, void* stream);
+
 /* replay_buffer.py:47-61: S, R, S_next, dVdx, d as float32, term float64; any may be NULL. */
 int cacto_buffer_gather(const cacto_sys* sys, const double* storage_d, const int32_t* idx_d, int B,
                         float* S_d, float* R_d, float* S_next_d, float* dVdx_d, float* d_d, double* term_d,
