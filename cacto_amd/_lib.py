@@ -65,6 +65,13 @@ class ToPlan(C.Structure):
                 ("launches_per_iter", C.c_int32)]
 
 
+class RoPlan(C.Structure):
+    """cacto_ro_plan: what cacto_rollout_sched runs for a batch and a schedule (cacto_rollout_plan)."""
+    _fields_ = [("kind", C.c_int32), ("groups", C.c_int32), ("workgroups", C.c_int32),
+                ("block_threads", C.c_int32), ("lds_bytes", C.c_int32), ("cus", C.c_int32)]
+
+
+RO_KIND_TEAM, RO_KIND_TWO_TEAMS, RO_KIND_WAVE_SLOT = 0, 1, 2
 CACTO_TO_CONVERGED, CACTO_TO_MAXITER, CACTO_TO_FAILED = 0, 1, 2
 CACTO_TO_PATH_DEFAULT, CACTO_TO_PATH_WAVE = 0, 1
 
@@ -116,6 +123,7 @@ _SIGS = {
     "cacto_rollout": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]),
     "cacto_rollout_sched": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int,
                                       C.c_int, C.c_int, vp]),
+    "cacto_rollout_plan": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(RoPlan)]),
     "cacto_rollout_rewards": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
     "cacto_ddp_backward": (C.c_int, [vp, vp, i64, vp, i64, vp, C.c_int, C.c_double, vp, vp]),
     "cacto_to_backward_gains": (C.c_int, [vp, vp, i64, vp, i64, vp, C.c_int, C.c_double, vp, vp, vp, vp, vp]),

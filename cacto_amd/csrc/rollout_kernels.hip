@@ -24,18 +24,72 @@
 
 #include "net_common.h"
 
+// ---------------------------------------------------------------- build-time knobs (defaults)
+#ifndef RO_STREAM_PF
+#define RO_STREAM_PF 2  // ro_layer2's L2-streamed weight rows loaded two 16-row blocks ahead (one at NG > 1)
+#endif
+// the 6-joint chain at one slot group: W2 wholly resident, REGK1 rows in registers + LDSK1 in LDS
+#ifndef RO_CHAIN6_REGK1
+#define RO_CHAIN6_REGK1 128
+#endif
+#ifndef RO_CHAIN6_LDSK1
+#define RO_CHAIN6_LDSK1 128
+#endif
+#ifndef RO_CHAIN6_PF
+#define RO_CHAIN6_PF 0  // 1: ro_layer2's LDS operands one step ahead for that kernel too (see PF there)
+#endif
+#ifndef RO_TBAR_SLEEP
+#define RO_TBAR_SLEEP 1  // s_sleep between polls of a team barrier (k_rollout_tt)
+#endif
+// Run time: the environment variable CACTO_REW_GRID=bt|c forces the reward kernel's element grid
+// (LaunchRolloutRewards; benchmarks).
+
+// ---------------------------------------------------------------- phase clock (CACTO_STAMPS)
+// One accumulator for the three kernels: lane 0 of every wave sums the cycles (s_memtime) it spends
+// in each phase of a step over the whole launch and stores them, with its step count, at
+// g_ro_clock[workgroup][hardware wave][phase]. Without CACTO_STAMPS the type is empty and every call
+// vanishes. Phases (tools/rollout_stamps.py, tools/tt_stamps.py print them):
+//   L1     layer 1 + its barrier (k_rollout: the joint placements before it; k_rollout_ks: layer 1
+//          of the wave's own slot at the end of the step)
+//   L2     layer 2 + its barrier
+//   L3     layer 3 + its barrier (k_rollout_ks: no barrier)
+//   DYN    k_rollout's revolute chains: RNEA (wave 0) / CRBA (waves 1-3) + their barrier
+//   STEP   the slot's action read and s' = f(s, a) (EARLY: and the next actor input)
+//   STORE  the end of the step: trajectory stores, NaN verdict, status
+//   REFILL the next queue entry into a finished slot
+//   X0     the next actor input and the any-slot-active ballot (wave-0 kernels)
+//   BAR    the barrier that ends the step (waves without a slot: their wait for wave 0's tail)
+enum RoPhase { RO_L1, RO_L2, RO_L3, RO_DYN, RO_STEP, RO_STORE, RO_REFILL, RO_X0, RO_BAR, RO_PHASES };
+constexpr int RO_CLOCK_WGS = 1024, RO_CLOCK_WAVES = 8, RO_CLOCK_COLS = RO_PHASES + 1;  // last column: steps
 #ifdef CACTO_STAMPS
-__device__ unsigned long long g_rstamps[20];
-__device__ unsigned long long g_ttacc[1024 * 2 * 2 * 10];  // [workgroup][team][wave 0/1][phase 0-8, steps]
-__device__ unsigned long long g_wsacc[1024 * 8 * 7];  // k_rollout_ks: [workgroup][wave][phase 0-5, steps]
-#define RSTAMP(k)                                                                     \
-  do {                                                                                \
-    if (blockIdx.x == 0 && threadIdx.x == 0 && it == 20) g_rstamps[k] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
+__device__ unsigned long long g_ro_clock[RO_CLOCK_WGS * RO_CLOCK_WAVES * RO_CLOCK_COLS];
+struct RoClock {
+  unsigned long long acc[RO_PHASES] = {}, prev = __builtin_amdgcn_s_memtime();
+  int steps = 0;
+  // the cycles since the last mark (or restart) belong to phase ph
+  __device__ __forceinline__ void mark(int ph) {
+    const unsigned long long now = __builtin_amdgcn_s_memtime();
+#pragma unroll
+    for (int k = 0; k < RO_PHASES; ++k)
+      if (k == ph) acc[k] += now - prev;
+    prev = now;
+  }
+  __device__ __forceinline__ void step_done() { ++steps; }
+  __device__ __forceinline__ void save() const {
+    if (blockIdx.x >= RO_CLOCK_WGS || (threadIdx.x & 63) != 0) return;
+    unsigned long long* o = g_ro_clock + ((size_t)blockIdx.x * RO_CLOCK_WAVES + (threadIdx.x >> 6)) * RO_CLOCK_COLS;
+    for (int k = 0; k < RO_PHASES; ++k) o[k] = acc[k];
+    o[RO_PHASES] = steps;
+  }
+};
 #else
-#define RSTAMP(k) \
-  do {            \
-  } while (0)
+// (not convergent: a convergent call, even an empty one, holds back the early control-flow
+// simplification around it and the kernels come out with other registers)
+struct RoClock {
+  [[clang::noconvergent]] __device__ __forceinline__ void mark(int) {}
+  [[clang::noconvergent]] __device__ __forceinline__ void step_done() {}
+  [[clang::noconvergent]] __device__ __forceinline__ void save() const {}
+};
 #endif
 
 namespace cacto {
@@ -60,25 +114,7 @@ __device__ __forceinline__ floatx4 mfma_bc(float x, float w, floatx4 c) {
 // dynamics of the manipulator / UR5 need many registers, so those systems keep fewer rows in
 // registers (and the UR5 streams some); the LDS share is what fits beside the step buffers.
 template <int NJ, int NG>
-#ifndef RO_DYN_IN_ACTOR
-// 1: the lane RNEA / CRBA inside the actor's layer-2 block (the scheduler keeps them after the MFMA
-// stream, and the layer-2 barrier then waits for them): 124.5 M against 132.1 M env-steps/s (UR5,
-// 2048 episodes) for the dynamics after the actor, so off
-#define RO_DYN_IN_ACTOR 0
-#endif
-#ifndef RO_STREAM_PF
-#define RO_STREAM_PF 2  // ro_layer2's L2-streamed weight rows loaded two 16-row blocks ahead (one at NG > 1)
-#endif
-#ifndef RO_CHAIN6_LDSK1
-#define RO_CHAIN6_LDSK1 128
-#endif
 struct RoSplit {
-#ifndef RO_CHAIN6_REGK1
-#define RO_CHAIN6_REGK1 128  // the 6-joint chain at one slot group: W2 wholly resident (128 + 128 rows)
-#endif
-#ifndef RO_CHAIN6_PF
-#define RO_CHAIN6_PF 0
-#endif
   static constexpr int REGK = NJ <= 2 ? 192 : NJ == 3 ? (NG == 4 ? 160 : 128) : NG == 4 ? 48 : NG == 1 ? RO_CHAIN6_REGK1 : 64;
   static constexpr int LDSK = NJ <= 2 ? 64 : NJ == 3 ? (NG == 4 ? 96 : 128) : NG == 4 ? 80 : NG == 1 ? RO_CHAIN6_LDSK1 : 112;
   static_assert(REGK % 16 == 0 && LDSK % 16 == 0 && REGK + LDSK <= 256, "row split");
@@ -111,12 +147,22 @@ struct RoActorLds {
   float a[RoCfg<NG>::SL * NA];                  // actions [slot][a]
 };
 
-template <int NG, int NS, int NA, int REGK, int LDSK>
-__device__ __forceinline__ void ro_load_actor(const NetView& N, const Lane& L, RoActorRegs<NS, REGK>& R,
-                                              RoActorLds<NG, NA, LDSK>& W) {
+// W3^T [a][f] (and, where the kernel keeps it in LDS, b3 padded to 8) staged by nthreads threads
+template <int NA>
+__device__ __forceinline__ void ro_stage_w3(const NetView& N, int tid, int nthreads, float* w3, float* b3) {
+  const float* W3 = N.flat + N.t.woff[2];
+  for (int e = tid; e < NA * 256; e += nthreads) w3[e] = W3[(e & 255) * NA + (e >> 8)];
+  if (b3 && tid < 8) b3[tid] = tid < NA ? N.bias(2, tid) : 0.f;
+}
+
+// The actor's weights of a 4-wave team: L (the team's wave / lane) picks the feature column held in
+// registers; the LDS copies (w2: rows [REGK, REGK + LDSK), w3, b3) are staged by the nthreads
+// threads tid that share them (one team, or the two teams of k_rollout_tt).
+template <int NS, int NA, int REGK, int LDSK>
+__device__ __forceinline__ void ro_load_actor(const NetView& N, const Lane& L, int tid, int nthreads,
+                                              RoActorRegs<NS, REGK>& R, float4* w2, float* w3, float* b3) {
   const float* W1 = N.flat + N.t.woff[0];
   const float* W2 = N.flat + N.t.woff[1];
-  const float* W3 = N.flat + N.t.woff[2];
   const int f = 64 * L.wave + L.lane;
 #pragma unroll
   for (int k = 0; k < REGK; ++k) R.w2[k] = W2[k * 256 + f];
@@ -124,13 +170,12 @@ __device__ __forceinline__ void ro_load_actor(const NetView& N, const Lane& L, R
   for (int q = 0; q < NS; ++q) R.w1[q] = W1[q * 256 + f];
   R.b1 = N.bias(0, f);
   R.b2 = N.bias(1, f);
-  for (int e = L.tid; e < LDSK * 64; e += CACTO_THREADS) {
+  for (int e = tid; e < LDSK * 64; e += nthreads) {
     const int lane = e & 63, w = (e >> 6) & 3, kq = e >> 8;
     const int k = REGK + 4 * kq, col = 64 * w + lane;
-    W.w2[e] = make_float4(W2[k * 256 + col], W2[(k + 1) * 256 + col], W2[(k + 2) * 256 + col], W2[(k + 3) * 256 + col]);
+    w2[e] = make_float4(W2[k * 256 + col], W2[(k + 1) * 256 + col], W2[(k + 2) * 256 + col], W2[(k + 3) * 256 + col]);
   }
-  for (int e = L.tid; e < NA * 256; e += CACTO_THREADS) W.w3[e] = W3[(e & 255) * NA + (e >> 8)];
-  if (L.tid < 8) W.b3[L.tid] = L.tid < NA ? N.bias(2, L.tid) : 0.f;
+  ro_stage_w3<NA>(N, tid, nthreads, w3, b3);
 }
 
 __device__ __forceinline__ float lrelu(float z) { return z > 0.f ? z : fmul(z, 0.3f); }
@@ -271,15 +316,9 @@ __device__ __forceinline__ void ro_layer2(const RoActorRegs<NS, REGK>& R, WT& W,
 
 // Actor forward of the workgroup's SL slots: x0 -> h1 -> h2 -> a. Contains 3 barriers (the last
 // one publishes W.a).
-struct RoNoDyn {
-  __device__ __forceinline__ void operator()() const {}
-};
-// dyn: work of this wave that needs nothing layer 2 produces, placed after layer 2's code in the
-// same basic block so the scheduler can interleave it with the layer's MFMAs and LDS waits
-template <int NG, int NS, int NA, int REGK, int LDSK, bool PF, bool SPLIT, typename WT, typename Bar,
-          typename Dyn = RoNoDyn>
+template <int NG, int NS, int NA, int REGK, int LDSK, bool PF, bool SPLIT, typename WT, typename Bar>
 __device__ __forceinline__ void ro_actor(const RoActorRegs<NS, REGK>& R, WT& W, const float* __restrict__ W2g,
-                                         const Lane& L, int it, Bar&& bar, Dyn dyn = Dyn{}) {
+                                         const Lane& L, Bar&& bar, RoClock& clk) {
   using C = RoCfg<NG>;
   // ---- layer 1 (K = NS): one activation VGPR per group covers every k
   {
@@ -303,12 +342,11 @@ __device__ __forceinline__ void ro_actor(const RoActorRegs<NS, REGK>& R, WT& W, 
       for (int i = 0; i < 4; ++i) W.h1[(g * 4 + L.wave) * C::H1B + q * 20 + 4 * i + v] = lrelu(fadd(acc[g][i], R.b1));
   }
   bar();
-  RSTAMP(4);
+  clk.mark(RO_L1);
   // ---- layer 2 (K = 256)
   ro_layer2<NG, NS, REGK, LDSK, PF, SPLIT>(R, W, W2g, L);
-  dyn();
   bar();
-  RSTAMP(5);
+  clk.mark(RO_L2);
   // ---- layer 3 (256 -> NA): one summation order for every NG (so the schedule never changes a
   //      result): 64 partial chains, chain j = features j, j + 64, j + 128, j + 192 (FMA in that
   //      order), combined by a butterfly over j with offsets 32, 16, ..., 1. Thread (slot s,
@@ -344,6 +382,7 @@ __device__ __forceinline__ void ro_actor(const RoActorRegs<NS, REGK>& R, WT& W, 
       for (int a = 0; a < NA; ++a) W.a[s * NA + a] = fadd(pa[a][0], W.b3[a]);
   }
   bar();
+  clk.mark(RO_L3);
 }
 
 // Chain dynamics workspace of the rollout, structure of arrays [joint][component][slot] (slot
@@ -490,19 +529,7 @@ __device__ __forceinline__ SV sv_sel(bool p, const SV& a, const SV& b) {
 // not read.
 template <int NJ, int SL>
 __device__ __forceinline__ void ro_chain_nle_lanes(const SysDevice& sd, const double* jt, RoChain<NJ, SL>& C,
-                                                   const double* sS, double* hS, double* dump, int lane,
-                                                   bool stamp = false) {
-#ifdef CACTO_STAMPS
-#define NSTAMP(k)                                                                   \
-  do {                                                                              \
-    __builtin_amdgcn_s_waitcnt(0);                                                  \
-    if (stamp) g_rstamps[k] = __builtin_amdgcn_s_memtime();                         \
-  } while (0)
-#else
-#define NSTAMP(k) \
-  do {            \
-  } while (0)
-#endif
+                                                   const double* sS, double* hS, double* dump, int lane) {
   // lanes per slot: a whole 16-lane DPP row per slot when the slots fit (SL = 4), so the base
   // joint's lane takes (0, a_g) as the shift's out-of-row value instead of a select per round
   constexpr int LPS = SL * 16 <= 64 ? 16 : 8;
@@ -520,7 +547,6 @@ __device__ __forceinline__ void ro_chain_nle_lanes(const SysDevice& sd, const do
   const SV zero{v3(0, 0, 0), v3(0, 0, 0)};
   const SV gacc{v3(-sd.p.gravity[0], -sd.p.gravity[1], -sd.p.gravity[2]), v3(0, 0, 0)};
   SV vp = zero, ap = gacc, vi, ai;
-  NSTAMP(17);
 #pragma unroll
   for (int r = 0; r < NJ; ++r) {
     vi = act_motion_inv(X, vp);
@@ -540,7 +566,6 @@ __device__ __forceinline__ void ro_chain_nle_lanes(const SysDevice& sd, const do
       }
     }
   }
-  NSTAMP(18);
   const SV Iv = inertia_mul(I, vi);
   const SV Ia = inertia_mul(I, ai);
   const SV vf = cross_force(vi, Iv);
@@ -548,7 +573,6 @@ __device__ __forceinline__ void ro_chain_nle_lanes(const SysDevice& sd, const do
   f.l = Ia.l + vf.l;
   f.a = Ia.a + vf.a;
   SV fc = f;
-  NSTAMP(19);
 #pragma unroll
   for (int r = 0; r < NJ - 1; ++r) {
     const SV fp = dpp_sv<DPP_SHL1>(act_force(X, fc));
@@ -561,7 +585,6 @@ __device__ __forceinline__ void ro_chain_nle_lanes(const SysDevice& sd, const do
   // every lane stores (no exec-mask branch in the block): lanes without a value write their dump slot
   const bool own = cr < SL && jr < NJ;
   *(own ? hS + j * SL + c : dump + lane) = h;
-#undef NSTAMP
 }
 
 template <int CTRL>
@@ -761,15 +784,123 @@ struct RoX0Lane {
   }
 };
 
-// Slot refill (wave 0; every lane calls it, lanes with `need` take the next queue entries in lane
-// order). A new episode's s_0 goes to the slot's state and the actor input; episodes of length 0
-// are completed on the spot (status 0: RL.py never rolls out NSTEPS_SH == 0).
+// ---------------------------------------------------------------- the slot lifecycle
+// An episode slot runs: take the next queue entry -> [actor, s' = f(s, a), end of step] per step ->
+// take the next entry. The three kernels share the pieces below and differ only in who runs them:
+// a slot is one lane of wave 0 (k_rollout, k_rollout_tt: RoLaneStores, queue positions by ballot)
+// or a whole wave (k_rollout_ks: RoWaveStores, queue positions from an LDS counter).
+
+// The launch's episode arrays and this (virtual) workgroup's place vb of G in the deal.
+struct RoQueue {
+  const double* S0;
+  const int32_t *nsteps, *order;
+  int T, B, G, vb;
+  double* Straj;
+  float* Atraj;
+  int32_t* status;
+};
+
+// Queue position k of (virtual) workgroup vb -> rank of the length-sorted order: the ranks are dealt
+// to the G workgroups in snake order, so every workgroup gets long and short episodes alike.
+__device__ __forceinline__ int ro_deal(int k, int G, int vb) { return k * G + ((k & 1) ? G - 1 - vb : vb); }
+
+// x[lane] for lanes < N (x uniform across the wave) as a select chain kept in VGPRs: without the
+// empty asm the optimiser turns the chain into an indexed load from a scratch copy of x.
+template <int N, typename V>
+__device__ __forceinline__ V lane_pick(const V* x, int lane) {
+  V v = x[0];
+#pragma unroll
+  for (int i = 1; i < N; ++i) {
+    v = lane == i ? x[i] : v;
+    __asm__ volatile("" : "+v"(v));
+  }
+  return v;
+}
+
+// Who stores an episode's rows. Lane per slot: the lane owns the episode and writes whole rows.
+struct RoLaneStores {
+  __device__ __forceinline__ int uniform(int v) const { return v; }
+  template <int N, typename V>
+  __device__ __forceinline__ void row(V* dst, const V* x) const {
+#pragma unroll
+    for (int i = 0; i < N; ++i) dst[i] = x[i];
+  }
+  template <int N>
+  __device__ __forceinline__ void nan_rows(double* dst, int rows) const {
+    for (int r = 0; r < rows; ++r)
+#pragma unroll
+      for (int i = 0; i < N; ++i) dst[r * N + i] = __builtin_nan("");
+  }
+  __device__ __forceinline__ void flag(int32_t* dst, int v) const { *dst = v; }
+};
+// Lane per component: the wave owns the episode (its values uniform over the lanes); lane i writes
+// component i of a row, lane 0 the status.
+struct RoWaveStores {
+  int lane;
+  __device__ __forceinline__ int uniform(int v) const { return __builtin_amdgcn_readfirstlane(v); }
+  template <int N, typename V>
+  __device__ __forceinline__ void row(V* dst, const V* x) const {
+    if (lane < N) dst[lane] = lane_pick<N>(x, lane);
+  }
+  template <int N>
+  __device__ __forceinline__ void nan_rows(double* dst, int rows) const {
+    for (int e = lane; e < rows * N; e += 64) dst[e] = __builtin_nan("");
+  }
+  __device__ __forceinline__ void flag(int32_t* dst, int v) const {
+    if (lane == 0) *dst = v;
+  }
+};
+
+// (ro_refill keeps its own copy of this, see there.)
+// Rank r (< B) -> its episode: b, n = min(nsteps, T) and s_0, which is also row 0 of its trajectory.
+// False for an episode of length 0: it is complete here (status 0: RL.py never rolls out
+// NSTEPS_SH == 0) and the caller takes the next entry.
+template <int NS, typename St>
+__device__ __forceinline__ bool ro_take(const RoQueue& Q, int r, const St& st, int& b, int& n, double* s) {
+  b = st.uniform(Q.order ? Q.order[r] : r);
+  n = min(Q.nsteps[b], Q.T);
+#pragma unroll
+  for (int i = 0; i < NS; ++i) s[i] = Q.S0[(size_t)b * NS + i];
+  if (Q.Straj) st.template row<NS>(Q.Straj + (size_t)b * (Q.T + 1) * NS, s);
+  if (n == 0 && Q.status) st.flag(Q.status + b, 0);
+  return n != 0;
+}
+
+// The end of step t of episode b after s' = f(s, a): the stores of (a_t, s_{t+1}) and the verdict.
+// A NaN state drops the episode (RL.py:229-231, status 1): the rest of its trajectory is NaN (the
+// reward / EE pass skips NaN states). True when the episode is over; the caller refills.
+template <int NS, int NA, typename St>
+__device__ __forceinline__ bool ro_end_step(const RoQueue& Q, const St& st, int b, int t, int n, const float* a,
+                                            const double* sn) {
+  bool bad = false;
+#pragma unroll
+  for (int i = 0; i < NS; ++i) bad |= isnan(sn[i]);
+  if (Q.Atraj) st.template row<NA>(Q.Atraj + ((size_t)b * Q.T + t) * NA, a);
+  if (Q.Straj) st.template row<NS>(Q.Straj + ((size_t)b * (Q.T + 1) + t + 1) * NS, sn);
+  if (bad && Q.Straj) st.template nan_rows<NS>(Q.Straj + ((size_t)b * (Q.T + 1) + t + 2) * NS, n - t - 1);
+  const bool fin = bad || t + 1 >= n;
+  if (fin && Q.status) st.flag(Q.status + b, bad ? 1 : 0);
+  return fin;
+}
+
+// The prismatic chain's constant Cholesky factor and bias forces from the system table
+// (k_const_dyn_init: the same chain_terms -> cholesky const_dyn_init runs per episode).
+template <int NJ>
+__device__ __forceinline__ void ro_const_dyn_table(const SysDevice& sd, ConstDyn<NJ>& cd) {
+  if constexpr (NJ > 0) {
+#pragma unroll
+    for (int k = 0; k < NJ * NJ; ++k) cd.L[k] = sd.cd_L[k];
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) cd.h[i] = sd.cd_h[i];
+  }
+}
+
+// Slot refill, lane per slot (wave 0; every lane calls it, lanes with `need` take the next queue
+// entries in lane order: positions by ballot and popcount). A new episode's s_0 goes to the slot's
+// state and the actor input. INIT_CD: a prismatic chain's M is factored here, once per episode.
 template <int NJ, int NG, typename ShT, bool INIT_CD = true>
-__device__ __forceinline__ void ro_refill(bool need, int c, int& head, ShT& Sh, const SysDevice& sd,
-                                          const double* __restrict__ S0,
-                                          const int32_t* __restrict__ nsteps, const int32_t* __restrict__ order, int T,
-                                          int B, int G, double* __restrict__ Straj, int32_t* __restrict__ status,
-                                          const RoNorm<Dims<NJ>::NS>& nrm, const Lane& L, int vb) {
+__device__ __forceinline__ void ro_refill(bool need, int c, int& head, ShT& Sh, const SysDevice& sd, const RoQueue& Q,
+                                          const RoNorm<Dims<NJ>::NS>& nrm, const Lane& L) {
   constexpr int ns = Dims<NJ>::NS, SL = RoCfg<NG>::SL;
   const cacto_sys_params& p = sd.p;
   while (true) {
@@ -779,21 +910,24 @@ __device__ __forceinline__ void ro_refill(bool need, int c, int& head, ShT& Sh, 
     const int k = head + rank;
     head += __popcll(m);
     if (need) {
-      const int r = k * G + ((k & 1) ? G - 1 - vb : vb);
-      if (r >= B) {
+      const int r = ro_deal(k, Q.G, Q.vb);
+      if (r >= Q.B) {
         need = false;
         Sh.sact[c] = 0;
       } else {
-        const int b = order ? order[r] : r;
-        const int n = min(nsteps[b], T);
+        // ro_take's work in this kernel family's own order (each component of s_0 stored as it is
+        // loaded): with ro_take called here the UR5 route (k_rollout<6, 1>, 2048 episodes) measured
+        // 0.826-0.832 ms against 0.778-0.785 ms; k_rollout_ks calls ro_take
+        const int b = Q.order ? Q.order[r] : r;
+        const int n = min(Q.nsteps[b], Q.T);
         double s[ns];
 #pragma unroll
         for (int i = 0; i < ns; ++i) {
-          s[i] = S0[(size_t)b * ns + i];
-          if (Straj) Straj[(size_t)b * (T + 1) * ns + i] = s[i];
+          s[i] = Q.S0[(size_t)b * ns + i];
+          if (Q.Straj) Q.Straj[(size_t)b * (Q.T + 1) * ns + i] = s[i];
         }
         if (n == 0) {
-          if (status) status[b] = 0;
+          if (Q.status) Q.status[b] = 0;
         } else {
           need = false;
           Sh.sb[c] = b;
@@ -821,18 +955,20 @@ __device__ __forceinline__ void ro_refill(bool need, int c, int& head, ShT& Sh, 
   }
 }
 
-// A slot's state as wave 0's lane c keeps it in registers: active flag, episode, step, s_t and, for
-// prismatic chains, the episode's Cholesky factor and bias forces (loaded from the slot's LDS copy
-// after the lane (re)fills it).
-template <int NJ, int NG>
+// An episode slot's state in the registers of whoever runs it (lane c of wave 0, or the wave of
+// k_rollout_ks): active flag, episode, step, length, s_t and, for prismatic chains, the Cholesky
+// factor and bias forces of M. Lane-per-slot kernels keep a copy in LDS (the lane is its only
+// writer) and load() it after the lane (re)fills the slot.
+template <int NJ>
 struct RoSlotRegs {
-  static constexpr int ns = Dims<NJ>::NS, SL = RoCfg<NG>::SL;
+  static constexpr int ns = Dims<NJ>::NS;
   bool act = false;
   int b = 0, t = 0, n = 0;
   double s[ns];
   ConstDyn<NJ> cd;
   template <typename ShT>
   __device__ __forceinline__ void load(const ShT& Sh, int c, bool cdyn) {
+    constexpr int SL = ShT::SL;
     if (c >= SL) return;
     act = Sh.sact[c] != 0;
     b = Sh.sb[c];
@@ -851,34 +987,60 @@ struct RoSlotRegs {
   }
 };
 
-// Wave 0, lane c (< SL): after s' = f(s, a) of slot c (already in the slot's LDS state): the
-// trajectory stores of (a_t, s_{t+1}) and the end of the episode (status; the caller refills).
-template <int NJ, int NG>
-__device__ __forceinline__ bool ro_advance(int c, int b, int tc, const double* sn, const float* a,
-                                           const SysDevice& sd, int T,
-                                           double* __restrict__ Straj, float* __restrict__ Atraj,
-                                           int32_t* __restrict__ status, const RoNorm<Dims<NJ>::NS>& nrm, int n) {
-  constexpr int ns = Dims<NJ>::NS, na = Dims<NJ>::NA;
-  const cacto_sys_params& p = sd.p;
-  bool bad = false;
+// The per-step tail of a lane-per-slot kernel (wave 0, every lane; lane c < SL <-> slot c), after
+// the actor's last barrier: the slot's action from LDS, s' = step(sr, a) — the kernel's dynamics —
+// into the slot's LDS state and registers, the end of the step, finished slots refilled and their
+// registers reloaded, the next actor input and the any-slot-active flag.
+// The next actor input is formed from s_{t+1}: the slots' lanes wrote sS, and LDS operations of one
+// wave complete in order, so after the wave-scope fence every lane reads them. EARLY: written
+// before the trajectory stores and the bookkeeping, which then overlap its latency; a slot that
+// ends and is refilled gets its new s_0 row from ro_refill afterwards (same wave, later in program
+// order). Measured per system (r03): UR5 +2.7 %, manipulator neutral, car_park -4.5 %, DI neutral,
+// so only the revolute chains take it.
+template <int NJ, int NG, bool EARLY, bool INIT_CD, typename ShT, typename Step>
+__device__ __forceinline__ void ro_wave0_tail(ShT& Sh, RoSlotRegs<NJ>& sr, int c, int& head, bool cdyn, int use_actor,
+                                              const SysDevice& sd, const RoQueue& Q,
+                                              const RoNorm<Dims<NJ>::NS>& nrm,
+                                              const RoX0Lane<Dims<NJ>::NS, ShT::SL>& x0l, const Lane& L, RoClock& clk,
+                                              Step&& step) {
+  constexpr int ns = Dims<NJ>::NS, na = Dims<NJ>::NA, SL = ShT::SL;
+  const bool active = L.lane < SL && sr.act;
+  bool fin = false;
+  float a[na];
+  if (active) {
+    double ad[na], sn[ns];
 #pragma unroll
-  for (int i = 0; i < ns; ++i) bad |= isnan(sn[i]);
-  if (Atraj)
+    for (int i = 0; i < na; ++i) {
+      a[i] = use_actor ? Sh.W.a[c * na + i] : 0.f;
+      ad[i] = (double)a[i];
+    }
+    step(sr, ad, sn);
 #pragma unroll
-    for (int i = 0; i < na; ++i) Atraj[((size_t)b * T + tc) * na + i] = a[i];
-  if (Straj)
-#pragma unroll
-    for (int i = 0; i < ns; ++i) Straj[((size_t)b * (T + 1) + tc + 1) * ns + i] = sn[i];
-  if (bad && Straj) {
-    // RL.py:229-231 drops the episode; the rest of its trajectory is NaN (the reward / EE pass
-    // skips NaN states)
-    for (int t = tc + 2; t <= n; ++t)
-#pragma unroll
-      for (int i = 0; i < ns; ++i) Straj[((size_t)b * (T + 1) + t) * ns + i] = __builtin_nan("");
+    for (int i = 0; i < ns; ++i) {
+      Sh.sS[c * ns + i] = sn[i];
+      sr.s[i] = sn[i];
+    }
   }
-  const bool fin = bad || tc + 1 >= n;
-  if (fin && status) status[b] = bad ? 1 : 0;
-  return fin;
+  if constexpr (EARLY) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    x0l.write(Sh, nrm, L.lane);
+  }
+  clk.mark(RO_STEP);
+  if (active) {
+    fin = ro_end_step<ns, na>(Q, RoLaneStores{}, sr.b, sr.t, sr.n, a, sr.s);
+    sr.t += 1;
+  }
+  clk.mark(RO_STORE);
+  ro_refill<NJ, NG, ShT, INIT_CD>(fin, c, head, Sh, sd, Q, nrm, L);
+  if (fin) sr.load(Sh, c, cdyn);  // the slot's next episode (or none), written by this lane
+  clk.mark(RO_REFILL);
+  if constexpr (!EARLY) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    x0l.write(Sh, nrm, L.lane);
+  }
+  const uint64_t m = __ballot(L.lane < SL && Sh.sact[c]);
+  if (L.lane == 0) Sh.anyact = m != 0;
+  clk.mark(RO_X0);
 }
 
 // Env.simulate of the rollout (float64 state and action, f32in = false) with the system scalars it
@@ -955,7 +1117,7 @@ __global__ void __launch_bounds__(CACTO_THREADS, 1)
   const bool split_dyn = NJ > 0 && !(RoConstDyn<NJ>::ok && p.const_dyn) && !planar;
   constexpr int REGK = RoSplit<NJ, NG>::REGK, LDSK = RoSplit<NJ, NG>::LDSK;
   RoActorRegs<ns, REGK> R;
-  if (use_actor) ro_load_actor<NG, ns, na, REGK, LDSK>(N, L, R, Sh.W);
+  if (use_actor) ro_load_actor<ns, na, REGK, LDSK>(N, L, L.tid, CACTO_THREADS, R, Sh.W.w2, Sh.W.w3, Sh.W.b3);
   const float* W2g = N.flat + N.t.woff[1];
   for (int e = L.tid; e < NG * 64; e += CACTO_THREADS) Sh.W.x0[e] = 0.f;
   // slot states too: a slot that is never filled still feeds its (unused) actor input row, which
@@ -968,9 +1130,9 @@ __global__ void __launch_bounds__(CACTO_THREADS, 1)
   int head = 0;  // queue position (wave 0, uniform)
   const RoNorm<ns> nrm(p);
   const RoSimScalars ks{p.dt, p.L_delta, p.tau_delta};
+  const RoQueue Q{S0, nsteps, order, T, B, G, (int)blockIdx.x, Straj, Atraj, status};
   if (L.wave == 0) {
-    ro_refill<NJ, NG>(L.lane < SL, L.lane, head, Sh, sd, S0, nsteps, order, T, B, G, Straj, status, nrm, L,
-                      (int)blockIdx.x);
+    ro_refill<NJ, NG>(L.lane < SL, L.lane, head, Sh, sd, Q, nrm, L);
     const uint64_t m = __ballot(L.lane < SL && Sh.sact[L.lane]);
     if (L.lane == 0) Sh.anyact = m != 0;
   }
@@ -978,13 +1140,33 @@ __global__ void __launch_bounds__(CACTO_THREADS, 1)
   const int c = L.lane % SL;  // slot of this lane
   const RoX0Lane<ns, SL> x0l(nrm, L.lane);
   // wave 0, lane c < SL: its slot's state in registers for the whole launch (the lane is the only
-  // writer of the slot's LDS copy: ro_advance and ro_refill run on it), so the dynamics phase waits
-  // only for the action, not for LDS reads of s_t and the episode's factored mass matrix
+  // writer of the slot's LDS copy: ro_wave0_tail runs on it), so the dynamics phase waits only for
+  // the action, not for LDS reads of s_t and the episode's factored mass matrix
   const bool cdyn = RoConstDyn<NJ>::ok && !split_dyn && NJ > 0;
-  RoSlotRegs<NJ, NG> sr;
+  RoSlotRegs<NJ> sr;
   if (L.wave == 0) sr.load(Sh, c, cdyn);
-  for (int it = 0; Sh.anyact; ++it) {
-    RSTAMP(0);
+  RoClock clk;
+  // s' = f(s, a) of the lane's slot: chains with configuration-dependent M from this step's M and h
+  // (LDS), the planar 3R chain in closed form, every other system from the slot's registers alone
+  auto step = [&](const RoSlotRegs<NJ>& r, const double* ad, double* sn) {
+    if constexpr (NJ > 0) {
+      if (split_dyn) {
+        double M[NJ * NJ], h[NJ];
+#pragma unroll
+        for (int k = 0; k < NJ * NJ; ++k) M[k] = Sh.MS[k * SL + c];
+#pragma unroll
+        for (int i = 0; i < NJ; ++i) h[i] = Sh.hS[i * SL + c];
+        chain_step<NJ>(sd, r.s, ad, M, h, sn);
+      } else if (NJ == 3 && planar) {
+        planar3_step(Planar3(sd.pl), ks.dt, r.s, ad, sn);
+      } else {
+        ro_simulate<NJ>(ks, r.cd, r.s, ad, sn);
+      }
+    } else {
+      ro_simulate<NJ>(ks, r.cd, r.s, ad, sn);
+    }
+  };
+  while (Sh.anyact) {
     // joint placements of s_t (published by the actor's first barrier)
     if constexpr (NJ > 0) {
       if (split_dyn) {
@@ -992,128 +1174,34 @@ __global__ void __launch_bounds__(CACTO_THREADS, 1)
         if (!use_actor) __syncthreads();
       }
     }
-    // revolute chains on (slot, joint) lanes: M(q) and h(q, v) depend on s_t only, so wave 0's RNEA
-    // and wave 1's CRBA run inside the actor, interleaved with their layer-2 MFMAs
-    constexpr bool LANE_DYN = NJ > 0 && SL * 8 <= 64;
     constexpr bool APF = NJ <= 2 || (NJ > 3 && NG == 1 && RO_CHAIN6_PF);
-    // (one slot group: at two the 8-lane layout's registers beside layer 2 would spill)
-    const bool dyn_in_actor = LANE_DYN && SL * 16 <= 64 && split_dyn && use_actor && RO_DYN_IN_ACTOR;
-    auto abar = [] { __syncthreads(); };
-    if (use_actor) {
-      if constexpr (LANE_DYN && SL * 16 <= 64) {
-        if (dyn_in_actor) {
-          if (L.wave == 0)
-            ro_actor<NG, ns, na, REGK, LDSK, APF, (NJ <= 3)>(R, Sh.W, W2g, L, it, abar, [&] {
-              ro_chain_nle_lanes<NJ, SL>(sd, Sh.jt, Sh.ch, Sh.sS, Sh.hS, Sh.dump, L.lane);
-            });
-          else if (L.wave == 1)
-            ro_actor<NG, ns, na, REGK, LDSK, APF, (NJ <= 3)>(R, Sh.W, W2g, L, it, abar, [&] {
-              ro_chain_mass_lanes<NJ, SL>(Sh.jt, Sh.ch, Sh.MS, Sh.dump, L.lane);
-            });
-          else
-            ro_actor<NG, ns, na, REGK, LDSK, APF, (NJ <= 3)>(R, Sh.W, W2g, L, it, abar);
-        } else {
-          ro_actor<NG, ns, na, REGK, LDSK, APF, (NJ <= 3)>(R, Sh.W, W2g, L, it, abar);
-        }
-      } else {
-        ro_actor<NG, ns, na, REGK, LDSK, APF, (NJ <= 3)>(R, Sh.W, W2g, L, it, abar);
-      }
-    }
-    RSTAMP(1);
-    const bool active = L.lane < SL && (L.wave == 0 ? sr.act : Sh.sact[c] != 0);
-    if (split_dyn && !dyn_in_actor) {
+    if (use_actor) ro_actor<NG, ns, na, REGK, LDSK, APF, (NJ <= 3)>(R, Sh.W, W2g, L, [] { __syncthreads(); }, clk);
+    // revolute chains: M(q) and h(q, v) of s_t, RNEA on wave 0 beside the CRBA on waves 1-3 (by
+    // (slot, joint) lanes where 8 lanes per slot fit a wave)
+    if (split_dyn) {
       if constexpr (NJ > 0) {
+        const bool active = L.lane < SL && (L.wave == 0 ? sr.act : Sh.sact[c] != 0);
         if (L.wave == 0) {
           if constexpr (SL * 8 <= 64)
-            ro_chain_nle_lanes<NJ, SL>(sd, Sh.jt, Sh.ch, Sh.sS, Sh.hS, Sh.dump, L.lane
-#ifdef CACTO_STAMPS
-                                       , blockIdx.x == 0 && L.lane == 0 && it == 20
-#endif
-            );
+            ro_chain_nle_lanes<NJ, SL>(sd, Sh.jt, Sh.ch, Sh.sS, Sh.hS, Sh.dump, L.lane);
           else if (active)
             ro_chain_nle<NJ, SL>(sd, Sh.ch, c, Sh.sS + c * ns, Sh.sS + c * ns + NJ, Sh.hS + c);
-          RSTAMP(9);
         } else if constexpr (SL * 8 <= 64) {
-          if (L.wave == 1) {
-            ro_chain_mass_lanes<NJ, SL>(Sh.jt, Sh.ch, Sh.MS, Sh.dump, L.lane);
-#ifdef CACTO_STAMPS
-            if (blockIdx.x == 0 && L.lane == 0 && it == 20) g_rstamps[10] = __builtin_amdgcn_s_memtime();
-#endif
-          }
+          if (L.wave == 1) ro_chain_mass_lanes<NJ, SL>(Sh.jt, Sh.ch, Sh.MS, Sh.dump, L.lane);
         } else if (active) {
           ro_chain_mass_cols<NJ, SL>(sd, Sh.ch, c, Sh.MS + c, RoMassCols<NJ>::lo(L.wave), RoMassCols<NJ>::hi(L.wave));
-#ifdef CACTO_STAMPS
-          if (blockIdx.x == 0 && L.lane == 0 && it == 20) g_rstamps[9 + L.wave] = __builtin_amdgcn_s_memtime();
-#endif
         }
       }
       __syncthreads();
+      clk.mark(RO_DYN);
     }
-    RSTAMP(2);
-    if (L.wave == 0) {
-      bool fin = false;
-      float a[na];
-      if (active) {
-        double ad[na], sn[ns];
-        const double* s = sr.s;
-#pragma unroll
-        for (int i = 0; i < na; ++i) {
-          a[i] = use_actor ? Sh.W.a[c * na + i] : 0.f;
-          ad[i] = (double)a[i];
-        }
-        if constexpr (NJ > 0) {
-          if (split_dyn) {
-            double M[NJ * NJ], h[NJ];
-#pragma unroll
-            for (int k = 0; k < NJ * NJ; ++k) M[k] = Sh.MS[k * SL + c];
-#pragma unroll
-            for (int i = 0; i < NJ; ++i) h[i] = Sh.hS[i * SL + c];
-            chain_step<NJ>(sd, s, ad, M, h, sn);
-          } else if (NJ == 3 && planar) {
-            planar3_step(Planar3(sd.pl), ks.dt, s, ad, sn);
-          } else {
-            ro_simulate<NJ>(ks, sr.cd, s, ad, sn);
-          }
-        } else {
-          ro_simulate<NJ>(ks, sr.cd, s, ad, sn);
-        }
-        RSTAMP(6);
-#pragma unroll
-        for (int i = 0; i < ns; ++i) {
-          Sh.sS[c * ns + i] = sn[i];
-          sr.s[i] = sn[i];
-        }
-      }
-      // The next actor input from s_{t+1}: the slots' lanes wrote sS above, and LDS operations of
-      // one wave complete in order, so after the wave-scope fence every lane reads them. EARLY
-      // (revolute chains): written before the trajectory stores and the bookkeeping, which then
-      // overlap its latency; a slot that ends and is refilled gets its new s_0 row from ro_refill
-      // afterwards (same wave, later in program order). Measured per system (r03): UR5 +2.7 %,
-      // manipulator neutral, car_park -4.5 %, DI neutral — the others write it last.
-      constexpr bool EARLY = NJ >= 3;
-      if constexpr (EARLY) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        x0l.write(Sh, nrm, L.lane);
-      }
-      RSTAMP(16);
-      if (active) {
-        fin = ro_advance<NJ, NG>(c, sr.b, sr.t, sr.s, a, sd, T, Straj, Atraj, status, nrm, sr.n);
-        sr.t += 1;
-        RSTAMP(7);
-      }
-      ro_refill<NJ, NG>(fin, c, head, Sh, sd, S0, nsteps, order, T, B, G, Straj, status, nrm, L, (int)blockIdx.x);
-      if (fin) sr.load(Sh, c, cdyn);  // the slot's next episode (or none), written by this lane
-      if constexpr (!EARLY) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        x0l.write(Sh, nrm, L.lane);
-      }
-      const uint64_t m = __ballot(L.lane < SL && Sh.sact[c]);
-      if (L.lane == 0) Sh.anyact = m != 0;
-      RSTAMP(8);
-    }
+    if (L.wave == 0)
+      ro_wave0_tail<NJ, NG, (NJ >= 3), true>(Sh, sr, c, head, cdyn, use_actor, sd, Q, nrm, x0l, L, clk, step);
     __syncthreads();
-    RSTAMP(3);
+    clk.mark(RO_BAR);
+    clk.step_done();
   }
+  clk.save();
 }
 
 // ---------------------------------------------------------------- two teams per workgroup
@@ -1173,9 +1261,6 @@ struct RoTeamView {
 
 // Barrier of the 4 waves of a team: each wave's lane 0 adds one arrival (release: the wave's LDS
 // writes are complete), the wave then waits for 4 arrivals per barrier so far (acquire).
-#ifndef RO_TBAR_SLEEP
-#define RO_TBAR_SLEEP 1  // s_sleep between polls of a team barrier
-#endif
 struct RoTeamBar {
   int* ctr;
   int target;
@@ -1206,51 +1291,24 @@ __global__ void __launch_bounds__(2 * CACTO_THREADS, 1)
   L.tid = L.wave * 64 + L.lane;
   RoTeamShared<NJ>& S = Sh.team[team];
   RoActorRegs<ns, REGK> R;
-  if (use_actor) {
-    const float* W1 = N.flat + N.t.woff[0];
-    const float* W2 = N.flat + N.t.woff[1];
-    const float* W3 = N.flat + N.t.woff[2];
-    const int f = 64 * L.wave + L.lane;
-#pragma unroll
-    for (int k = 0; k < REGK; ++k) R.w2[k] = W2[k * 256 + f];
-#pragma unroll
-    for (int q = 0; q < ns; ++q) R.w1[q] = W1[q * 256 + f];
-    R.b1 = N.bias(0, f);
-    R.b2 = N.bias(1, f);
-    for (int e = threadIdx.x; e < LDSK * 64; e += 2 * CACTO_THREADS) {
-      const int lane = e & 63, w = (e >> 6) & 3, kq = e >> 8;
-      const int k = REGK + 4 * kq, col = 64 * w + lane;
-      Sh.w2[e] = make_float4(W2[k * 256 + col], W2[(k + 1) * 256 + col], W2[(k + 2) * 256 + col],
-                             W2[(k + 3) * 256 + col]);
-    }
-    for (int e = threadIdx.x; e < na * 256; e += 2 * CACTO_THREADS) Sh.w3[e] = W3[(e & 255) * na + (e >> 8)];
-    if (threadIdx.x < 8) Sh.b3[threadIdx.x] = threadIdx.x < na ? N.bias(2, threadIdx.x) : 0.f;
-  }
+  if (use_actor) ro_load_actor<ns, na, REGK, LDSK>(N, L, threadIdx.x, 2 * CACTO_THREADS, R, Sh.w2, Sh.w3, Sh.b3);
   if (L.tid < 64) S.W.x0[L.tid] = 0.f;
   for (int e = L.tid; e < SL * ns; e += CACTO_THREADS) S.sS[e] = 0.0;
   if (L.tid < SL) S.sact[L.tid] = 0;
   if (L.tid == 0) S.bar = 0;
   __syncthreads();  // the only workgroup barrier: weights and team state in place
   RoTeamBar tbar{&S.bar, 0, L.lane};
-  const int vb = 2 * (int)blockIdx.x + team, G = 2 * (int)gridDim.x;
+  const RoQueue Q{S0, nsteps, order, T, B, 2 * (int)gridDim.x, 2 * (int)blockIdx.x + team, Straj, Atraj, status};
   int head = 0;
   const RoNorm<ns> nrm(p);
   const RoSimScalars ks{p.dt, p.L_delta, p.tau_delta};
   const int c = L.lane % SL;
   // prismatic chains (the host runs this kernel for const_dyn chains only): M's Cholesky factor
-  // and h do not depend on (q, v) — the values k_const_dyn_init tabled in SysDevice, computed by
-  // the same chain_terms -> cholesky the single-team kernel runs per episode
-  ConstDyn<NJ> cd;
-  if constexpr (NJ > 0) {
-#pragma unroll
-    for (int k = 0; k < NJ * NJ; ++k) cd.L[k] = sd.cd_L[k];
-#pragma unroll
-    for (int i = 0; i < NJ; ++i) cd.h[i] = sd.cd_h[i];
-  }
-  RoSlotRegs<NJ, NG> sr;
+  // and h do not depend on (q, v), so the slot record keeps the system table's for the whole launch
+  RoSlotRegs<NJ> sr;
+  ro_const_dyn_table<NJ>(sd, sr.cd);
   if (L.wave == 0) {
-    ro_refill<NJ, NG, RoTeamShared<NJ>, false>(L.lane < SL, L.lane, head, S, sd, S0, nsteps, order, T, B, G, Straj,
-                                                status, nrm, L, vb);
+    ro_refill<NJ, NG, RoTeamShared<NJ>, false>(L.lane < SL, L.lane, head, S, sd, Q, nrm, L);
     const uint64_t m = __ballot(L.lane < SL && S.sact[L.lane]);
     if (L.lane == 0) S.anyact = m != 0;
     sr.load(S, c, false);
@@ -1259,133 +1317,24 @@ __global__ void __launch_bounds__(2 * CACTO_THREADS, 1)
   const RoX0Lane<ns, SL> x0l(nrm, L.lane);
   RoTeamView<na> V{Sh.w2, Sh.w3, Sh.b3, S.W.h1, S.W.h2, S.W.x0, S.W.a};
   const float* W2g = N.flat + N.t.woff[1];
-#ifdef CACTO_STAMPS
-#define TSTAMP(k)                                                                                          \
-  do {                                                                                                     \
-    if (blockIdx.x == 0 && L.wave == 0 && L.lane == 0 && it == 20) g_rstamps[8 * team + k] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
-  // accumulated phase cycles of every step of every team (waves 0 and 1 of the team, lane 0):
-  // [0] layer 1 + its barrier, [1] layer 2 + barrier, [2] layer 3 + barrier, [3] dynamics, stores,
-  // refill (wave 0; the other waves go straight to the barrier), [4] the end-of-step barrier
-  // (wave 0 also splits [3]: [5] action read + s' = f(s, a), [6] trajectory stores, [7] refill,
-  // [8] next input + ballot)
-  unsigned long long tacc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0, tsub = 0;
-  int tbi = 0;
-  auto tmark = [&](int ph) {
-    const unsigned long long now = __builtin_amdgcn_s_memtime();
-    if (ph == 1) tacc[0] += now - tprev;
-    if (ph == 2) tacc[1] += now - tprev;
-    if (ph == 3) tacc[2] += now - tprev;
-    if (ph == 4) tacc[3] += now - tprev;
-    if (ph == 5) tacc[4] += now - tprev;
-    tprev = now;
-    tsub = now;
-  };
-  auto tsubmark = [&](int k) {
-    const unsigned long long now = __builtin_amdgcn_s_memtime();
-    if (k == 5) tacc[5] += now - tsub;
-    if (k == 6) tacc[6] += now - tsub;
-    if (k == 7) tacc[7] += now - tsub;
-    if (k == 8) tacc[8] += now - tsub;
-    tsub = now;
-  };
-#define TSUB(k) tsubmark(k)
-  auto sbar = [&] {
-    tbar();
-    tmark(++tbi);
-  };
-  int tsteps = 0;
-#else
-#define TSTAMP(k) \
-  do {            \
-  } while (0)
-#define TSUB(k) \
-  do {          \
-  } while (0)
-#endif
-  for (int it = 0; S.anyact; ++it) {
-    TSTAMP(0);
+  RoClock clk;
+  auto step = [&](const RoSlotRegs<NJ>& r, const double* ad, double* sn) { ro_simulate<NJ>(ks, r.cd, r.s, ad, sn); };
+  while (S.anyact) {
     // Every wave must have read S.anyact (the loop test) before wave 0 rewrites it below. With the
     // actor, its first team barrier orders that; without it (ep == 0, zero controls) this barrier
     // does: a counter barrier, unlike s_barrier, would wait forever for waves that left the loop on
     // an anyact they read too late.
     if (!use_actor) tbar();
-#ifdef CACTO_STAMPS
-    tbi = 0;
-    tmark(0);
-    if (use_actor) ro_actor<NG, ns, na, REGK, LDSK, true, true>(R, V, W2g, L, it, sbar);
-#else
-    if (use_actor) ro_actor<NG, ns, na, REGK, LDSK, true, true>(R, V, W2g, L, it, tbar);
-#endif
-    TSTAMP(1);
-    if (L.wave == 0) {
-      const bool active = L.lane < SL && sr.act;
-      bool fin = false;
-      float a[na];
-      if (active) {
-        double ad[na], sn[ns];
-#pragma unroll
-        for (int i = 0; i < na; ++i) {
-          a[i] = use_actor ? S.W.a[c * na + i] : 0.f;
-          ad[i] = (double)a[i];
-        }
-        ro_simulate<NJ>(ks, cd, sr.s, ad, sn);
-#pragma unroll
-        for (int i = 0; i < ns; ++i) {
-          S.sS[c * ns + i] = sn[i];
-          sr.s[i] = sn[i];
-        }
-      }
-      TSUB(5);
-      if (active) {
-        fin = ro_advance<NJ, NG>(c, sr.b, sr.t, sr.s, a, sd, T, Straj, Atraj, status, nrm, sr.n);
-        sr.t += 1;
-      }
-      TSUB(6);
-      ro_refill<NJ, NG, RoTeamShared<NJ>, false>(fin, c, head, S, sd, S0, nsteps, order, T, B, G, Straj, status, nrm,
-                                                  L, vb);
-      if (fin) sr.load(S, c, false);
-      TSUB(7);
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      x0l.write(S, nrm, L.lane);
-      const uint64_t m = __ballot(L.lane < SL && S.sact[c]);
-      if (L.lane == 0) S.anyact = m != 0;
-      TSUB(8);
-      TSTAMP(2);
-    }
-#ifdef CACTO_STAMPS
-    tmark(4);
-#endif
+    if (use_actor) ro_actor<NG, ns, na, REGK, LDSK, true, true>(R, V, W2g, L, tbar, clk);
+    if (L.wave == 0)
+      ro_wave0_tail<NJ, NG, false, false>(S, sr, c, head, false, use_actor, sd, Q, nrm, x0l, L, clk, step);
     tbar();
-    TSTAMP(3);
-#ifdef CACTO_STAMPS
-    tmark(5);
-    ++tsteps;
-#endif
+    clk.mark(RO_BAR);
+    clk.step_done();
   }
-#ifdef CACTO_STAMPS
-  if (L.lane == 0 && L.wave < 2) {
-    unsigned long long* o = g_ttacc + ((size_t)(blockIdx.x * 2 + team) * 2 + L.wave) * 10;
-    for (int k = 0; k < 9; ++k) o[k] = tacc[k];
-    o[9] = tsteps;
-  }
-#endif
-#undef TSTAMP
-#undef TSUB
+  clk.save();
 }
 
-// x[lane] for lanes < N (x uniform across the wave) as a select chain kept in VGPRs: without the
-// empty asm the optimiser turns the chain into an indexed load from a scratch copy of x.
-template <int N, typename V>
-__device__ __forceinline__ V lane_pick(const V* x, int lane) {
-  V v = x[0];
-#pragma unroll
-  for (int i = 1; i < N; ++i) {
-    v = lane == i ? x[i] : v;
-    __asm__ volatile("" : "+v"(v));
-  }
-  return v;
-}
 
 __device__ __forceinline__ double readlane_d(double v, int l) {
   const long long b = __double_as_longlong(v);
@@ -1462,7 +1411,7 @@ __global__ void __launch_bounds__(8 * CACTO_WAVE, 1)
 #pragma unroll
     for (int a = 0; a < na; ++a) b3[a] = N.bias(2, a);
     if constexpr (LW) {
-      for (int e = threadIdx.x; e < na * 256; e += 8 * CACTO_WAVE) Sh.w3s[e] = W3[(e & 255) * na + (e >> 8)];
+      ro_stage_w3<na>(N, threadIdx.x, 8 * CACTO_WAVE, Sh.w3s, nullptr);
       for (int e = threadIdx.x; e < 256; e += 8 * CACTO_WAVE) Sh.b2s[e] = N.bias(1, e);
       for (int e = threadIdx.x; e < 8 * 64; e += 8 * CACTO_WAVE) {
         const int q = e >> 6, l = e & 63;
@@ -1480,51 +1429,36 @@ __global__ void __launch_bounds__(8 * CACTO_WAVE, 1)
   for (int e = threadIdx.x; e < 2 * 4 * H1B; e += 8 * CACTO_WAVE) Sh.h1[e] = 0.f;
   if (threadIdx.x == 0) Sh.qhead = 0;
   __syncthreads();
-  const int vb = (int)blockIdx.x, G = (int)gridDim.x;
+  const RoQueue Q{S0, nsteps, order, T, B, (int)gridDim.x, (int)blockIdx.x, Straj, Atraj, status};
   const RoNorm<ns> nrm(p);
   float nl = 1.f;
 #pragma unroll
   for (int q = 0; q < ns; ++q) nl = lane == q ? nrm.n[q] : nl;
   const bool tl = lane == ns - 1;
-  // the prismatic chain's constant Cholesky factor and bias forces; the planar 3R chain's link
-  // constants (planar3_step)
-  ConstDyn<NJ> cd;
-  if constexpr (NJ > 0 && NJ != 3) {
-#pragma unroll
-    for (int k = 0; k < NJ * NJ; ++k) cd.L[k] = sd.cd_L[k];
-#pragma unroll
-    for (int i = 0; i < NJ; ++i) cd.h[i] = sd.cd_h[i];
-  }
+  // this wave's slot; a prismatic chain keeps the system table's constant Cholesky factor and bias
+  // forces in it (the planar 3R chain steps from its link constants, planar3_step)
+  RoSlotRegs<NJ> sr;
+  if constexpr (NJ != 3) ro_const_dyn_table<NJ>(sd, sr.cd);
   const RoSimScalars ks{p.dt, p.L_delta, p.tau_delta};
-  bool act = false;
-  int b = 0, n = 0, t = 0;
-  double s[ns];
 #pragma unroll
-  for (int i = 0; i < ns; ++i) s[i] = 0.0;
+  for (int i = 0; i < ns; ++i) sr.s[i] = 0.0;
 
-  // the next queue entries until one has steps (ro_refill's dealing: snake order over the
-  // workgroups; zero-length episodes completed on the spot)
+  // Slot refill, wave per slot (the wave's lanes act as one): the next queue entries, positions
+  // from the workgroup's LDS counter, until one has steps or the queue is empty
   auto refill = [&]() {
-    act = false;
+    sr.act = false;
     while (true) {
       int k = 0;
       if (lane == 0) k = __hip_atomic_fetch_add(&Sh.qhead, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       k = __builtin_amdgcn_readfirstlane(k);
-      const int r = k * G + ((k & 1) ? G - 1 - vb : vb);
-      if (r >= B) return;
-      const int bb = __builtin_amdgcn_readfirstlane(order ? order[r] : r);
-      const int nn = min(nsteps[bb], T);
-#pragma unroll
-      for (int i = 0; i < ns; ++i) s[i] = S0[(size_t)bb * ns + i];
-      if (Straj && lane < ns) Straj[(size_t)bb * (T + 1) * ns + lane] = lane_pick<ns>(s, lane);
-      if (nn == 0) {
-        if (status && lane == 0) status[bb] = 0;
-        continue;
-      }
-      b = bb;
-      n = nn;
-      t = 0;
-      act = true;
+      const int r = ro_deal(k, Q.G, Q.vb);
+      if (r >= Q.B) return;
+      int bb, nn;
+      if (!ro_take<ns>(Q, r, RoWaveStores{lane}, bb, nn, sr.s)) continue;
+      sr.b = bb;
+      sr.n = nn;
+      sr.t = 0;
+      sr.act = true;
       return;
     }
   };
@@ -1532,7 +1466,7 @@ __global__ void __launch_bounds__(8 * CACTO_WAVE, 1)
   // readlane; h1[k] = lrelu(b1[k] + sum_q x0[q] W1[q][k]) for k = lane + 64 m, into the slot's
   // column of the two-group layer-2 operand layout
   auto layer1 = [&]() {
-    const double sv = lane_pick<ns>(s, lane);
+    const double sv = lane_pick<ns>(sr.s, lane);
     const float qv = fdiv((float)sv, nl);
     const float xv = nrm.on ? (tl ? fsub(fmul(qv, 2.0f), 1.0f) : qv) : (float)sv;
     float x0[ns];
@@ -1560,31 +1494,14 @@ __global__ void __launch_bounds__(8 * CACTO_WAVE, 1)
     }
   };
 
-#ifdef CACTO_STAMPS
-  // accumulated phase cycles of every step (lane 0 of each wave): [0] loop test + layer 2 + its
-  // barrier, [1] layer 3, [2] s' = f(s, a) + trajectory stores, [3] refill, [4] layer 1, [5] the
-  // end-of-step barrier
-  unsigned long long wacc[6] = {0, 0, 0, 0, 0, 0}, wprev = __builtin_amdgcn_s_memtime();
-  int wsteps = 0;
-  auto wmark = [&](int ph) {
-    const unsigned long long now = __builtin_amdgcn_s_memtime();
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-      if (k == ph) wacc[k] += now - wprev;
-    wprev = now;
-  };
-#define KMARK(k) wmark(k)
-#else
-#define KMARK(k) \
-  do {           \
-  } while (0)
-#endif
-
+  RoClock clk;
   refill();
-  if (act && use_actor) layer1();
-  if (lane == 0) Sh.act[w] = act;
+  if (sr.act && use_actor) layer1();
+  if (lane == 0) Sh.act[w] = sr.act;
   __syncthreads();
   const int rd = (lane >> 2) * 20 + 4 * (lane & 3);
+  // (the counted form: as `while (true)` the loop is rotated, the flag reads are duplicated and the
+  // car's step measured 4 % slower)
   for (int it = 0;; ++it) {
     int any = 0;
 #pragma unroll
@@ -1622,8 +1539,8 @@ __global__ void __launch_bounds__(8 * CACTO_WAVE, 1)
 #pragma unroll
         for (int i = 0; i < 4; ++i) Sh.P[hk][(4 * gg + i) * 256 + 64 * fq + lane] = fadd(acc[gg][0][i], acc[gg][1][i]);
       __syncthreads();
-      KMARK(0);
-      if (act) {
+      clk.mark(RO_L2);
+      if (sr.act) {
         // layer 3 of slot w on the two halves' sums: h2 = lrelu((lo + hi) + b2), then ro_actor's
         // chains and butterfly (both actions in one permlane butterfly for na == 2)
         float pa[na];
@@ -1674,10 +1591,10 @@ __global__ void __launch_bounds__(8 * CACTO_WAVE, 1)
             a[i] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(fadd(pa[i], b3[i]))));
         }
       }
-      KMARK(1);
+      clk.mark(RO_L3);
     }
     bool fin = false;
-    if (act) {
+    if (sr.act) {
       double ad[na], sn[ns];
 #pragma unroll
       for (int i = 0; i < na; ++i) ad[i] = (double)a[i];
@@ -1685,46 +1602,28 @@ __global__ void __launch_bounds__(8 * CACTO_WAVE, 1)
         // sin / cos of q1 on even lanes and of q2 on odd lanes at once (joint_sincos is the
         // function planar3_step calls, so the bits are the same)
         double sv, cv;
-        joint_sincos((lane & 1) ? s[2] : s[1], &sv, &cv);
-        planar3_step_sc(Planar3(Sh.pls), ks.dt, s, ad, readlane_d(sv, 0), readlane_d(cv, 0), readlane_d(sv, 1),
+        joint_sincos((lane & 1) ? sr.s[2] : sr.s[1], &sv, &cv);
+        planar3_step_sc(Planar3(Sh.pls), ks.dt, sr.s, ad, readlane_d(sv, 0), readlane_d(cv, 0), readlane_d(sv, 1),
                         readlane_d(cv, 1), sn);
       } else
-        ro_simulate<NJ>(ks, cd, s, ad, sn);
-      bool bad = false;
+        ro_simulate<NJ>(ks, sr.cd, sr.s, ad, sn);
+      clk.mark(RO_STEP);
+      fin = ro_end_step<ns, na>(Q, RoWaveStores{lane}, sr.b, sr.t, sr.n, a, sn);
 #pragma unroll
-      for (int i = 0; i < ns; ++i) bad |= isnan(sn[i]);
-      if (Atraj && lane < na) Atraj[((size_t)b * T + t) * na + lane] = lane_pick<na>(a, lane);
-      if (Straj && lane < ns) Straj[((size_t)b * (T + 1) + t + 1) * ns + lane] = lane_pick<ns>(sn, lane);
-      if (bad && Straj) {
-        for (int e = lane; e < (n - t - 1) * ns; e += 64)
-          Straj[((size_t)b * (T + 1) + t + 2) * ns + e] = __builtin_nan("");
-      }
-      fin = bad || t + 1 >= n;
-      if (fin && status && lane == 0) status[b] = bad ? 1 : 0;
-#pragma unroll
-      for (int i = 0; i < ns; ++i) s[i] = sn[i];
-      t += 1;
+      for (int i = 0; i < ns; ++i) sr.s[i] = sn[i];
+      sr.t += 1;
     }
-    KMARK(2);
+    clk.mark(RO_STORE);
     if (fin) refill();
-    KMARK(3);
-    if (act && use_actor) layer1();
-    if (lane == 0) Sh.act[w] = act;
-    KMARK(4);
+    clk.mark(RO_REFILL);
+    if (sr.act && use_actor) layer1();
+    if (lane == 0) Sh.act[w] = sr.act;
+    clk.mark(RO_L1);
     __syncthreads();
-    KMARK(5);
-#ifdef CACTO_STAMPS
-    ++wsteps;
-#endif
+    clk.mark(RO_BAR);
+    clk.step_done();
   }
-#ifdef CACTO_STAMPS
-  if (lane == 0) {
-    unsigned long long* o = g_wsacc + ((size_t)blockIdx.x * 8 + w) * 7;
-    for (int k = 0; k < 6; ++k) o[k] = wacc[k];
-    o[6] = wsteps;
-  }
-#endif
-#undef KMARK
+  clk.save();
 }
 
 // Rewards and end-effector positions of every recorded step (Env.step's reward and
@@ -1902,113 +1801,122 @@ struct LaunchRolloutRewards {
   }
 };
 
+// ---------------------------------------------------------------- the route
+// What cacto_rollout_sched runs for (system, B, groups, workgroups) on a device of `cus` CUs; no
+// launch and no device work in it. "eight" = the systems whose step needs no workgroup-wide
+// dynamics (SI, car, car_park, a prismatic chain: the DI), "planar" = a planar 3-joint chain (the
+// manipulator); per = B / (8 cus), the episodes per slot of an 8-slot workgroup.
+//   groups  system           B                   kernel (kind)                    slots / workgroup
+//   -3      eight or planar  any                 k_rollout_ks (2)                 8
+//   -1      eight            any                 k_rollout_tt (1)                 8
+//   -3, -1  any other        -                   CACTO_EINVAL
+//   1|2|4   any              any                 k_rollout<NJ, groups> (0)        4 groups
+//   0       planar           any                 k_rollout_ks
+//   0       eight            B <= 16 cus         k_rollout_ks
+//   0       prismatic chain  above, per == 2     k_rollout_tt
+//   0       otherwise        any                 k_rollout<NJ, per >= 4 ? 4 : per >= 2 ? 2 : 1>
+//   workgroups: 0 -> min(cus, ceil(B / slots)); always clamped to [1, ceil(B / slots)]
+// Measured at 4096 episodes (ms per rollout, one MI355X): DI k_rollout_tt 0.750 / one slot per wave
+// in two teams (round 4, removed) 0.630 / k_rollout_ks 0.578; SI single-team 0.519 / ks 0.292;
+// car_park single-team 0.432 / ks 0.405 / two teams 0.50; car 1.865 / ks 1.768. UR5 at 2048 episodes:
+// one group with two episodes per slot 1.25, two groups with one 1.28 (tools/ro_sched.py).
+enum RoKind { RO_KIND_TEAM = 0, RO_KIND_TWO_TEAMS = 1, RO_KIND_WAVE_SLOT = 2 };
+struct RoRoute {
+  int kind, groups, workgroups, threads, lds_bytes;
+};
+
+// the schedule arguments of cacto_rollout_sched / cacto_rollout_plan
+#define RO_SCHED_ARGS_MSG                                                                                       \
+  "cacto_rollout_sched: groups must be 0, 1, 2, 4, -1 (two teams) or -3 (one slot per wave, layer 2 split over " \
+  "K), workgroups >= 0"
+inline bool ro_sched_args_ok(int groups, int wgs) {
+  return (groups == 0 || groups == 1 || groups == 2 || groups == 4 || groups == -1 || groups == -3) && wgs >= 0;
+}
+
+template <int NJ>
+int ro_route(const cacto_sys* sys, int B, int groups, int wgs, int cus, RoRoute& r) {
+  constexpr bool tt_ok = NJ <= 2, ks_ok = tt_ok || NJ == 3;
+  const bool eight = tt_ok && (NJ <= 0 || sys->host.p.const_dyn);
+  const bool planar = NJ == 3 && sys->host.pl[0] != 0.0;
+  if ((groups == -1 && !eight) || (groups == -3 && !(eight || planar))) {
+    set_error("cacto_rollout_sched: groups -1 needs a system without configuration-dependent M, -3 such a system "
+              "or a planar 3-joint chain");
+    return CACTO_EINVAL;
+  }
+  const int per = B / (2 * 4 * cus);
+  if (groups == -3 || (groups == 0 && (planar || (eight && B <= 2 * 8 * cus)))) {
+    r = RoRoute{RO_KIND_WAVE_SLOT, 2, 0, 8 * CACTO_WAVE, 0};
+    if constexpr (ks_ok) r.lds_bytes = (int)sizeof(RoKsShared<NJ>);
+  } else if (groups == -1 || (groups == 0 && eight && NJ > 0 && per == 2)) {
+    r = RoRoute{RO_KIND_TWO_TEAMS, 2, 0, 2 * CACTO_THREADS, 0};
+    if constexpr (tt_ok) r.lds_bytes = (int)sizeof(RoTTShared<NJ>);
+  } else {
+    const int g = groups > 0 ? groups : per >= 4 ? 4 : per >= 2 ? 2 : 1;
+    const size_t lds = g == 1 ? sizeof(RoShared<NJ, 1>) : g == 2 ? sizeof(RoShared<NJ, 2>) : sizeof(RoShared<NJ, 4>);
+    r = RoRoute{RO_KIND_TEAM, g, 0, CACTO_THREADS, (int)lds};
+  }
+  r.workgroups = std::max(1, std::min(wgs > 0 ? wgs : cus, ceil_div(B, 4 * r.groups)));
+  return CACTO_OK;
+}
+
 template <int NJ>
 struct LaunchRollout {
   static int run(const cacto_sys* sys, NetView v, const double* S0, const int32_t* n, int T, int use_actor,
                  const double* W, double* S, float* A, double* R, double* EE, int32_t* status, const int32_t* order,
                  int B, int groups, int wgs, hipStream_t st) {
-    const int cus = ro_cus();
-    // two teams of 4 slots per workgroup (k_rollout_tt) for the systems whose step needs no
-    // workgroup-wide dynamics: automatically where the single-team kernel would take 2 groups,
-    // or on request (groups == -1)
-    constexpr bool tt_ok = NJ <= 2 && !(NJ > 0 && !RoConstDyn<NJ>::ok);
-    const bool tt_sys = tt_ok && (NJ <= 0 || sys->host.p.const_dyn);
-    // automatic only where it measured faster: the prismatic chain (DI 0.75 -> 0.72 ms at 4096
-    // episodes); car_park's step was slower on two teams (0.42 -> 0.50 ms)
-    const bool tt_auto = tt_sys && NJ > 0;
-    // planar 3-joint chains (the manipulator): k_rollout_ks with the closed-form planar3_step
-    constexpr bool ks_ok = tt_ok || NJ == 3;
-    const bool planar = NJ == 3 && sys->host.pl[0] != 0.0;
-    const bool ks_sys = tt_sys || planar;
-    if ((groups == -1 && !tt_sys) || (groups == -3 && !ks_sys)) {
-      set_error("cacto_rollout_sched: groups -1 needs a system without configuration-dependent M, -3 such a system "
-                "or a planar 3-joint chain");
-      return CACTO_EINVAL;
-    }
-    // one slot per wave with layer 2 split over K (k_rollout_ks) for every system it can run, up
-    // to two episodes per slot. Measured at 4096 episodes (ms per rollout, one MI355X): DI
-    // k_rollout_tt 0.750 / one slot per wave in two teams (round 4, removed) 0.630 / k_rollout_ks
-    // 0.578; SI single-team 0.519 / ks 0.292; car_park single-team 0.432 / ks 0.405; car 1.865 / 1.768.
-    // The planar chain takes it at every batch size.
-    const bool ks_auto = (tt_sys && B <= 2 * 8 * cus) || planar;
-    if (groups == -3 || (groups == 0 && ks_auto)) {
-      // one slot per wave, layer 2 split over K (k_rollout_ks), one 8-wave workgroup per CU
-      if (wgs <= 0) wgs = std::min(cus, ceil_div(B, 8));
-      wgs = std::max(1, std::min(wgs, ceil_div(B, 8)));
-      if constexpr (ks_ok)
-        hipLaunchKernelGGL(k_rollout_ks<NJ>, dim3(wgs), dim3(8 * CACTO_WAVE), 0, st, sys->dev, v, S0, n, T,
-                           use_actor, S, A, status, order, B);
-      CACTO_CHECK_HIP(hipGetLastError());
-      if (R || EE) return LaunchRolloutRewards<NJ>::run(sys, S, A, n, T, use_actor, W, R, EE, B, st);
-      return CACTO_OK;
-    }
-    if (tt_sys && (groups == -1 || (tt_auto && groups == 0 && B / (2 * 4 * cus) == 2))) {
-      if (wgs <= 0) wgs = std::min(cus, ceil_div(B, 8));
-      wgs = std::max(1, std::min(wgs, ceil_div(B, 8)));
-      if constexpr (tt_ok)
-        hipLaunchKernelGGL(k_rollout_tt<NJ>, dim3(wgs), dim3(2 * CACTO_THREADS), 0, st, sys->dev, v, S0, n, T,
-                           use_actor, S, A, status, order, B);
-      CACTO_CHECK_HIP(hipGetLastError());
-      if (R || EE) return LaunchRolloutRewards<NJ>::run(sys, S, A, n, T, use_actor, W, R, EE, B, st);
-      return CACTO_OK;
-    }
-    // the float64 6-joint chain dynamics need the registers that more slots would take
-    constexpr int gmax = 4;
-    if (groups <= 0) {
-      // about two episodes per slot. (UR5 at 2048 episodes: one group, two episodes per slot,
-      // 1.25 ms against 1.28 ms for two groups with one episode per slot, tools/ro_sched.py.)
-      const int per = B / (2 * 4 * cus);
-      groups = std::min(gmax, per >= 4 ? 4 : per >= 2 ? 2 : 1);
-    }
-    if (groups > gmax) {
-      set_error("cacto_rollout_sched: groups above this system's maximum (1 for 6 joints)");
-      return CACTO_EINVAL;
-    }
-    if (wgs <= 0) wgs = std::min(cus, ceil_div(B, 4 * groups));
-    wgs = std::max(1, std::min(wgs, ceil_div(B, 4 * groups)));
-    switch (groups) {
-      case 1:
-        hipLaunchKernelGGL((k_rollout<NJ, 1>), dim3(wgs), dim3(CACTO_THREADS), 0, st, sys->dev, v, S0, n, T, use_actor,
-                           S, A, status, order, B);
+    RoRoute r;
+    if (const int rc = ro_route<NJ>(sys, B, groups, wgs, ro_cus(), r)) return rc;
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(r.workgroups), dim3(r.threads), 0, st, sys->dev, v, S0, n, T, use_actor, S, A,
+                         status, order, B);
+    };
+    switch (r.kind) {
+      case RO_KIND_WAVE_SLOT:
+        if constexpr (NJ <= 3) launch(k_rollout_ks<NJ>);
         break;
-      case 2:
-        hipLaunchKernelGGL((k_rollout<NJ, (gmax >= 2 ? 2 : 1)>), dim3(wgs), dim3(CACTO_THREADS), 0, st, sys->dev, v, S0,
-                           n, T, use_actor, S, A, status, order, B);
-        break;
-      case 4:
-        hipLaunchKernelGGL((k_rollout<NJ, (gmax >= 4 ? 4 : 1)>), dim3(wgs), dim3(CACTO_THREADS), 0, st, sys->dev, v, S0,
-                           n, T, use_actor, S, A, status, order, B);
+      case RO_KIND_TWO_TEAMS:
+        if constexpr (NJ <= 2) launch(k_rollout_tt<NJ>);
         break;
       default:
-        set_error("cacto_rollout_sched: groups must be 1, 2 or 4");
-        return CACTO_EINVAL;
+        launch(r.groups == 1 ? k_rollout<NJ, 1> : r.groups == 2 ? k_rollout<NJ, 2> : k_rollout<NJ, 4>);
     }
     CACTO_CHECK_HIP(hipGetLastError());
     if (R || EE) return LaunchRolloutRewards<NJ>::run(sys, S, A, n, T, use_actor, W, R, EE, B, st);
     return CACTO_OK;
   }
 };
+
+// cacto_rollout_plan: the route, reported
+template <int NJ>
+struct LaunchRolloutPlan {
+  static int run(const cacto_sys* sys, int B, int groups, int wgs, cacto_ro_plan* out) {
+    const int cus = ro_cus();
+    RoRoute r;
+    if (const int rc = ro_route<NJ>(sys, B, groups, wgs, cus, r)) return rc;
+    *out = cacto_ro_plan{r.kind, r.groups, r.workgroups, r.threads, r.lds_bytes, cus};
+    return CACTO_OK;
+  }
+};
 }  // namespace
 
 #ifdef CACTO_STAMPS
-extern "C" int cacto_debug_rollout_stamps(unsigned long long* out_h) {
+// The phase clock's table [RO_CLOCK_WGS][RO_CLOCK_WAVES][RO_CLOCK_COLS] (see RoClock) as the last
+// rollout kernel left it. One table for the three kernels; the three names remain for the tools.
+static int ro_clock_read(unsigned long long* out_h) {
   CACTO_CHECK_HIP(hipDeviceSynchronize());
-  CACTO_CHECK_HIP(hipMemcpyFromSymbol(out_h, HIP_SYMBOL(g_rstamps), sizeof(unsigned long long) * 20));
+  CACTO_CHECK_HIP(hipMemcpyFromSymbol(out_h, HIP_SYMBOL(g_ro_clock), sizeof(g_ro_clock)));
   return CACTO_OK;
 }
-// k_rollout_ks's accumulated phase cycles: 1024 x 8 x 7 values (see the kernel)
-extern "C" int cacto_debug_rollout_ws_acc(unsigned long long* out_h) {
-  CACTO_CHECK_HIP(hipDeviceSynchronize());
-  CACTO_CHECK_HIP(hipMemcpyFromSymbol(out_h, HIP_SYMBOL(g_wsacc), sizeof(unsigned long long) * 1024 * 8 * 7));
-  return CACTO_OK;
-}
-// k_rollout_tt's accumulated phase cycles: 1024 x 2 x 2 x 10 values (see the kernel)
-extern "C" int cacto_debug_rollout_tt_acc(unsigned long long* out_h) {
-  CACTO_CHECK_HIP(hipDeviceSynchronize());
-  CACTO_CHECK_HIP(hipMemcpyFromSymbol(out_h, HIP_SYMBOL(g_ttacc), sizeof(unsigned long long) * 1024 * 2 * 2 * 10));
-  return CACTO_OK;
-}
+extern "C" int cacto_debug_rollout_stamps(unsigned long long* out_h) { return ro_clock_read(out_h); }
+extern "C" int cacto_debug_rollout_ws_acc(unsigned long long* out_h) { return ro_clock_read(out_h); }
+extern "C" int cacto_debug_rollout_tt_acc(unsigned long long* out_h) { return ro_clock_read(out_h); }
 #endif
+
+extern "C" int cacto_rollout_plan(const cacto_sys* sys, int B, int groups, int workgroups, cacto_ro_plan* out) {
+  CACTO_REQUIRE(sys && out && B >= 0, "cacto_rollout_plan: bad arguments");
+  CACTO_REQUIRE(ro_sched_args_ok(groups, workgroups), RO_SCHED_ARGS_MSG);
+  return dispatch_nj<LaunchRolloutPlan>(sys->host.p, sys, B, groups, workgroups, out);
+}
 
 extern "C" int cacto_rollout_sched(const cacto_sys* sys, const float* actor_netbuf_d, const double* S0_d,
                                    const int32_t* nsteps_d, int T, int use_actor, const double* W_d, double* S_traj_d,
@@ -2016,10 +1924,7 @@ extern "C" int cacto_rollout_sched(const cacto_sys* sys, const float* actor_netb
                                    const int32_t* order_d, int B, int groups, int workgroups, void* stream) {
   CACTO_REQUIRE(sys && S0_d && nsteps_d && T >= 0 && B >= 0, "cacto_rollout: bad arguments");
   CACTO_REQUIRE(!use_actor || actor_netbuf_d, "cacto_rollout: use_actor needs the actor net buffer");
-  CACTO_REQUIRE(groups == 0 || groups == 1 || groups == 2 || groups == 4 || groups == -1 || groups == -3,
-                "cacto_rollout_sched: groups must be 0, 1, 2, 4, -1 (two teams) or -3 (one slot per wave, layer 2 "
-                "split over K)");
-  CACTO_REQUIRE(workgroups >= 0, "cacto_rollout_sched: workgroups must be >= 0");
+  CACTO_REQUIRE(ro_sched_args_ok(groups, workgroups), RO_SCHED_ARGS_MSG);
   CACTO_REQUIRE(!(R_traj_d || EE_traj_d) || (S_traj_d && (A_traj_d || !use_actor)),
                 "cacto_rollout: R_traj / EE_traj need S_traj (and A_traj when use_actor)");
   if (B == 0) return CACTO_OK;

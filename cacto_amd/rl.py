@@ -754,6 +754,14 @@ class RL_AC:
                      int(sched[1]), stream())
         return out
 
+    def rollout_plan(self, B, sched=(0, 0)):
+        """cacto_rollout_plan: what rollout_batch runs for B episodes under `sched` — kind (0 single
+        team, 1 two teams, 2 one slot per wave), slot groups, workgroups, block_threads, lds_bytes,
+        cus. Raises for a schedule the system does not accept; launches nothing."""
+        plan = L.RoPlan()
+        L.lib().call("cacto_rollout_plan", self.sys.handle, int(B), int(sched[0]), int(sched[1]), C.byref(plan))
+        return {name: getattr(plan, name) for name, _ in L.RoPlan._fields_}
+
     def rollout_rewards(self, out, n, T, ep=1, weights=None):
         """Rewards / EE positions of a recorded rollout (cacto_rollout_rewards) into out["R"] /
         out["EE"]: the second kernel of a rollout, launched on its own (bench times it apart)."""

@@ -494,8 +494,8 @@ int cacto_to_solve(const cacto_sys* sys, const double* S0_d, const double* U_ini
                    double* U_d, double* step_cost_d, int32_t* status_d, int32_t* iters_d, double* J_d, void* ws_d,
                    size_t ws_bytes, void* stream);
 
-/* What cacto_to_solve runs for a system and a config (the role cacto_rollout_sched's arguments play
- * for the rollout: TO.py:37-100 has one host-side IPOPT call per episode and nothing to plan), so a
+/* What cacto_to_solve runs for a system and a config (the role cacto_rollout_plan plays for the
+ * rollout: TO.py:37-100 has one host-side IPOPT call per episode and nothing to plan), so a
  * caller can tell before capturing a call into a hipGraph whether it is one kernel. */
 typedef struct {
   int32_t on_device;         /* 1: the whole iteration loop runs in one kernel, no host round trip and
@@ -508,6 +508,29 @@ typedef struct {
 
 /* CACTO_EINVAL for a null argument or an unknown cfg_h->path; no device work, nothing enqueued. */
 int cacto_to_solve_plan(const cacto_sys* sys, const cacto_to_cfg* cfg_h, cacto_to_plan* out);
+
+/* What cacto_rollout_sched runs for B episodes under a schedule (groups, workgroups), decided by the
+ * same function that launches it. "eight" = the systems whose step needs no workgroup-wide dynamics
+ * (SI, car, car_park, the prismatic DI), "planar" = a planar 3-joint chain (the manipulator), CUs =
+ * the device's compute units, per = B / (8 CUs):
+ *   groups -3: eight or planar -> kind 2;  -1: eight -> kind 1;  any other system: CACTO_EINVAL
+ *   groups 1, 2, 4: kind 0 with that many slot groups
+ *   groups 0: planar -> kind 2; eight with B <= 16 CUs -> kind 2; else the prismatic chain with
+ *             per == 2 -> kind 1; else kind 0 with per >= 4 ? 4 : per >= 2 ? 2 : 1 slot groups
+ *   workgroups 0 -> one per CU; always clamped to [1, ceil(B / (4 groups))] */
+typedef struct {
+  int32_t kind;          /* 0 single team (k_rollout), 1 two teams (k_rollout_tt), 2 one slot per wave
+                          * (k_rollout_ks) */
+  int32_t groups;        /* groups of 4 episode slots per workgroup (kinds 1 and 2: 2) */
+  int32_t workgroups;    /* the grid */
+  int32_t block_threads; /* threads per workgroup */
+  int32_t lds_bytes;     /* the kernel's static LDS */
+  int32_t cus;           /* the compute-unit count the decision used */
+} cacto_ro_plan;
+
+/* CACTO_EINVAL for a null argument, B < 0 or a schedule the system does not accept; no device work,
+ * nothing enqueued. */
+int cacto_rollout_plan(const cacto_sys* sys, int B, int groups, int workgroups, cacto_ro_plan* out);
 
 /* ---------------------------------------------------------------- replay ------------------ */
 

@@ -98,12 +98,14 @@ def test_status_matches_oracle_under_refill(setup, sched):
     assert sum(fail[k] is not None and fail[k] > 5 for k in pinned) >= 2, "and some mid-episode"
     for k in pinned:
         assert st[k] == (1 if fail[k] is not None else 0), (k, fail[k], st[k])
-    # a dropped episode's trajectory is NaN from its failing state on, never a stale value
+    # a dropped episode's trajectory is NaN from its failing state on, never a stale value: the
+    # failing state has a NaN, and every component of every later row the episode owns is NaN
     S = got["S"].cpu().numpy()
     for k in pinned:
         if fail[k] is not None:
             assert np.isnan(S[k, fail[k] + 1]).any()
             assert np.isnan(S[k, ns_[k]]).any()
+            assert np.isnan(S[k, fail[k] + 2:ns_[k] + 1]).all(), (k, fail[k], ns_[k])
 
 
 @pytest.mark.parametrize("sched", [(1, 3), (-1, 2), (-3, 3), (-3, 1)])

@@ -441,6 +441,87 @@ def test_rollout_slot_refill_matches_one_episode_per_slot(system, sched):
         np.testing.assert_allclose(EE[k, n], oe.get_end_effector_position(S[k, n]), rtol=1e-12, atol=1e-12)
 
 
+# cacto_rollout_plan under groups = 0 for B = 1, 8, 9, 16C, 16C+1, 24C-1, 24C, 32C (C = the CU count):
+# (kind, slot groups), kind 0 = k_rollout<NJ, groups>, 1 = k_rollout_tt, 2 = k_rollout_ks. The rules
+# of the route as they were before it was a function of its own: the planar chain takes the
+# one-slot-per-wave kernel at every size; SI, car, car_park and the prismatic DI up to two episodes
+# per slot (B <= 16C); above that the DI takes two teams while B / (8C) == 2; everything else the
+# single-team kernel with 1, 2 or 4 groups for B / (8C) < 2, < 4, >= 4.
+_KS, _TT = (2, 2), (1, 2)
+_EIGHT_AUTO = [_KS, _KS, _KS, _KS, (0, 2), (0, 2), (0, 2), (0, 4)]
+PLAN_AUTO = {
+    "single_integrator": _EIGHT_AUTO, "car": _EIGHT_AUTO, "car_park": _EIGHT_AUTO,
+    "double_integrator": [_KS, _KS, _KS, _KS, _TT, _TT, (0, 2), (0, 4)],
+    "manipulator": [_KS] * 8,
+    "ur5": [(0, 1), (0, 1), (0, 1), (0, 2), (0, 2), (0, 2), (0, 2), (0, 4)],
+}
+PLAN_TWO_TEAMS = ("single_integrator", "car", "car_park", "double_integrator")     # groups = -1
+PLAN_WAVE_SLOT = PLAN_TWO_TEAMS + ("manipulator",)                                 # groups = -3
+PLAN_THREADS = {0: 256, 1: 512, 2: 512}
+# the kernels' static LDS as the compiler reports it for gfx950 (tools/resource_usage.py): (kind, groups) -> bytes
+PLAN_LDS = {
+    "single_integrator": {(0, 1): 78928, (0, 2): 89168, (0, 4): 109648, _TT: 154576, _KS: 26704},
+    "car": {(0, 1): 79024, (0, 2): 89360, (0, 4): 110032, _TT: 154768, _KS: 26704},
+    "car_park": {(0, 1): 79024, (0, 2): 89360, (0, 4): 110032, _TT: 154768, _KS: 26704},
+    "double_integrator": {(0, 1): 81184, (0, 2): 92256, (0, 4): 113376, _TT: 155056, _KS: 26704},
+    "manipulator": {(0, 1): 148800, (0, 2): 160720, (0, 4): 150784, _KS: 39120},
+    "ur5": {(0, 1): 155456, (0, 2): 153920, (0, 4): 149824},
+}
+
+
+@pytest.mark.parametrize("system", SYSTEMS)
+def test_rollout_plan_matches_route(system):
+    conf, genv, oe, nn, rl = _nets(system, None)
+    C = rl.rollout_plan(1)["cus"]
+    assert C > 0
+    sizes = [1, 8, 9, 16 * C, 16 * C + 1, 24 * C - 1, 24 * C, 32 * C]
+    for groups in (0, 1, 2, 4, -1, -3):
+        refused = (groups == -1 and system not in PLAN_TWO_TEAMS) or (groups == -3 and system not in PLAN_WAVE_SLOT)
+        for i, B in enumerate(sizes):
+            if refused:
+                with pytest.raises(RuntimeError, match=r"cacto_rollout_plan failed \(-1\)"):
+                    rl.rollout_plan(B, (groups, 0))
+                continue
+            kind, g = PLAN_AUTO[system][i] if groups == 0 else (0, groups) if groups > 0 else _TT if groups == -1 else _KS
+            most = -(-B // (4 * g))            # one workgroup per 4 g slots holds every episode
+            p = rl.rollout_plan(B, (groups, 0))
+            assert (p["kind"], p["groups"], p["workgroups"]) == (kind, g, max(1, min(C, most))), (system, groups, B, p)
+            assert p["block_threads"] == PLAN_THREADS[kind] and p["cus"] == C
+            assert p["lds_bytes"] == PLAN_LDS[system][(kind, g)], (system, groups, B, p)
+            # an explicit workgroup count is clamped to ceil(B / slots per workgroup)
+            for wgs in (3, 10 ** 6):
+                q = rl.rollout_plan(B, (groups, wgs))
+                assert (q["kind"], q["groups"], q["workgroups"]) == (kind, g, min(wgs, most)), (system, groups, B, wgs, q)
+
+
+def test_rollout_runs_what_the_plan_says():
+    """The three kernel kinds on the slot-refill test's inputs: the plan names a different kind for
+    each schedule, and the rollouts under them are bit-equal."""
+    conf, genv, oe, nn, rl = _nets("double_integrator", None, seed=4)
+    rng = random.Random(11)
+    n_ep = 45
+    S0 = np.array([oe.reset(rng) for _ in range(n_ep)])
+    ns_ = [conf.NSTEPS - int(s[-1] / conf.dt) for s in S0]
+    ns_[3] = 0
+    ns_[17] = 1
+    T = max(ns_)
+    scheds = [(1, 3), (-1, 2), (-3, 3)]
+    assert [rl.rollout_plan(n_ep, sc)["kind"] for sc in scheds] == [0, 1, 2]
+    assert [rl.rollout_plan(n_ep, sc)["workgroups"] for sc in scheds] == [3, 2, 3]
+    outs = [rl.rollout_batch(S0, ns_, T, sched=sc) for sc in scheds]
+    torch.cuda.synchronize()
+    ref = {k: outs[0][k].cpu().numpy() for k in ("S", "A", "R", "EE", "status")}
+    for got in outs[1:]:
+        got = {k: got[k].cpu().numpy() for k in ref}
+        np.testing.assert_array_equal(got["status"], ref["status"])
+        for k in range(n_ep):
+            n = ns_[k]
+            np.testing.assert_array_equal(got["S"][k, :n + 1], ref["S"][k, :n + 1])
+            np.testing.assert_array_equal(got["A"][k, :n], ref["A"][k, :n])
+            np.testing.assert_array_equal(got["R"][k, :n], ref["R"][k, :n])
+            np.testing.assert_array_equal(got["EE"][k, :n + 1], ref["EE"][k, :n + 1])
+
+
 @pytest.mark.parametrize("sched", [(0, 0), (-1, 2), (-1, 1), (1, 3), (-3, 2), (-3, 1)])
 def test_rollout_zero_controls_ep0_exact(sched):
     """ep == 0 (zero warm-start controls, no actor) on the default schedule, on the two-team kernel

@@ -1,59 +1,56 @@
-"""Diagnostic: per-phase cycle counts of one k_rollout step (workgroup 0, step 20) from the
-CACTO_STAMPS build. Not part of the product path.
+"""Diagnostic: cycles per step and phase of a rollout kernel, from the phase clock of the
+CACTO_STAMPS build (RoClock in csrc/rollout_kernels.hip, where the phases are described). Not part
+of the product path.
 
     python -c "from cacto_amd.build import build_variant; build_variant('libcacto_hip_stamps', ['CACTO_STAMPS'])"
     CACTO_HIP_LIB=cacto_amd/libcacto_hip_stamps.so python tools/rollout_stamps.py [system [R [groups,workgroups]]]
+
+The table is [1024 workgroups][8 hardware waves][9 phases + the wave's step count], written by lane
+0 of every wave of the last rollout launch. k_rollout has waves 0-3; k_rollout_tt's team is wave >> 2
+and its dynamics wave is wave 0 (team 0) or 7 (team 1); every wave of k_rollout_ks runs a slot.
 """
 import ctypes
 import os
-import random
 import sys
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.argv += [] if len(sys.argv) > 1 else ["double_integrator"]
 
 from cacto_amd import _lib as L  # noqa: E402
 import bench  # noqa: E402
 
+PHASES = ["L1", "L2", "L3", "DYN", "STEP", "STORE", "REFILL", "X0", "BAR"]
+WGS, WAVES, COLS = 1024, 8, len(PHASES) + 1
 
-def main():
-    system = sys.argv[1]
+
+def clock_table(entry="cacto_debug_rollout_stamps"):
+    acc = (ctypes.c_ulonglong * (WGS * WAVES * COLS))()
+    getattr(L.lib().dll, entry)(acc)
+    return np.array(acc[:], dtype=np.float64).reshape(WGS, WAVES, COLS)
+
+
+def report(system, R, sched, entry="cacto_debug_rollout_stamps"):
     conf, env, rl = bench.make_learner(system)
-    R = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
     S0, n = bench.initial_states(env, conf, R, seed=0)
     T = int(n.max())
     inputs = rl.rollout_inputs(S0, n)
-    sched = tuple(int(x) for x in sys.argv[3].split(",")) if len(sys.argv) > 3 else None
+    plan = rl.rollout_plan(R, sched)
     for _ in range(3):
-        out = rl.rollout_batch(None, None, T, inputs=inputs, sched=sched or (0, 0))
+        rl.rollout_batch(None, None, T, inputs=inputs, want=("S", "A"), sched=sched)
     torch.cuda.synchronize()
-    st = (ctypes.c_ulonglong * 20)()
-    L.lib().dll.cacto_debug_rollout_stamps(st)
-    t = np.array(st[:4], dtype=np.float64)
-    a1, a2 = float(st[4]) - t[0], float(st[5]) - float(st[4])
-    names = ["actor", "E1 (dynamics | reward terms)", "E2 (reward combine + stores + refill | EE(s'))"]
-    print(system, R, "step cycles %.0f: " % (t[3] - t[0]) + ", ".join("%s %.0f" % (nm, d) for nm, d in zip(names, np.diff(t))))
-    print("   actor: layer 1 (+ placements) %.0f, layer 2 %.0f, layer 3 %.0f" % (a1, a2, t[1] - float(st[5])))
-    if st[9] > st[1]:
-        print("   chain dynamics after the actor: RNEA (wave 0) %.0f, CRBA columns (waves 1-3) %s"
-              % (float(st[9]) - t[1], ", ".join("%.0f" % (float(st[9 + w]) - t[1]) if st[9 + w] > st[1] else "-"
-                                                   for w in (1, 2, 3))))
-    if st[17] > st[1] and st[18] > st[17]:
-        print("   RNEA by lanes: loads %.0f, v / a rounds %.0f, force terms %.0f, force rounds %.0f"
-              % (float(st[17]) - t[1], float(st[18]) - float(st[17]), float(st[19]) - float(st[18]),
-                 float(st[9]) - float(st[19])))
-    if st[13] > st[2] or st[14] > st[2]:
-        print("   reward waves after the actor / dynamics phase: r_t (wave 1) %s, EE(s_t) (wave 2) %s, EE(s_n) (wave 3) %s"
-              % tuple("%.0f" % (float(st[k]) - t[2]) if st[k] > st[2] else "-" for k in (13, 14, 15)))
-    print("   wave 0 after the dynamics phase: s' %.0f, advance/stores %.0f, refill+ballot %.0f, barrier %.0f"
-          % (float(st[6]) - t[2], float(st[7]) - float(st[6]), float(st[8]) - float(st[7]), t[3] - float(st[8])))
-    if st[16] >= st[6]:
-        print("      (of advance/stores: next input (revolute chains: before the stores) %.0f, stores %.0f)"
-              % (float(st[16]) - float(st[6]), float(st[7]) - float(st[16])))
+    a = clock_table(entry)[:plan["workgroups"], :plan["block_threads"] // 64]
+    print(system, R, "sched", sched, "plan", plan)
+    print("   wave  steps  cycles/step  " + "  ".join("%6s" % p for p in PHASES))
+    for w in range(a.shape[1]):
+        steps = a[:, w, -1].sum()
+        per = a[:, w, :-1].sum(axis=0) / max(steps, 1)
+        print("   %4d %6d  %11.0f  " % (w, steps, per.sum()) + "  ".join("%6.0f" % x for x in per))
 
 
 if __name__ == "__main__":
-    main()
+    system = sys.argv[1] if len(sys.argv) > 1 else "double_integrator"
+    R = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
+    sched = tuple(int(x) for x in sys.argv[3].split(",")) if len(sys.argv) > 3 else (0, 0)
+    report(system, R, sched)
