@@ -71,7 +71,17 @@ class RoPlan(C.Structure):
                 ("block_threads", C.c_int32), ("lds_bytes", C.c_int32), ("cus", C.c_int32)]
 
 
+class UpdPlan(C.Structure):
+    """cacto_upd_plan: which kernels the update calls run for a batch (cacto_update_plan)."""
+    _fields_ = [(n, C.c_int32) for n in (
+        "Bp", "chain_tile", "elu", "paired",
+        "critic_rows", "critic_chunk", "critic_nch", "critic_gemm", "critic_xcd", "critic_adam_nch",
+        "actor_rows", "actor_chunk", "actor_nch", "actor_gemm", "actor_xcd", "actor_adam_nch",
+        "xcd_tiles", "pair_xcds", "per_overlap", "devwait_actor", "cus")]
+
+
 RO_KIND_TEAM, RO_KIND_TWO_TEAMS, RO_KIND_WAVE_SLOT = 0, 1, 2
+WG_FUSED, WG_SPLIT, WG_BIG = 0, 1, 2
 CACTO_TO_CONVERGED, CACTO_TO_MAXITER, CACTO_TO_FAILED = 0, 1, 2
 CACTO_TO_PATH_DEFAULT, CACTO_TO_PATH_WAVE = 0, 1
 
@@ -94,6 +104,7 @@ _SIGS = {
     "cacto_critic_forward": (C.c_int, [vp, vp, vp, vp, C.c_int, vp]),
     "cacto_critic_input_grad": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp]),
     "cacto_workspace_bytes": (sz, [vp, C.c_int]),
+    "cacto_update_plan": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(UpdPlan)]),
     "cacto_critic_grad": (C.c_int, [vp, C.POINTER(Nets), C.POINTER(UpdateCfg), vp, vp, vp, C.c_int, vp, vp,
                                     vp, vp, vp, sz, vp]),
     "cacto_actor_grad": (C.c_int, [vp, C.POINTER(Nets), C.POINTER(UpdateCfg), vp, vp, C.c_int, vp, vp, sz, vp]),

@@ -1,4 +1,4 @@
-// Where learn_kernels.hip (the kernels, the launch_* functions that name one, the knobs that pick
+// Where learn_kernels.hip (the kernels, the launch_* functions that name one, the route that picks
 // one) and learn_host.hip (workspace, C ABI, update pipelines) meet: plain structs and declarations.
 #pragma once
 
@@ -68,7 +68,41 @@ struct AdamNet {  // one network of the fused weight-gradient + Adam launch (k_w
   int ioff[MAX_LAYERS + 1];     // first item of layer l: KT*OT weight tiles then OT bias tiles
 };
 
+// Which kernels a batch takes: the one place it is decided (learn_route), a function of the two
+// networks, whether the critic's Sobolev half is on, the batch and the device's CU count — no
+// environment, no launches. Every update path of one batch reads the same route, so every path
+// runs the same kernels on the same sums (bit-identical results). cacto_update_plan reports it.
+enum { WG_FUSED = 0, WG_SPLIT = 1, WG_BIG = 2 };
+struct NetRoute {  // one network's weight-gradient GEMM and Adam step
+  int rows;      // gradient rows: critic 2 Bp with the Sobolev half, else Bp; actor Bp
+  int chunk;     // rows per split-K chunk (one slab each): 64 up to 1024 rows, 128 below 4096, else 256
+  int nch;       // chunks
+  int gemm;      // the update's: WG_FUSED (k_wgrad_adam, with its Adam), WG_SPLIT (k_wgrad), WG_BIG
+                 // (k_wgrad_big). cacto_critic_grad / cacto_actor_grad and the data-parallel paths keep
+                 // the slabs at every batch: k_wgrad where the update fuses
+  int xcd;       // the split GEMM's workgroups dealt by XCD (from 8 chunks on)
+  int adam_nch;  // the k_adam / k_reduce instance that sums the chunks (nch_instance)
+};
+struct LearnRoute {
+  int Bp;             // batch rounded up to 16
+  int tile;           // samples per chain workgroup: Q4_TILE or CACTO_TILE
+  int elu;            // the elu critic's chain kernels (elu_kernels.hip)
+  int paired;         // cacto_update_n[_per]: the paired single-stream pipeline with fused GEMM + Adam
+                      // launches; else two streams and split launches
+  NetRoute critic, actor;
+  int xcd_tiles;      // ChainScalars::xcd_tiles
+  int pair_xcds;      // XCDs the paired q4 chain grid runs on (0: not a q4 batch)
+  int per_overlap;    // the batch's half of per_overlap_ok: k_wgrad_big and a k_adam<NCH> that holds
+                      // every chunk, for the critic
+  int devwait_actor;  // the batch's half of the actor chain's device-side wait: 16-sample tiles, at
+                      // most one actor workgroup per CU
+};
+LearnRoute learn_route(const NetTopo& critic, const NetTopo& actor, bool sobolev, int B, int cus);
+int nch_instance(int nch);
+int cu_count();
+
 struct Workspace {
+  LearnRoute route;  // of the call's batch (plan)
   GradBufs crit, act;
   float* slab;    // critic weight-gradient slabs
   float* slab_a;  // actor's (a separate region: cacto_update_n overlaps the two steps)
@@ -81,20 +115,12 @@ struct Workspace {
   int Bp;
 };
 
-// Which kernel a batch takes (learn_kernels.hip): functions of the batch and the network only.
-int q4_max_bp();
-int chain_tile(const NetTopo& critic, int Bp);
-int cu_count();
-int wg_chunk(int rows);
-bool wgrad_big(const NetTopo& t, int rows);
-bool fused_adam(int Bp);
-
+// The launches (learn_kernels.hip); each reads w.route.
 int launch_reduce(const float* slab, int nch, int P, float* out, hipStream_t st);
-// the weight-gradient GEMM of a network into its slabs (launch_wgrad over the critic's / actor's rows)
-int launch_critic_wgrad(const cacto_sys* sys, bool sobolev, const Workspace& w, hipStream_t st,
-                        int* nch, const PerRunArgs* per_run = nullptr);
-int launch_actor_wgrad(const cacto_sys* sys, const Workspace& w, hipStream_t st, int* nch,
-                       unsigned long long* sig_p = nullptr, unsigned long long sig_v = 0);
+// the weight-gradient GEMM of a network into its slabs (route.critic.nch / route.actor.nch of them)
+int launch_critic_wgrad(const cacto_sys* sys, const Workspace& w, hipStream_t st, const PerRunArgs* per_run = nullptr);
+int launch_actor_wgrad(const cacto_sys* sys, const Workspace& w, hipStream_t st, unsigned long long* sig_p = nullptr,
+                       unsigned long long sig_v = 0);
 int launch_critic_chain(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
                         const double* storage, const int32_t* idx, const float* isw, int B, float* y, float* V,
                         float* Vt, const Workspace& w, hipStream_t st);
@@ -102,7 +128,7 @@ int launch_actor_chain(const cacto_sys* sys, const cacto_nets* nets, const cacto
                        const double* storage, const int32_t* idx, int B, const Workspace& w, hipStream_t st,
                        const unsigned long long* wait_p = nullptr, unsigned long long wait_v = 0,
                        int wait_at_start = 0);
-ChainScalars chain_scalars(const cacto_update_cfg* cfg, int B);
+ChainScalars chain_scalars(const cacto_update_cfg* cfg, const LearnRoute& r, int B);
 int launch_chain_pair(const cacto_sys* sys, const NetView& C, const NetView& Tg, const NetView& Ac,
                       const ChainScalars& cs, const double* storage, const int32_t* idx_c, const float* isw,
                       const int32_t* idx_a, int B, const Workspace& w, float* y, float* V, int32_t* step,

@@ -20,9 +20,12 @@ inline size_t critic_buf_floats(const NetTopo& tc) { return (size_t)flat_span(tc
 inline size_t critic_buf_bytes(const NetTopo& tc) { return critic_buf_floats(tc) * sizeof(float); }
 inline size_t critic_buf_stride(const NetTopo& tc) { return align64(critic_buf_floats(tc)); }
 
-Workspace plan(const cacto_sys* sys, int B, char* base) {
+// The route and the workspace map of a call of batch B. The map does not depend on `sobolev`: the
+// critic's slabs are sized for its 2 Bp rows either way.
+Workspace plan(const cacto_sys* sys, bool sobolev, int B, char* base) {
   Workspace w{};
-  const int Bp = (B + 15) / 16 * 16;
+  w.route = learn_route(sys->critic, sys->actor, sobolev, B, cu_count());
+  const int Bp = w.route.Bp;
   w.Bp = Bp;
   const NetTopo& tc = sys->critic;
   const NetTopo& ta = sys->actor;
@@ -48,8 +51,9 @@ Workspace plan(const cacto_sys* sys, int B, char* base) {
     aoff += (size_t)16 * ta.OT[l] * w.act.ld;
   }
   off = align64(aoff);
-  const int nch_a = ceil_div(Bp, wg_chunk(Bp));
-  const int nch_c = ceil_div(2 * Bp, wg_chunk(2 * Bp));  // Sobolev rows, or the plain half
+  const int nch_a = w.route.actor.nch;
+  const int nch_c = sobolev ? w.route.critic.nch  // of the 2 Bp rows
+                            : learn_route(sys->critic, sys->actor, true, B, cu_count()).critic.nch;
   w.slab = f ? f + off : nullptr;
   off += align64((size_t)nch_c * tc.params);
   w.slab_a = f ? f + off : nullptr;
@@ -81,26 +85,25 @@ int critic_step_tail(const cacto_sys* sys, const cacto_nets* nets, const cacto_u
                      unsigned long long wait_v = 0, unsigned long long* sig_p = nullptr, unsigned long long sig_v = 0,
                      const PerRunArgs* per_run = nullptr, const PerSampleArgs* sample = nullptr, int thru = 0) {
   const int soft = cfg->MC ? 0 : 1;
-  if (fused_adam(w.Bp)) return launch_wgrad_adam(sys, 0, critic_adam_net(sys, nets, cfg, w, soft, src, nb), nullptr,
-                                                 nets->step_d, st);
-  int nch = 0;
-  if (int e = launch_critic_wgrad(sys, cfg->w_S != 0.0, w, st, &nch, per_run)) return e;
+  if (w.route.critic.gemm == WG_FUSED)
+    return launch_wgrad_adam(sys, 0, critic_adam_net(sys, nets, cfg, w, soft, src, nb), nullptr, nets->step_d, st);
+  if (int e = launch_critic_wgrad(sys, w, st, per_run)) return e;
   cacto_nets dst = *nets;
   dst.critic_d = nb;
-  return launch_adam(sys, &dst, cfg, CACTO_NET_CRITIC, w.slab, nch, soft, st, src, wait_p, wait_v, sig_p, sig_v,
-                     sample, thru);
+  return launch_adam(sys, &dst, cfg, CACTO_NET_CRITIC, w.slab, w.route.critic.nch, soft, st, src, wait_p, wait_v, sig_p,
+                     sig_v, sample, thru);
 }
 
 int actor_step_tail(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg, const Workspace& w,
                     hipStream_t st, unsigned long long* sig_p = nullptr, unsigned long long sig_v = 0) {
-  if (fused_adam(w.Bp)) return launch_wgrad_adam(sys, 1, actor_adam_net(sys, nets, cfg, w), nullptr, nets->step_d, st);
-  int nch = 0;
-  if (int e = launch_actor_wgrad(sys, w, st, &nch, sig_p, sig_v)) return e;
-  return launch_adam(sys, nets, cfg, CACTO_NET_ACTOR, w.slab_a, nch, 0, st);
+  if (w.route.actor.gemm == WG_FUSED)
+    return launch_wgrad_adam(sys, 1, actor_adam_net(sys, nets, cfg, w), nullptr, nets->step_d, st);
+  if (int e = launch_actor_wgrad(sys, w, st, sig_p, sig_v)) return e;
+  return launch_adam(sys, nets, cfg, CACTO_NET_ACTOR, w.slab_a, w.route.actor.nch, 0, st);
 }
 
 #define CHECK_WS(ws, nbytes, B)                                                                   \
-  CACTO_REQUIRE((ws) != nullptr && (nbytes) >= plan(sys, (B), nullptr).bytes,                     \
+  CACTO_REQUIRE((ws) != nullptr && (nbytes) >= plan(sys, true, (B), nullptr).bytes,               \
                 "workspace too small: query cacto_workspace_bytes(sys, B)");                      \
   CACTO_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "workspace must be 256-byte aligned")
 
@@ -113,13 +116,12 @@ int pair_grads(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_
                const int32_t* idx_c_d, const float* is_w_d, const int32_t* idx_a_d, int B, float* grad_d, float* y_d,
                float* V_d, void* workspace_d, size_t workspace_bytes, int stages, hipStream_t st) {
   CHECK_WS(workspace_d, workspace_bytes, B);
-  const Workspace w = plan(sys, B, static_cast<char*>(workspace_d));
+  const Workspace w = plan(sys, cfg->w_S != 0.0, B, static_cast<char*>(workspace_d));
   const int Pc = sys->critic.params, Pa = sys->actor.params;
   if (stages & 2) {
     if (!idx_a_d) return CACTO_OK;
-    int nch = 0;
-    if (int e = launch_actor_wgrad(sys, w, st, &nch)) return e;
-    return launch_reduce(w.slab_a, nch, Pa, grad_d + Pc, st);
+    if (int e = launch_actor_wgrad(sys, w, st)) return e;
+    return launch_reduce(w.slab_a, w.route.actor.nch, Pa, grad_d + Pc, st);
   }
   float* yb = y_d ? y_d : w.scal;
   float* Vb = V_d ? V_d : w.scal + w.Bp;
@@ -127,8 +129,8 @@ int pair_grads(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_
     const NetView C = cacto_make_view(sys, CACTO_NET_CRITIC, nets->critic_d);
     const NetView Tg = cacto_make_view(sys, CACTO_NET_CRITIC, nets->target_d);
     const NetView Ac = cacto_make_view(sys, CACTO_NET_ACTOR, nets->actor_d);
-    if (int e = launch_chain_pair(sys, C, Tg, Ac, chain_scalars(cfg, B), storage_d, idx_c_d, is_w_d, idx_a_d, B, w, yb,
-                                  Vb, nets->step_d, st))
+    if (int e = launch_chain_pair(sys, C, Tg, Ac, chain_scalars(cfg, w.route, B), storage_d, idx_c_d, is_w_d, idx_a_d,
+                                  B, w, yb, Vb, nets->step_d, st))
       return e;
   } else if (idx_c_d) {
     if (int e = launch_critic_chain(sys, nets, cfg, storage_d, idx_c_d, is_w_d, B, yb, Vb, nullptr, w, st)) return e;
@@ -136,9 +138,8 @@ int pair_grads(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_
     if (int e = launch_actor_chain(sys, nets, cfg, storage_d, idx_a_d, B, w, st)) return e;
   }
   if (idx_c_d) {
-    int nch = 0;
-    if (int e = launch_critic_wgrad(sys, cfg->w_S != 0.0, w, st, &nch)) return e;
-    if (int e = launch_reduce(w.slab, nch, Pc, grad_d, st)) return e;
+    if (int e = launch_critic_wgrad(sys, w, st)) return e;
+    if (int e = launch_reduce(w.slab, w.route.critic.nch, Pc, grad_d, st)) return e;
   }
   if (stages & 2) return pair_grads(sys, nets, cfg, storage_d, idx_c_d, is_w_d, idx_a_d, B, grad_d, y_d, V_d,
                                     workspace_d, workspace_bytes, 2, st);
@@ -148,7 +149,19 @@ int pair_grads(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_
 
 extern "C" size_t cacto_workspace_bytes(const cacto_sys* sys, int B) {
   if (!sys || B <= 0) return 0;
-  return plan(sys, B, nullptr).bytes;
+  return plan(sys, true, B, nullptr).bytes;
+}
+
+// the route, reported
+extern "C" int cacto_update_plan(const cacto_sys* sys, int sobolev, int B, cacto_upd_plan* out) {
+  CACTO_REQUIRE(sys && out && B > 0, "cacto_update_plan: bad arguments");
+  const int cus = cu_count();
+  const LearnRoute r = learn_route(sys->critic, sys->actor, sobolev != 0, B, cus);
+  const NetRoute &c = r.critic, &a = r.actor;
+  *out = cacto_upd_plan{r.Bp,       r.tile,    r.elu,      r.paired,  c.rows,     c.chunk,     c.nch,
+                        c.gemm,     c.xcd,     c.adam_nch, a.rows,    a.chunk,    a.nch,       a.gemm,
+                        a.xcd,      a.adam_nch, r.xcd_tiles, r.pair_xcds, r.per_overlap, r.devwait_actor, cus};
+  return CACTO_OK;
 }
 
 extern "C" int cacto_critic_grad(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
@@ -158,12 +171,11 @@ extern "C" int cacto_critic_grad(const cacto_sys* sys, const cacto_nets* nets, c
   CACTO_REQUIRE(sys && cfg && storage_d && idx_d && grad_d && B > 0, "cacto_critic_grad: bad arguments");
   if (int e = check_nets(nets)) return e;
   CHECK_WS(workspace_d, workspace_bytes, B);
-  const Workspace w = plan(sys, B, static_cast<char*>(workspace_d));
+  const Workspace w = plan(sys, (float)cfg->w_S != 0.f, B, static_cast<char*>(workspace_d));
   hipStream_t st = as_stream(stream);
-  int nch = 0;
   if (int e = launch_critic_chain(sys, nets, cfg, storage_d, idx_d, is_w_d, B, y_d, V_d, Vt_d, w, st)) return e;
-  if (int e = launch_critic_wgrad(sys, (float)cfg->w_S != 0.f, w, st, &nch)) return e;
-  return launch_reduce(w.slab, nch, sys->critic.params, grad_d, st);
+  if (int e = launch_critic_wgrad(sys, w, st)) return e;
+  return launch_reduce(w.slab, w.route.critic.nch, sys->critic.params, grad_d, st);
 }
 
 extern "C" int cacto_actor_grad(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,
@@ -172,12 +184,11 @@ extern "C" int cacto_actor_grad(const cacto_sys* sys, const cacto_nets* nets, co
   CACTO_REQUIRE(sys && cfg && storage_d && idx_d && grad_d && B > 0, "cacto_actor_grad: bad arguments");
   if (int e = check_nets(nets)) return e;
   CHECK_WS(workspace_d, workspace_bytes, B);
-  const Workspace w = plan(sys, B, static_cast<char*>(workspace_d));
+  const Workspace w = plan(sys, cfg->w_S != 0.0, B, static_cast<char*>(workspace_d));
   hipStream_t st = as_stream(stream);
-  int nch = 0;
   if (int e = launch_actor_chain(sys, nets, cfg, storage_d, idx_d, B, w, st)) return e;
-  if (int e = launch_actor_wgrad(sys, w, st, &nch)) return e;
-  return launch_reduce(w.slab_a, nch, sys->actor.params, grad_d, st);
+  if (int e = launch_actor_wgrad(sys, w, st)) return e;
+  return launch_reduce(w.slab_a, w.route.actor.nch, sys->actor.params, grad_d, st);
 }
 
 extern "C" int cacto_adam_step(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg, int which,
@@ -200,7 +211,7 @@ extern "C" int cacto_update(const cacto_sys* sys, const cacto_nets* nets, const 
   CACTO_REQUIRE(sys && cfg && storage_d && idx_d && B > 0, "cacto_update: bad arguments");
   if (int e = check_nets(nets)) return e;
   CHECK_WS(workspace_d, workspace_bytes, B);
-  const Workspace w = plan(sys, B, static_cast<char*>(workspace_d));
+  const Workspace w = plan(sys, cfg->w_S != 0.0, B, static_cast<char*>(workspace_d));
   hipStream_t st = as_stream(stream);
   if (int e = launch_critic_chain(sys, nets, cfg, storage_d, idx_d, is_w_d, B, y_d, V_d, Vt_d, w, st)) return e;
   if (int e = critic_step_tail(sys, nets, cfg, w, st, nullptr, nets->critic_d)) return e;
@@ -269,19 +280,18 @@ struct PerArgs {
 
 // Whether the PER loop of this batch can take the overlapped form: the count deferred into the
 // priority update (large batches), a priority update at all (alpha != 0), 256-leaf subtrees whose
-// roots fit one workgroup, the large-batch critic GEMM and an Adam step with all chunks in flight.
+// roots fit one workgroup, and the route's half (the large-batch critic GEMM and an Adam step with
+// all chunks in flight).
 // CACTO_PER_OVERLAP (default 1): the pipelined PER loop's priority update and next sample share the
 // critic GEMM's and Adam's launches (k_wgrad_big_per, k_adam_sample) instead of following them.
-bool per_overlap_ok(const cacto_sys* sys, const cacto_update_cfg* cfg, const PerArgs* per, int B, const Workspace& w) {
+bool per_overlap_ok(const PerArgs* per, int B, const Workspace& w) {
   static const bool on = [] {
     const char* e = std::getenv("CACTO_PER_OVERLAP");
     return !(e && e[0] == '0');
   }();
   if (!per || !on || B < cacto_per_mw_min() || per->alpha == 0.0) return false;
   if (per->cap < 2 * PER_RUN_SUB || per->cap > (int64_t)PER_RUN_SUB * PER_RUN_SUB || per->cap % PER_RUN_SUB) return false;
-  if (fused_adam(w.Bp)) return false;
-  const int rows = cfg->w_S != 0.0 ? 2 * w.Bp : w.Bp;  // the critic GEMM's (launch_critic_wgrad)
-  return wgrad_big(sys->critic, rows) && ceil_div(rows, wg_chunk(rows)) <= 64;
+  return w.route.per_overlap != 0;
 }
 
 // The priority update of one PER step (RL.py:129-131). late_count: the sampler left its
@@ -297,7 +307,7 @@ int per_priority_update(const PerArgs* per, const int32_t* idx, const float* y, 
                           per->alpha, per->max_priority, B, st);
 }
 
-// Small batches (fused_adam): one stream, K + 1 steps. Step t runs the critic chain of update t
+// Small batches (route.paired): one stream, K + 1 steps. Step t runs the critic chain of update t
 // and the actor chain of update t - 1 as one grid (k_chain_pair), then both GEMM + Adam steps as
 // one k_wgrad_adam launch:
 //   critic(t) reads C_t, T_t (Adam of step t - 1 wrote them); actor(t-1) reads A_{t-1} and C_t —
@@ -311,7 +321,7 @@ int update_pipeline_pair(const cacto_sys* sys, const cacto_nets* nets, const cac
   float* const y = w.scal;
   float* const V = w.scal + w.Bp;
   const int soft = cfg->MC ? 0 : 1;
-  const ChainScalars cs = chain_scalars(cfg, B);
+  const ChainScalars cs = chain_scalars(cfg, w.route, B);
   const NetView C = cacto_make_view(sys, CACTO_NET_CRITIC, nets->critic_d);
   const NetView Tg = cacto_make_view(sys, CACTO_NET_CRITIC, nets->target_d);
   const NetView Ac = cacto_make_view(sys, CACTO_NET_ACTOR, nets->actor_d);
@@ -524,14 +534,14 @@ int update_pipeline_body(const cacto_sys* sys, const cacto_nets* nets, const cac
   // q4 chains take no wait), at most one actor workgroup per CU (a CU holding one actor workgroup
   // still fits a critic chain, GEMM or Adam workgroup beside it, so the critic stream always
   // progresses). DI B = 4096 13.2-13.3 k -> 14.2-14.4 k updates/s (r05).
-  const bool devwait_actor = devwait && chain_tile(sys->critic, w.Bp) == CACTO_TILE && w.Bp / CACTO_TILE <= cu_count();
+  const bool devwait_actor = devwait && w.route.devwait_actor;
   const int thru = devwait_actor ? 1 : 0;
   unsigned long long* const sig = ms->pipe_sig;
   // the overlapped PER form (per_overlap_ok): priority update t inside the critic GEMM's launch,
   // sample t + 1 inside its Adam's; the index ring has five buffers (sample t + 1 runs in the launch
   // after the Adam(t - 1) that waited for actor chain t - 4). Otherwise the sample and the priority
   // update run on the critic stream between its launches.
-  const bool ovl = per && devwait && per_overlap_ok(sys, cfg, per, B, w);
+  const bool ovl = devwait && per_overlap_ok(per, B, w);
   const int nring = ovl ? 5 : devwait ? 4 : 3;
   const unsigned long long base = ms->pipe_seq;
   ms->pipe_seq = base + K;  // reserved up front: no later call's waits can be satisfied by this call's values
@@ -689,7 +699,7 @@ int update_pipeline_dp_body(const cacto_sys* sys, const cacto_nets* nets, const 
   // and the sample of t + 1 (IS weights over the union) inside the Adam's launch; the index ring has
   // five buffers (sample t + 1 overwrites the one actor chain t - 4 read, which the marker before
   // update t - 1 or t covers). Otherwise the sample and the priority update run between the launches.
-  const bool ovl = per && per_overlap_ok(sys, cfg, per, B, w);
+  const bool ovl = per_overlap_ok(per, B, w);
   const int nring = ovl ? 5 : 3;
   const int nroot = per ? (int)(per->cap / PER_RUN_SUB) : 0;
   double* const stats = ms->dp_stats;       // [3] this shard
@@ -724,7 +734,6 @@ int update_pipeline_dp_body(const cacto_sys* sys, const cacto_nets* nets, const 
     cur.critic_d = buf[t % 3];
     nxt.critic_d = buf[(t + 1) % 3];
     if (int e = launch_critic_chain(sys, &cur, cfg, storage_d, idx, isw, B, y, V, nullptr, w, st)) return e;
-    int nch = 0;
     PerRunArgs pra{};
     PerSampleArgs psa{};
     if (ovl) {
@@ -733,7 +742,7 @@ int update_pipeline_dp_body(const cacto_sys* sys, const cacto_nets* nets, const 
       pra = per_run_args(per, idx, w, t + 1 < K && nroot > 1 ? shards : nullptr, 3 * ms->dp_rank, 3 * ms->dp_world);
       if (t + 1 < K) psa = per_sample_args(per, t, B, nring, w, shards, ms->dp_world);
     }
-    if (int e = launch_critic_wgrad(sys, cfg->w_S != 0.0, w, st, &nch, ovl ? &pra : nullptr)) return e;
+    if (int e = launch_critic_wgrad(sys, w, st, ovl ? &pra : nullptr)) return e;
     if (ovl && t + 1 < K) {
       if (nroot > 1)  // the table with this rank's words filled and the others zero: summed = gathered
         CACTO_CHECK_RCCL(R.all_reduce(shards, shards, (size_t)3 * ms->dp_world, ncclFloat64, ncclSum, cc, st),
@@ -741,7 +750,7 @@ int update_pipeline_dp_body(const cacto_sys* sys, const cacto_nets* nets, const 
       else if (int e = gather_stats())
         return e;
     }
-    if (int e = launch_reduce(w.slab, nch, Pc, ms->dp_gc, st)) return e;
+    if (int e = launch_reduce(w.slab, w.route.critic.nch, Pc, ms->dp_gc, st)) return e;
     CACTO_CHECK_RCCL(R.all_reduce(ms->dp_gc, ms->dp_gc, (size_t)Pc, ncclFloat32, ncclSum, cc, st),
                      "ncclAllReduce(critic gradient)");
     cacto_nets dst = *nets;
@@ -755,9 +764,8 @@ int update_pipeline_dp_body(const cacto_sys* sys, const cacto_nets* nets, const 
       if (int e = per_priority_update(per, idx, y, V, B, false, st)) return e;
     CACTO_CHECK_HIP(hipStreamWaitEvent(side, ms->ev_critic, 0));
     if (int e = launch_actor_chain(sys, &nxt, cfg, storage_d, idx, B, w, side)) return e;
-    int ncha = 0;
-    if (int e = launch_actor_wgrad(sys, w, side, &ncha)) return e;
-    if (int e = launch_reduce(w.slab_a, ncha, Pa, ms->dp_ga, side)) return e;
+    if (int e = launch_actor_wgrad(sys, w, side)) return e;
+    if (int e = launch_reduce(w.slab_a, w.route.actor.nch, Pa, ms->dp_ga, side)) return e;
     CACTO_CHECK_RCCL(R.all_reduce(ms->dp_ga, ms->dp_ga, (size_t)Pa, ncclFloat32, ncclSum, ca, side),
                      "ncclAllReduce(actor gradient)");
     if (int e = launch_adam(sys, nets, cfg, CACTO_NET_ACTOR, ms->dp_ga, 1, 0, side)) return e;
@@ -789,13 +797,13 @@ int update_n(const char* name, bool dp, const cacto_sys* sys, const cacto_nets* 
   if (int e = check_nets(nets)) return e;
   CHECK_WS(workspace_d, workspace_bytes, B);
   if (K == 0) return CACTO_OK;
-  const Workspace w = plan(sys, B, static_cast<char*>(workspace_d));
+  const Workspace w = plan(sys, cfg->w_S != 0.0, B, static_cast<char*>(workspace_d));
   hipStream_t st = as_stream(stream);
   if (dp) return update_pipeline_dp(sys, nets, cfg, storage_d, idx_d, per, K, B, w, st);
   // small batches: the paired single-stream schedule with the sampling and priority update between
   // steps (car_park B = 64 with the q4 chains: 21.1 k vs 19.8 k updates/s two-stream); larger
   // batches keep the two-stream pipeline (the actor step beside the sampling / priority update)
-  if (fused_adam(w.Bp)) return update_pipeline_pair(sys, nets, cfg, storage_d, idx_d, per, K, B, w, st);
+  if (w.route.paired) return update_pipeline_pair(sys, nets, cfg, storage_d, idx_d, per, K, B, w, st);
   return update_pipeline(sys, nets, cfg, storage_d, idx_d, per, K, B, w, st);
 }
 }  // namespace

@@ -15,6 +15,7 @@
 // critic's chain kernels, which the launch_* functions here hand an elu-topology handle to).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 #include "learn.h"
@@ -125,11 +126,6 @@ namespace cacto {
 // in a fixed order, so the result is deterministic), or up to 4 bias tiles (one per wave). A
 // block loads each LT/RT panel slice once for 4 tiles instead of once per tile.
 constexpr int WG_BLK = 4;
-// 16-row steps of panel slices in flight per wave. Measured (updates/s, DI B = 4096): 1 11.3 k,
-// 2 10.5 k, 3 10.3 k — deeper prefetch costs the GEMM its 4 waves per SIMD beside the chains.
-#ifndef WG_PF
-#define WG_PF 1
-#endif
 
 // One workgroup's block of NI x NO output tiles (of a layer) over the rows [lo, hi) of one chunk:
 // the 4 waves split the rows, each keeping NI x NO accumulator tiles, then reduce through LDS in a
@@ -148,10 +144,11 @@ __device__ __forceinline__ void wg_block(const WgArgs& a, const WgLayer& Ly, int
     for (int o = 0; o < NO; ++o) acc[i][o] = floatx4{0.f, 0.f, 0.f, 0.f};
   const float* ap = Ly.LT + (size_t)(16 * it0 + c) * a.ld + 4 * g;
   const float* bp = Ly.RT + (size_t)(16 * ot0 + c) * a.ld + 4 * g;
-  // panel slices of the next WG_PF 16-row steps are in flight while a step's MFMAs run; the steps
-  // are summed in row order whatever the depth
-  float4 As[WG_PF][NI], Bs[WG_PF][NO];
-  auto fetch = [&](float4 (&An)[NI], float4 (&Bn)[NO], int r) {
+  // the panel slices of the next 16-row step are in flight while a step's MFMAs run (one step: a
+  // deeper prefetch cost the GEMM its 4 waves per SIMD beside the chains); the steps are
+  // summed in row order
+  float4 An[NI], Bn[NO];
+  auto fetch = [&](int r) {
     const int rr = min(r, r1 - 16);  // clamped (branch-free); a past-the-end fetch is unused
 #pragma unroll
     for (int i = 0; i < NI; ++i) An[i] = *reinterpret_cast<const float4*>(ap + (size_t)16 * min(i, ni - 1) * a.ld + rr);
@@ -176,23 +173,15 @@ __device__ __forceinline__ void wg_block(const WgArgs& a, const WgLayer& Ly, int
 #pragma unroll
       for (int o = 0; o < NO; ++o) acc[i][o] = mfma4(A[i].w, Bv[o].w, acc[i][o]);
   };
-  if (r0 < r1) {
+  if (r0 < r1) fetch(r0);
+  for (int r = r0; r < r1; r += 16) {
+    float4 A[NI], Bv[NO];
 #pragma unroll
-    for (int d = 0; d < WG_PF; ++d) fetch(As[d], Bs[d], r0 + 16 * d);
-  }
-  for (int r = r0; r < r1; r += 16 * WG_PF) {
+    for (int i = 0; i < NI; ++i) A[i] = An[i];
 #pragma unroll
-    for (int d = 0; d < WG_PF; ++d) {
-      if (r + 16 * d < r1) {
-        float4 A[NI], Bv[NO];
-#pragma unroll
-        for (int i = 0; i < NI; ++i) A[i] = As[d][i];
-#pragma unroll
-        for (int o = 0; o < NO; ++o) Bv[o] = Bs[d][o];
-        fetch(As[d], Bs[d], r + 16 * (d + WG_PF));
-        step(A, Bv);
-      }
-    }
+    for (int o = 0; o < NO; ++o) Bv[o] = Bn[o];
+    fetch(r + 16);
+    step(A, Bv);
   }
   constexpr int NT = NI * NO, HT = NT < 8 ? NT : 8;  // tiles, tiles per round
   constexpr int NR = (NT + HT - 1) / HT;
@@ -227,12 +216,74 @@ __device__ __forceinline__ void wg_block(const WgArgs& a, const WgLayer& Ly, int
   }
 }
 
-//
-// xcd = 1: the items of one chunk run on blocks that share an XCD (blocks b and b + 8 are dealt to
-// one; observed dealing, so it decides only which L2 serves a re-read): chunk (b / 8 / tpc) * 8 +
-// b % 8, item (b / 8) % tpc. The 4 (resp. nbi) blocks that read one LT (RT) slice then read it from
-// one L2 instead of up to four; the grid is padded to whole groups of 8 chunks.
-//
+// One split-K item, decoded (k_wgrad and k_wgrad_big share the items; each deals its workgroups to
+// (chunk, item) its own way — the WgDeal): a block of ni x no (<= 4 x 4) output tiles of layer l from
+// tile (it0, ot0), or, with ni == 0, the group of up to 4 bias tiles from tile ot0 (one per wave);
+// over the rows [lo, hi) of the chunk, into the chunk's slab `out`.
+struct WgDeal {
+  int chunk, item;  // chunk < 0: a padding workgroup of the grid
+};
+struct WgItem {
+  int l, it0, ot0, ni, no, lo, hi;
+  float* out;
+};
+__device__ __forceinline__ WgItem wg_item(const WgArgs& a, float* __restrict__ slab, const WgDeal d) {
+  WgItem w;
+  int rem = d.item;
+  w.l = 0;
+  while (rem >= a.toff[w.l + 1]) ++w.l;
+  const WgLayer& Ly = a.l[w.l];
+  rem -= a.toff[w.l];
+  w.lo = a.r_begin + d.chunk * a.CH;
+  w.hi = min(a.r_end, w.lo + a.CH);
+  w.out = slab + (size_t)d.chunk * a.P;
+  const int nbi = (Ly.IT + WG_BLK - 1) / WG_BLK, nbo = (Ly.OT + WG_BLK - 1) / WG_BLK;
+  if (rem < nbi * nbo) {
+    w.it0 = (rem / nbo) * WG_BLK, w.ot0 = (rem % nbo) * WG_BLK;
+    w.ni = min(WG_BLK, Ly.IT - w.it0), w.no = min(WG_BLK, Ly.OT - w.ot0);
+  } else {
+    w.it0 = w.ni = w.no = 0;
+    w.ot0 = (rem - nbi * nbo) * WG_BLK;
+  }
+  return w;
+}
+
+// One wave's bias tile `ot` of a layer over the rows of [lo, hi) from bias_r0 on: 64-row groups (4
+// loads in flight) then 16-row steps, summed in row order, then over the 4 row groups of the lanes.
+__device__ __forceinline__ void wg_bias_tile(const WgArgs& a, const WgLayer& Ly, int ot, int lo, int hi,
+                                             float* __restrict__ out) {
+  const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
+  if (ot >= Ly.OT) return;
+  const float* bp = Ly.RT + (size_t)(16 * ot + c) * a.ld + 4 * g;
+  float s = 0.f;
+  int r = max(lo, a.bias_r0);
+  for (; r + 64 <= hi; r += 64) {
+    float4 v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = *reinterpret_cast<const float4*>(bp + r + 16 * k);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
+  }
+  for (; r < hi; r += 16) {
+    const float4 v = *reinterpret_cast<const float4*>(bp + r);
+    s += (v.x + v.y) + (v.z + v.w);
+  }
+  s += __shfl_xor(s, 16);
+  s += __shfl_xor(s, 32);
+  if (g == 0 && 16 * ot + c < Ly.out) out[Ly.boff + 16 * ot + c] = s;
+}
+
+// k_wgrad's deal. xcd = 0: chunk-major (the small batches of cacto_critic_grad / cacto_actor_grad).
+// xcd = 1 (from 8 chunks on): the items of one chunk run on blocks that share an XCD (blocks b and
+// b + 8 are dealt to one; observed dealing, so it decides only which L2 serves a re-read): chunk
+// (b / 8 / tpc) * 8 + b % 8, item (b / 8) % tpc. The 4 (resp. nbi) blocks that read one LT (RT) slice
+// then read it from one L2 instead of up to four; the grid is padded to whole groups of 8 chunks.
+__device__ __forceinline__ WgDeal wg_deal(const WgArgs& a, int blk, int xcd) {
+  if (!xcd) return WgDeal{blk / a.tpc, blk % a.tpc};
+  const int sl = blk >> 3, chunk = (sl / a.tpc) * 8 + (blk & 7);
+  return WgDeal{chunk < a.nch ? chunk : -1, sl % a.tpc};
+}
+
 // sig_p (the pipeline's device-side ordering): this launch follows the actor chain of an iteration
 // on its stream, so that chain has finished; block 0 publishes sig_v = (iterations done) for the
 // critic stream's Adam, which must not overwrite a critic buffer the chain read (k_adam's wait_p).
@@ -243,55 +294,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))
   __shared__ float4 part[4 * (WG_BLK * WG_BLK / 2) * 64];
   if (sig_p && blockIdx.x == 0 && threadIdx.x == 0)  // write-after-read order only: relaxed
     __hip_atomic_store(sig_p, sig_v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  int chunk, rem;
-  if (xcd) {
-    const int sl = blockIdx.x >> 3;
-    chunk = (sl / a.tpc) * 8 + (blockIdx.x & 7);
-    rem = sl % a.tpc;
-    if (chunk >= a.nch) return;
-  } else {
-    chunk = blockIdx.x / a.tpc;
-    rem = blockIdx.x - chunk * a.tpc;
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
-  int li = 0;
-  while (rem >= a.toff[li + 1]) ++li;
-  const WgLayer& Ly = a.l[li];
-  rem -= a.toff[li];
-  const int lo = a.r_begin + chunk * a.CH, hi = min(a.r_end, lo + a.CH);
-  float* out = slab + (size_t)chunk * a.P;
-  const int nbi = (Ly.IT + WG_BLK - 1) / WG_BLK, nbo = (Ly.OT + WG_BLK - 1) / WG_BLK;
-  if (rem < nbi * nbo) {
-    const int it0 = (rem / nbo) * WG_BLK, ot0 = (rem % nbo) * WG_BLK;
-    const int ni = min(WG_BLK, Ly.IT - it0), no = min(WG_BLK, Ly.OT - ot0);
-    // the block shapes the networks have, compiled for their size (an edge block of the input or
-    // output layer loads and multiplies only its own tiles); any other shape runs the 4 x 4 code
-    // on clamped duplicate tiles (unused)
-    if (ni == WG_BLK && no == WG_BLK) wg_block<WG_BLK, WG_BLK>(a, Ly, lo, hi, it0, ot0, ni, no, out, part);
-    else if (ni == 1 && no == WG_BLK) wg_block<1, WG_BLK>(a, Ly, lo, hi, it0, ot0, ni, no, out, part);
-    else if (ni == WG_BLK && no == 1) wg_block<WG_BLK, 1>(a, Ly, lo, hi, it0, ot0, ni, no, out, part);
-    else wg_block<WG_BLK, WG_BLK>(a, Ly, lo, hi, it0, ot0, ni, no, out, part);
-  } else {
-    const int ot = (rem - nbi * nbo) * WG_BLK + wave;
-    if (ot >= Ly.OT) return;
-    const float* bp = Ly.RT + (size_t)(16 * ot + c) * a.ld + 4 * g;
-    float s = 0.f;
-    int r = max(lo, a.bias_r0);
-    for (; r + 64 <= hi; r += 64) {  // 4 loads in flight, summed in row order
-      float4 v[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] = *reinterpret_cast<const float4*>(bp + r + 16 * k);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
-    }
-    for (; r < hi; r += 16) {
-      const float4 v = *reinterpret_cast<const float4*>(bp + r);
-      s += (v.x + v.y) + (v.z + v.w);
-    }
-    s += __shfl_xor(s, 16);
-    s += __shfl_xor(s, 32);
-    if (g == 0 && 16 * ot + c < Ly.out) out[Ly.boff + 16 * ot + c] = s;
-  }
+  const WgDeal d = wg_deal(a, blockIdx.x, xcd);
+  if (d.chunk < 0) return;
+  const WgItem w = wg_item(a, slab, d);
+  const WgLayer& Ly = a.l[w.l];
+  if (w.ni == 0) return wg_bias_tile(a, Ly, w.ot0 + (threadIdx.x >> 6), w.lo, w.hi, w.out);
+  // the block shapes the networks have, compiled for their size (an edge block of the input or
+  // output layer loads and multiplies only its own tiles); any other shape runs the 4 x 4 code
+  // on clamped duplicate tiles (unused)
+  if (w.ni == 1 && w.no == WG_BLK) wg_block<1, WG_BLK>(a, Ly, w.lo, w.hi, w.it0, w.ot0, w.ni, w.no, w.out, part);
+  else if (w.ni == WG_BLK && w.no == 1) wg_block<WG_BLK, 1>(a, Ly, w.lo, w.hi, w.it0, w.ot0, w.ni, w.no, w.out, part);
+  else wg_block<WG_BLK, WG_BLK>(a, Ly, w.lo, w.hi, w.it0, w.ot0, w.ni, w.no, w.out, part);
 }
 
 // ---------------------------------------------------------------- weight-gradient GEMM, large batches
@@ -404,69 +417,38 @@ __device__ __forceinline__ void wgb_block(const int ld, const WgLayer Ly, int lo
   }
 }
 
-//
-// Grid order: block b runs on XCD b % 8 (observed dealing), which owns chunks x, x + 8, ...; its j-th
-// block (j = b / 8) takes item perm[j / cpx] of its chunk j % cpx — every XCD starts with the full
-// 4 x 4 blocks of all its chunks, one per CU, before the lighter items fill in (with the work dealt
-// chunk-major, two heavy items could share a CU's matrix cores while others idled).
-__device__ __forceinline__ void wgrad_big_body(const int blk, const WgArgs& a, float* __restrict__ slab, int xcd,
+// k_wgrad_big's deal (it always has 9 chunks or more): block b runs on XCD b % 8 (observed dealing),
+// which owns chunks x, x + 8, ...; its j-th block (j = b / 8) takes item perm[j / cpx] of its chunk
+// j % cpx — every XCD starts with the full 4 x 4 blocks of all its chunks, one per CU, before the
+// lighter items fill in (with the work dealt chunk-major, two heavy items could share a CU's matrix
+// cores while others idled). The grid is padded to whole groups of 8 chunks.
+__device__ __forceinline__ WgDeal wgb_deal(const WgArgs& a, int blk) {
+  const int j = blk >> 3, cpx = (a.nch + 7) >> 3;
+  const int pi = j / cpx, chunk = (j - pi * cpx) * 8 + (blk & 7);
+  if (chunk >= a.nch || pi >= a.tpc) return WgDeal{-1, 0};
+  return WgDeal{chunk, a.perm[pi]};
+}
+
+__device__ __forceinline__ void wgrad_big_body(const int blk, const WgArgs& a, float* __restrict__ slab,
                                                unsigned long long* sig_p, unsigned long long sig_v, float* stage) {
   if (sig_p && blk == 0 && threadIdx.x == 0)  // write-after-read order only: relaxed
     __hip_atomic_store(sig_p, sig_v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  int chunk, rem;
-  if (xcd) {
-    const int j = blk >> 3, cpx = (a.nch + 7) >> 3;
-    const int pi = j / cpx;
-    chunk = (j - pi * cpx) * 8 + (blk & 7);
-    if (chunk >= a.nch || pi >= a.tpc) return;
-    rem = a.perm[pi];
-  } else {
-    chunk = blk / a.tpc;
-    rem = a.perm[blk - chunk * a.tpc];
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
-  int li = 0;
-  while (rem >= a.toff[li + 1]) ++li;
-  const WgLayer& Ly = a.l[li];
-  rem -= a.toff[li];
-  const int lo = a.r_begin + chunk * a.CH, hi = min(a.r_end, lo + a.CH);
-  float* out = slab + (size_t)chunk * a.P;
-  const int nbi = (Ly.IT + WG_BLK - 1) / WG_BLK, nbo = (Ly.OT + WG_BLK - 1) / WG_BLK;
-  if (rem < nbi * nbo) {
-    const int it0 = (rem / nbo) * WG_BLK, ot0 = (rem % nbo) * WG_BLK;
-    const int ni = min(WG_BLK, Ly.IT - it0), no = min(WG_BLK, Ly.OT - ot0);
-    const WgLayer lv{Ly.LT, Ly.RT, Ly.in, Ly.out, Ly.IT, Ly.OT, Ly.woff, Ly.boff};
-    if (ni == 4 && no == 4) wgb_block<4, 4>(a.ld, lv, lo, hi, it0, ot0, out, stage);
-    else if (ni == 1 && no == 4) wgb_block<1, 4>(a.ld, lv, lo, hi, it0, ot0, out, stage);
-    else if (ni == 4 && no == 1) wgb_block<4, 1>(a.ld, lv, lo, hi, it0, ot0, out, stage);
-    // (the host checks that every block of the network has one of these shapes)
-  } else {
-    const int ot = (rem - nbi * nbo) * WG_BLK + wave;
-    if (ot >= Ly.OT) return;
-    const float* bp = Ly.RT + (size_t)(16 * ot + c) * a.ld + 4 * g;
-    float s = 0.f;
-    int r = max(lo, a.bias_r0);
-    for (; r + 64 <= hi; r += 64) {  // 4 loads in flight, summed in row order
-      float4 v[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] = *reinterpret_cast<const float4*>(bp + r + 16 * k);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
-    }
-    for (; r < hi; r += 16) {
-      const float4 v = *reinterpret_cast<const float4*>(bp + r);
-      s += (v.x + v.y) + (v.z + v.w);
-    }
-    s += __shfl_xor(s, 16);
-    s += __shfl_xor(s, 32);
-    if (g == 0 && 16 * ot + c < Ly.out) out[Ly.boff + 16 * ot + c] = s;
-  }
+  const WgDeal d = wgb_deal(a, blk);
+  if (d.chunk < 0) return;
+  const WgItem w = wg_item(a, slab, d);
+  const WgLayer& Ly = a.l[w.l];
+  if (w.ni == 0) return wg_bias_tile(a, Ly, w.ot0 + (threadIdx.x >> 6), w.lo, w.hi, w.out);
+  const WgLayer lv{Ly.LT, Ly.RT, Ly.in, Ly.out, Ly.IT, Ly.OT, Ly.woff, Ly.boff};
+  if (w.ni == 4 && w.no == 4) wgb_block<4, 4>(a.ld, lv, w.lo, w.hi, w.it0, w.ot0, w.out, stage);
+  else if (w.ni == 1 && w.no == 4) wgb_block<1, 4>(a.ld, lv, w.lo, w.hi, w.it0, w.ot0, w.out, stage);
+  else if (w.ni == 4 && w.no == 1) wgb_block<4, 1>(a.ld, lv, w.lo, w.hi, w.it0, w.ot0, w.out, stage);
+  // (the route takes this kernel only when every block of the network has one of these shapes)
 }
 
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) k_wgrad_big(WgArgs a, float* __restrict__ slab, int xcd,
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) k_wgrad_big(WgArgs a, float* __restrict__ slab,
                                                    unsigned long long* sig_p, unsigned long long sig_v) {
   __shared__ __attribute__((aligned(16))) float stage[2 * WGB_STAGE];  // 20 KiB
-  wgrad_big_body(blockIdx.x, a, slab, xcd, sig_p, sig_v, stage);
+  wgrad_big_body(blockIdx.x, a, slab, sig_p, sig_v, stage);
 }
 
 // The pipelined PER loop's critic GEMM with the priority update of the same update in one grid:
@@ -475,22 +457,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))
 // sample needs both (the trees, and this stream's order). LDS: the GEMM's 20 KiB ring, the priority
 // update's 10 KiB in the same bytes.
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8)))
-k_wgrad_big_per(WgArgs a, float* __restrict__ slab, int xcd, int nwg, PerRunArgs pa, int nroot) {
+k_wgrad_big_per(WgArgs a, float* __restrict__ slab, int nwg, PerRunArgs pa, int nroot) {
   static_assert(sizeof(PerRunLds) <= 2 * WGB_STAGE * sizeof(float), "LDS union");
   __shared__ __attribute__((aligned(16))) float stage[2 * WGB_STAGE];  // 20 KiB
-  if ((int)blockIdx.x < nwg) wgrad_big_body(blockIdx.x, a, slab, xcd, nullptr, 0, stage);
+  if ((int)blockIdx.x < nwg) wgrad_big_body(blockIdx.x, a, slab, nullptr, 0, stage);
   else per_update_run_body(blockIdx.x - nwg, nroot, pa, *reinterpret_cast<PerRunLds*>(stage));
 }
 
 // ---------------------------------------------------------------- Adam (+ packed refresh, soft update)
-// write_packed for a weight W_l[i][o] whose layer and indices are known (no search, no division)
-__device__ __forceinline__ void write_packed_w(float4* pk4, const NetTopo& t, int l, int i, int o, float val) {
-  float* pk = reinterpret_cast<float*>(pk4);
-  pk[((size_t)(t.pkoff[l] + (o >> 4) * t.KT[l] + (i >> 4)) * 64 + ((i & 15) >> 2) * 16 + (o & 15)) * 4 + (i & 3)] = val;
-  pk[((size_t)(t.blocks + t.pkoff[l] + (i >> 4) * t.OT[l] + (o >> 4)) * 64 + ((o & 15) >> 2) * 16 + (i & 15)) * 4 +
-     (o & 3)] = val;
-}
-
 // thru: the store written through to memory at agent scope (a relaxed atomic store), for a reader
 // on another stream that orders itself by a device-side flag instead of a kernel boundary
 __device__ __forceinline__ void store_f(float* p, float v, bool thru) {
@@ -498,18 +472,26 @@ __device__ __forceinline__ void store_f(float* p, float v, bool thru) {
   else *p = v;
 }
 
-__device__ __forceinline__ void write_packed(float4* pk4, const NetTopo& t, int p, float val, bool thru = false) {
+// The two packed copies of a weight W_l[i][o] whose layer and indices are known (no search, no
+// division): the pk block (o tile, i tile) and the pkT block (i tile, o tile).
+__device__ __forceinline__ void write_packed_w(float4* pk4, const NetTopo& t, int l, int i, int o, float val,
+                                               bool thru = false) {
   float* pk = reinterpret_cast<float*>(pk4);
-  int l = t.L - 1;
-  while (t.woff[l] > p) --l;
-  if (p >= t.boff[l]) return;
-  const int local = p - t.woff[l];
-  const int i = local / t.out[l], o = local - (local / t.out[l]) * t.out[l];
   store_f(pk + ((size_t)(t.pkoff[l] + (o >> 4) * t.KT[l] + (i >> 4)) * 64 + ((i & 15) >> 2) * 16 + (o & 15)) * 4 + (i & 3),
           val, thru);
   store_f(pk + ((size_t)(t.blocks + t.pkoff[l] + (i >> 4) * t.OT[l] + (o >> 4)) * 64 + ((o & 15) >> 2) * 16 + (i & 15)) * 4 +
               (o & 3),
           val, thru);
+}
+
+// ... of the Keras-flat parameter p: its layer searched for, nothing for a bias
+__device__ __forceinline__ void write_packed(float4* pk4, const NetTopo& t, int p, float val, bool thru = false) {
+  int l = t.L - 1;
+  while (t.woff[l] > p) --l;
+  if (p >= t.boff[l]) return;
+  const int local = p - t.woff[l];
+  const int i = local / t.out[l], o = local - (local / t.out[l]) * t.out[l];
+  write_packed_w(pk4, t, l, i, o, val, thru);
 }
 
 struct AdamScalars {
@@ -536,6 +518,52 @@ __device__ __forceinline__ AdamScalars adam_scalars(const AdamArgs& a, const int
   s.omt = (float)(1.0 - a.tau);
   return s;
 }
+
+// The Adam step of one parameter (Keras), values only: gradient g; m, v and the weight th stepped in
+// place; tg: the target's value in, its soft update against the new weight out (unused without one).
+// The one place this arithmetic is written: every Adam kernel calls it, so the split, fused and
+// data-parallel paths agree bit for bit.
+__device__ __forceinline__ void adam_math(const AdamScalars& s, float g, float& mm, float& vv, float& th, float& tg) {
+  mm = fadd(mm, fmul(fsub(g, mm), s.c1));
+  vv = fadd(vv, fmul(fsub(fmul(g, g), vv), s.c2));
+  th = fsub(th, fdiv(fmul(mm, s.alpha), fadd(__fsqrt_rn(vv), s.eps)));
+  tg = fadd(fmul(th, s.tau), fmul(tg, s.omt));
+}
+
+// ... and of parameter p of the split path (k_adam, k_adam_sample) with its stores: m, v, the weight
+// and its packed copies (thru: written through), the target and its packed copies with `soft`
+__device__ __forceinline__ void adam_param(const AdamScalars& s, const NetTopo& t, int p, float g, float mm, float vv,
+                                           float th, float tg, float* netbuf, float4* packed, float* __restrict__ m,
+                                           float* __restrict__ v, bool soft, float* target, float4* target_packed,
+                                           bool thru) {
+  adam_math(s, g, mm, vv, th, tg);
+  m[p] = mm;
+  v[p] = vv;
+  store_f(netbuf + p, th, thru);
+  write_packed(packed, t, p, th, thru);
+  if (soft) {
+    target[p] = tg;
+    write_packed(target_packed, t, p, tg);
+  }
+}
+
+// The NCH chunk partials of parameter pc (of P) loaded at once (clamped to the nch that exist,
+// branch-free), then summed in chunk order: g = q[0]; g += q[k] — the order of every chunk sum here.
+template <int NCH>
+struct ChunkPartials {
+  float q[NCH];
+  __device__ __forceinline__ void load(const float* __restrict__ slab, int nch, int P, int pc) {
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) q[k] = slab[(size_t)min(k, nch - 1) * P + pc];
+  }
+  __device__ __forceinline__ float sum(int nch) const {
+    float g = q[0];
+#pragma unroll
+    for (int k = 1; k < NCH; ++k)
+      if (k < nch) g += q[k];
+    return g;
+  }
+};
 
 // NCH > 0: every chunk partial of a parameter is loaded at once (clamped, branch-free) together with
 // m, v, the weight and the target value, so a thread waits for one memory latency instead of one per
@@ -571,34 +599,14 @@ __device__ __forceinline__ void adam_nch_body(const int blk, const float* __rest
                                               float* target, float4* target_packed, const unsigned long long* wait_p,
                                               unsigned long long wait_v, bool thru = false) {
   const int p0 = blk * 256 + threadIdx.x;
-  float q[NCH], mm = 0.f, vv = 0.f, th0 = 0.f, tg0 = 0.f;
   const int pc = min(p0, t.params - 1);
-#pragma unroll
-  for (int k = 0; k < NCH; ++k) q[k] = slab[(size_t)min(k, nch - 1) * t.params + pc];
-  mm = m[pc];
-  vv = v[pc];
-  th0 = src[pc];
-  if (a.soft) tg0 = target[pc];
+  ChunkPartials<NCH> q;
+  q.load(slab, nch, t.params, pc);
+  const float mm = m[pc], vv = v[pc], th = src[pc], tg = a.soft ? target[pc] : 0.f;
   const AdamScalars s = adam_scalars(a, step);
   pipe_wait(wait_p, wait_v, const_cast<unsigned long long*>(wait_p) + 1);  // the loads above are in flight
-  if (p0 < t.params) {
-    float g = q[0];
-#pragma unroll
-    for (int k = 1; k < NCH; ++k)
-      if (k < nch) g += q[k];
-    mm = fadd(mm, fmul(fsub(g, mm), s.c1));
-    vv = fadd(vv, fmul(fsub(fmul(g, g), vv), s.c2));
-    const float th = fsub(th0, fdiv(fmul(mm, s.alpha), fadd(__fsqrt_rn(vv), s.eps)));
-    m[p0] = mm;
-    v[p0] = vv;
-    store_f(netbuf + p0, th, thru);
-    write_packed(packed, t, p0, th, thru);
-    if (a.soft) {
-      const float tg = fadd(fmul(th, s.tau), fmul(tg0, s.omt));
-      target[p0] = tg;
-      write_packed(target_packed, t, p0, tg);
-    }
-  }
+  if (p0 < t.params)
+    adam_param(s, t, p0, q.sum(nch), mm, vv, th, tg, netbuf, packed, m, v, a.soft, target, target_packed, thru);
 }
 
 // The pipelined PER loop's critic Adam step with the next update's sample in one grid: blocks
@@ -636,19 +644,7 @@ __global__ void __launch_bounds__(256) k_adam(const float* __restrict__ slab, in
     adam_publish_thru(sig_p, sig_v, gridDim.x);  // (sig_p only with write-through stores)
     return;
   }
-  const int it = step[a.which];  // = Keras iterations + 1
-  const int iters = it - 1;
-  double lr = a.lr[4];
-  for (int k = 0; k < 4; ++k)
-    if ((double)iters <= a.bounds[k]) {
-      lr = a.lr[k];
-      break;
-    }
-  const float tf = (float)it;
-  const float b1p = powf((float)a.beta1, tf), b2p = powf((float)a.beta2, tf);
-  const float alpha = fdiv(fmul((float)lr, __fsqrt_rn(fsub(1.f, b2p))), fsub(1.f, b1p));
-  const float c1 = (float)(1.0 - a.beta1), c2 = (float)(1.0 - a.beta2), eps = (float)a.eps;
-  const float tau = (float)a.tau, omt = (float)(1.0 - a.tau);
+  const AdamScalars s = adam_scalars(a, step);
   pipe_wait(wait_p, wait_v, const_cast<unsigned long long*>(wait_p) + 1);
   for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < t.params; p += gridDim.x * blockDim.x) {
     // chunk partials summed in chunk order; loads issued 8 at a time so they overlap
@@ -662,19 +658,8 @@ __global__ void __launch_bounds__(256) k_adam(const float* __restrict__ slab, in
       for (int k = 0; k < 8; ++k) g += q[k];
     }
     for (; ch < nch; ++ch) g += slab[(size_t)ch * t.params + p];
-    float mm = m[p], vv = v[p];
-    mm = fadd(mm, fmul(fsub(g, mm), c1));
-    vv = fadd(vv, fmul(fsub(fmul(g, g), vv), c2));
-    const float th = fsub(src[p], fdiv(fmul(mm, alpha), fadd(__fsqrt_rn(vv), eps)));
-    m[p] = mm;
-    v[p] = vv;
-    store_f(netbuf + p, th, thru != 0);
-    write_packed(packed, t, p, th, thru != 0);
-    if (a.soft) {
-      const float tg = fadd(fmul(th, tau), fmul(target[p], omt));
-      target[p] = tg;
-      write_packed(target_packed, t, p, tg);
-    }
+    adam_param(s, t, p, g, m[p], v[p], src[p], a.soft ? target[p] : 0.f, netbuf, packed, m, v, a.soft, target,
+               target_packed, thru != 0);
   }
   adam_publish_thru(sig_p, sig_v, gridDim.x);
 }
@@ -698,15 +683,9 @@ template <int NCH>
 __global__ void __launch_bounds__(256) k_reduce(const float* __restrict__ slab, int nch, int P, float* __restrict__ out) {
   if constexpr (NCH > 0) {
     const int p = blockIdx.x * 256 + threadIdx.x;
-    const int pc = min(p, P - 1);
-    float q[NCH];
-#pragma unroll
-    for (int k = 0; k < NCH; ++k) q[k] = slab[(size_t)min(k, nch - 1) * P + pc];
-    float g = q[0];
-#pragma unroll
-    for (int k = 1; k < NCH; ++k)
-      if (k < nch) g += q[k];
-    if (p < P) out[p] = g;
+    ChunkPartials<NCH> q;
+    q.load(slab, nch, P, min(p, P - 1));
+    if (p < P) out[p] = q.sum(nch);
     return;
   }
   for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x) {
@@ -716,18 +695,25 @@ __global__ void __launch_bounds__(256) k_reduce(const float* __restrict__ slab, 
   }
 }
 
+// The <NCH> instance of k_adam / k_adam_sample / k_reduce that sums nch chunks: the smallest of 8, 16,
+// 32, 64 that holds them (one parameter per thread, a grid of `full` workgroups), else 0 (the looped
+// form on at most 1024 workgroups). go(integral_constant<NCH>, grid).
+int nch_instance(int nch) { return nch <= 8 ? 8 : nch <= 16 ? 16 : nch <= 32 ? 32 : nch <= 64 ? 64 : 0; }
+template <class Go>
+static void nch_dispatch(int nch, int full, Go&& go) {
+  switch (nch_instance(nch)) {
+    case 8: return go(std::integral_constant<int, 8>{}, full);
+    case 16: return go(std::integral_constant<int, 16>{}, full);
+    case 32: return go(std::integral_constant<int, 32>{}, full);
+    case 64: return go(std::integral_constant<int, 64>{}, full);
+    default: return go(std::integral_constant<int, 0>{}, std::min(full, 1024));
+  }
+}
+
 int launch_reduce(const float* slab, int nch, int P, float* out, hipStream_t st) {
-  const int full = (P + 255) / 256;
-  if (nch <= 8)
-    hipLaunchKernelGGL(k_reduce<8>, dim3(full), dim3(256), 0, st, slab, nch, P, out);
-  else if (nch <= 16)
-    hipLaunchKernelGGL(k_reduce<16>, dim3(full), dim3(256), 0, st, slab, nch, P, out);
-  else if (nch <= 32)
-    hipLaunchKernelGGL(k_reduce<32>, dim3(full), dim3(256), 0, st, slab, nch, P, out);
-  else if (nch <= 64)
-    hipLaunchKernelGGL(k_reduce<64>, dim3(full), dim3(256), 0, st, slab, nch, P, out);
-  else
-    hipLaunchKernelGGL(k_reduce<0>, dim3(std::min(full, 1024)), dim3(256), 0, st, slab, nch, P, out);
+  nch_dispatch(nch, (P + 255) / 256, [&](auto n, int grid) {
+    hipLaunchKernelGGL(k_reduce<decltype(n)::value>, dim3(grid), dim3(256), 0, st, slab, nch, P, out);
+  });
   CACTO_CHECK_HIP(hipGetLastError());
   return CACTO_OK;
 }
@@ -741,27 +727,16 @@ int launch_reduce(const float* slab, int nch, int P, float* out, hipStream_t st)
 // reduced ((p0 + p1) + p2) + p3; bias: 64-row groups, then shuffles over g) followed by k_adam's
 // chunk order, so results are bit-identical to the split path.
 
-// k_adam's per-parameter arithmetic (same ops, same order), values only
-__device__ __forceinline__ void adam_math(const AdamScalars& s, float g, float& mm, float& vv, float& th, float& tg) {
-  mm = fadd(mm, fmul(fsub(g, mm), s.c1));
-  vv = fadd(vv, fmul(fsub(fmul(g, g), vv), s.c2));
-  th = fsub(th, fdiv(fmul(mm, s.alpha), fadd(__fsqrt_rn(vv), s.eps)));
-  tg = fadd(fmul(th, s.tau), fmul(tg, s.omt));
-}
-
-// k_adam's per-parameter arithmetic (same ops, same order); l >= 0: a weight W_l[i][o] (direct
-// packed writes), l < 0: a bias (not packed)
+// One parameter's step with its stores; l >= 0: a weight W_l[i][o] (direct packed writes), l < 0: a
+// bias (not packed)
 __device__ __forceinline__ void adam_apply(const AdamNet& N, const AdamScalars& s, int p, float g, float mm, float vv,
-                                           float th0, float tg0, int l, int i, int o) {
-  mm = fadd(mm, fmul(fsub(g, mm), s.c1));
-  vv = fadd(vv, fmul(fsub(fmul(g, g), vv), s.c2));
-  const float th = fsub(th0, fdiv(fmul(mm, s.alpha), fadd(__fsqrt_rn(vv), s.eps)));
+                                           float th, float tg, int l, int i, int o) {
+  adam_math(s, g, mm, vv, th, tg);
   N.m[p] = mm;
   N.v[p] = vv;
   N.nb[p] = th;
   if (l >= 0) write_packed_w(N.pk, N.t, l, i, o, th);
   if (N.target) {
-    const float tg = fadd(fmul(th, s.tau), fmul(tg0, s.omt));
     N.target[p] = tg;
     if (l >= 0) write_packed_w(N.tpk, N.t, l, i, o, tg);
   }
@@ -772,6 +747,40 @@ __device__ __forceinline__ void adam_apply(const AdamNet& N, const AdamScalars& 
 // them in chunk order and runs the Adam step: the same sums in the same order (bit-identical),
 // with a quarter of the chunk loads and MFMAs on each wave.
 constexpr int WA_MAXCH = 16;  // fused path: <= 1024 rows of 64
+constexpr int WA_CB = WA_MAXCH / 4;  // chunks per wave
+
+// That scheme, for the weight tiles and the bias tiles alike: load(j, lo, hi) issues the loads of the
+// wave's j-th chunk (all WA_CB in flight together), park(j, ch, lo, hi) forms chunk ch's partial and
+// parks it in part[ch]; [lo, hi) are the chunk's rows. After the barrier wave 0 sums the parked
+// partials (wa_chunk_sum).
+template <class Load, class Park>
+__device__ __forceinline__ void wa_chunks(const WgArgs& a, int wave, Load&& load, Park&& park) {
+#pragma unroll
+  for (int j = 0; j < WA_CB; ++j) {
+    const int ch = min(wave + 4 * j, a.nch - 1);
+    const int lo = a.r_begin + ch * a.CH, hi = min(a.r_end, lo + a.CH);
+    if (wave + 4 * j < a.nch) load(j, lo, hi);
+  }
+#pragma unroll
+  for (int j = 0; j < WA_CB; ++j) {
+    const int ch = wave + 4 * j;
+    if (ch < a.nch) {
+      const int lo = a.r_begin + ch * a.CH, hi = min(a.r_end, lo + a.CH);
+      park(j, ch, lo, hi);
+    }
+  }
+  __syncthreads();
+}
+// the lane's NQ values of every chunk's parked partial, summed in chunk order
+template <int NQ>
+__device__ __forceinline__ void wa_chunk_sum(const float* part, int nch, int lane, float (&gs)[NQ]) {
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) gs[q] = part[q * 64 + lane];
+  for (int ch = 1; ch < nch; ++ch)
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) gs[q] += part[ch * 256 + q * 64 + lane];
+}
+
 __device__ __forceinline__ void wgrad_adam_item(const AdamNet& N, int item, int l, const int32_t* __restrict__ step,
                                                 int wave, int lane, float* tr, float* part) {
   const int g = lane >> 4, c = lane & 15;  // l: the item's layer, from the work list (no search)
@@ -828,60 +837,46 @@ __device__ __forceinline__ void wgrad_adam_item(const AdamNet& N, int item, int 
     CSTAMP(5);
 #endif
     // this wave's chunks (ch = wave + 4 j), all their panel loads in flight together
-    constexpr int CB = WA_MAXCH / 4;
     {
-      float4 A[CB][4], Bv[CB][4];
+      float4 A[WA_CB][4], Bv[WA_CB][4];
+      wa_chunks(
+          a, wave,
+          [&](int j, int lo, int hi) {
 #pragma unroll
-      for (int j = 0; j < CB; ++j) {
-        const int ch = min(wave + 4 * j, a.nch - 1);
-        const int lo = a.r_begin + ch * a.CH, hi = min(a.r_end, lo + a.CH);
-        if (wave + 4 * j < a.nch) {
-#pragma unroll
-          for (int w = 0; w < 4; ++w) {
-            const int r = min(lo + 16 * w, hi - 16);  // clamped (branch-free); unused past hi
-            A[j][w] = *reinterpret_cast<const float4*>(ap + r);
-            Bv[j][w] = *reinterpret_cast<const float4*>(bp + r);
-          }
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < CB; ++j) {
-        const int ch = wave + 4 * j;
-        if (ch < a.nch) {
-          const int lo = a.r_begin + ch * a.CH, hi = min(a.r_end, lo + a.CH);
-          floatx4 part4[4];
-#pragma unroll
-          for (int w = 0; w < 4; ++w) {
-            floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-            if (lo + 16 * w < hi) {
-              acc = mfma4(A[j][w].x, Bv[j][w].x, acc);
-              acc = mfma4(A[j][w].y, Bv[j][w].y, acc);
-              acc = mfma4(A[j][w].z, Bv[j][w].z, acc);
-              acc = mfma4(A[j][w].w, Bv[j][w].w, acc);
+            for (int w = 0; w < 4; ++w) {
+              const int r = min(lo + 16 * w, hi - 16);  // clamped (branch-free); unused past hi
+              A[j][w] = *reinterpret_cast<const float4*>(ap + r);
+              Bv[j][w] = *reinterpret_cast<const float4*>(bp + r);
             }
-            part4[w] = acc;
-          }
-          floatx4 s4 = part4[0];
+          },
+          [&](int j, int ch, int lo, int hi) {
+            floatx4 part4[4];
 #pragma unroll
-          for (int w = 1; w < 4; ++w) {
-            s4[0] += part4[w][0];
-            s4[1] += part4[w][1];
-            s4[2] += part4[w][2];
-            s4[3] += part4[w][3];
-          }
+            for (int w = 0; w < 4; ++w) {
+              floatx4 acc = {0.f, 0.f, 0.f, 0.f};
+              if (lo + 16 * w < hi) {
+                acc = mfma4(A[j][w].x, Bv[j][w].x, acc);
+                acc = mfma4(A[j][w].y, Bv[j][w].y, acc);
+                acc = mfma4(A[j][w].z, Bv[j][w].z, acc);
+                acc = mfma4(A[j][w].w, Bv[j][w].w, acc);
+              }
+              part4[w] = acc;
+            }
+            floatx4 s4 = part4[0];
 #pragma unroll
-          for (int q = 0; q < 4; ++q) part[ch * 256 + q * 64 + lane] = s4[q];
-        }
-      }
+            for (int w = 1; w < 4; ++w) {
+              s4[0] += part4[w][0];
+              s4[1] += part4[w][1];
+              s4[2] += part4[w][2];
+              s4[3] += part4[w][3];
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) part[ch * 256 + q * 64 + lane] = s4[q];
+          });
     }
-    __syncthreads();
     if (wave != 0) return;
-    floatx4 gs;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) gs[q] = part[q * 64 + lane];
-    for (int ch = 1; ch < a.nch; ++ch)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) gs[q] += part[ch * 256 + q * 64 + lane];
+    float gs[4];
+    wa_chunk_sum(part, a.nch, lane, gs);
     CSTAMP(2);
 #ifdef CACTO_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // diagnostic: the GEMM's results landed
@@ -939,40 +934,31 @@ __device__ __forceinline__ void wgrad_adam_item(const AdamNet& N, int item, int 
     // per chunk: its (<= 4) 16-row steps from max(lo, bias_r0), summed in row order from 0 — the
     // sequence k_wgrad's 64-row groups and 16-row tail produce — then the shuffles over g; chunks
     // dealt to the waves as for the weight tiles, summed in chunk order by wave 0
-    constexpr int CB = WA_MAXCH / 4;
     {
-      float4 v4[CB][4];
+      float4 v4[WA_CB][4];
+      wa_chunks(
+          a, wave,
+          [&](int j, int lo, int hi) {
+            const int r0 = max(lo, a.bias_r0);
 #pragma unroll
-      for (int j = 0; j < CB; ++j) {
-        const int ch = min(wave + 4 * j, a.nch - 1);
-        const int lo = a.r_begin + ch * a.CH, hi = min(a.r_end, lo + a.CH);
-        const int r0 = max(lo, a.bias_r0);
-        if (wave + 4 * j < a.nch)
+            for (int k = 0; k < 4; ++k) v4[j][k] = *reinterpret_cast<const float4*>(bp + max(0, min(r0 + 16 * k, hi - 16)));
+          },
+          [&](int j, int ch, int lo, int hi) {
+            const int r0 = max(lo, a.bias_r0);
+            float sb = 0.f;
 #pragma unroll
-          for (int k = 0; k < 4; ++k) v4[j][k] = *reinterpret_cast<const float4*>(bp + max(0, min(r0 + 16 * k, hi - 16)));
-      }
-#pragma unroll
-      for (int j = 0; j < CB; ++j) {
-        const int ch = wave + 4 * j;
-        if (ch < a.nch) {
-          const int lo = a.r_begin + ch * a.CH, hi = min(a.r_end, lo + a.CH);
-          const int r0 = max(lo, a.bias_r0);
-          float sb = 0.f;
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            if (r0 + 16 * k < hi) sb += (v4[j][k].x + v4[j][k].y) + (v4[j][k].z + v4[j][k].w);
-          sb += __shfl_xor(sb, 16);
-          sb += __shfl_xor(sb, 32);
-          part[ch * 256 + lane] = sb;
-        }
-      }
+            for (int k = 0; k < 4; ++k)
+              if (r0 + 16 * k < hi) sb += (v4[j][k].x + v4[j][k].y) + (v4[j][k].z + v4[j][k].w);
+            sb += __shfl_xor(sb, 16);
+            sb += __shfl_xor(sb, 32);
+            part[ch * 256 + lane] = sb;
+          });
     }
-    __syncthreads();
     if (wave != 0) return;
-    float gsum = part[lane];
-    for (int ch = 1; ch < a.nch; ++ch) gsum = gsum + part[ch * 256 + lane];
+    float gsum[1];
+    wa_chunk_sum(part, a.nch, lane, gsum);
     const AdamScalars s = adam_scalars(N.ad, step);
-    if (ok) adam_apply(N, s, pp, gsum, mm, vv, th, tg, -1, 0, 0);
+    if (ok) adam_apply(N, s, pp, gsum[0], mm, vv, th, tg, -1, 0, 0);
   }
 }
 
@@ -1019,21 +1005,57 @@ extern "C" int cacto_debug_actor_stamps(unsigned long long* out_h) {
 
 namespace cacto {
 
-// Samples per chain workgroup: 4-sample tiles (chain_q4.h) up to a padded batch of Q4_MAX_BP, so a
-// reference-size batch (64 / 128) spreads over 4x the workgroups; 16-sample tiles above, and at every
-// batch size for the elu critic (elu_kernels.hip has no 4-sample form). A function of the critic's
-// network and the batch only, so every update path of one network and batch size runs the same
-// chain kernels (bit-identical results). CACTO_Q4_MAX_BP overrides the bound (read once; benchmarks).
-int q4_max_bp() {
-  static const int v = [] {
-    const char* e = std::getenv("CACTO_Q4_MAX_BP");
-    return e ? std::atoi(e) : 512;
-  }();
-  return v;
+// k_wgrad_big serves a network when every 4 x 4 tile block of it is 4 x 4, 1 x 4 or 4 x 1 tiles (the
+// configs' networks; not the elu critic's 16/32/256/256)
+static bool wgb_shapes(const NetTopo& t) {
+  for (int l = 0; l < t.L; ++l)
+    for (int i0 = 0; i0 < t.KT[l]; i0 += WG_BLK)
+      for (int o0 = 0; o0 < t.OT[l]; o0 += WG_BLK) {
+        const int ni = std::min(WG_BLK, t.KT[l] - i0), no = std::min(WG_BLK, t.OT[l] - o0);
+        if (!((ni == 4 && (no == 4 || no == 1)) || (ni == 1 && no == 4))) return false;
+      }
+  return true;
 }
-int chain_tile(const NetTopo& critic, int Bp) {
-  return !is_elu_topo(critic) && Bp <= q4_max_bp() ? Q4_TILE : CACTO_TILE;
+
+// The route (learn.h). The rules, each with its measurement in DESIGN §3 / §6:
+//   chain tile   4-sample tiles (chain_q4.h) up to Bp = 512, so a reference-size batch (64 / 128)
+//                spreads over 4x the workgroups; 16-sample tiles above, and always for the elu critic
+//                (elu_kernels.hip has no 4-sample form)
+//   paired       while the critic's 2 Bp rows fit 64-row chunks (2 Bp <= 1024): k_wgrad + k_adam as one
+//                launch (k_wgrad_adam), the critic of update t and the actor of t - 1 as one grid
+//   chunk        short chunks for small batches so the grid still fills the chip; from 4096 rows on
+//                256: k_wgrad_big walks a whole chunk per wave, so longer chunks amortise its fill
+//   k_wgrad_big  above 1024 rows, for the networks it has the block shapes of
+//   xcd          chunks grouped by XCD from 8 chunks on
+//   xcd_tiles    the 16-sample chain tiles dealt to the XCD that k_wgrad_big runs their 256-row chunk
+//                on: whole groups of 128 tiles, both networks on 256-row chunks
+//   pair_xcds    about 8 tiles of the paired q4 grid (2 Bp / 4) per XCD, at most all 8 XCDs
+LearnRoute learn_route(const NetTopo& critic, const NetTopo& actor, bool sobolev, int B, int cus) {
+  LearnRoute r{};
+  r.Bp = (B + 15) / 16 * 16;
+  r.elu = is_elu_topo(critic);
+  r.tile = !r.elu && r.Bp <= 512 ? Q4_TILE : CACTO_TILE;
+  r.paired = 2 * r.Bp <= 1024;
+  auto net = [&](const NetTopo& t, int rows) {
+    NetRoute n{};
+    n.rows = rows;
+    n.chunk = rows <= 1024 ? 64 : rows < 4096 ? 128 : 256;
+    n.nch = ceil_div(rows, n.chunk);
+    n.gemm = r.paired ? WG_FUSED : rows > 1024 && wgb_shapes(t) ? WG_BIG : WG_SPLIT;
+    n.xcd = n.nch >= 8;
+    n.adam_nch = nch_instance(n.nch);
+    return n;
+  };
+  r.critic = net(critic, sobolev ? 2 * r.Bp : r.Bp);
+  r.actor = net(actor, r.Bp);
+  r.xcd_tiles = (r.Bp / CACTO_TILE) % 128 == 0 && r.critic.chunk == 256 && r.actor.chunk == 256;
+  if (r.tile == Q4_TILE)
+    for (r.pair_xcds = 1; r.pair_xcds < 8 && 2 * (r.Bp / Q4_TILE) > 8 * r.pair_xcds;) r.pair_xcds *= 2;
+  r.per_overlap = r.critic.gemm == WG_BIG && r.critic.adam_nch != 0;
+  r.devwait_actor = r.tile == CACTO_TILE && r.Bp / CACTO_TILE <= cus;
+  return r;
 }
+
 int cu_count() {
   static const int cus = [] {
     int dev = 0, v = 0;
@@ -1046,47 +1068,30 @@ int cu_count() {
 }
 template <int NJ>
 struct LaunchActorChain {
-  static int run(const cacto_sys* sys, NetView Ac, NetView C, ChainScalars cs, const double* storage,
-                 const int32_t* idx, int B, GradBufs gb, int32_t* step, hipStream_t st) {
-    const int Bp = (B + 15) / 16 * 16;
-    if (is_elu_topo(C.t)) return launch_actor_chain_elu(sys, Ac, C, cs, storage, idx, B, gb, step, st);
-    if (chain_tile(C.t, Bp) == Q4_TILE)
-      hipLaunchKernelGGL(k_actor_grad_q4<NJ>, dim3(Bp / Q4_TILE), dim3(Q4_THREADS), 0, st, sys->dev, Ac, C, cs,
+  static int run(const cacto_sys* sys, const LearnRoute& r, NetView Ac, NetView C, ChainScalars cs,
+                 const double* storage, const int32_t* idx, int B, GradBufs gb, int32_t* step, hipStream_t st) {
+    if (r.elu) return launch_actor_chain_elu(sys, Ac, C, cs, storage, idx, B, gb, step, st);
+    if (r.tile == Q4_TILE)
+      hipLaunchKernelGGL(k_actor_grad_q4<NJ>, dim3(r.Bp / Q4_TILE), dim3(Q4_THREADS), 0, st, sys->dev, Ac, C, cs,
                          storage, idx, B, gb, step);
     else
-      hipLaunchKernelGGL(k_actor_grad<NJ>, dim3(Bp / 16), dim3(CACTO_THREADS), 0, st, sys->dev, Ac, C, cs, storage, idx,
-                         B, gb, step);
+      hipLaunchKernelGGL(k_actor_grad<NJ>, dim3(r.Bp / 16), dim3(CACTO_THREADS), 0, st, sys->dev, Ac, C, cs, storage,
+                         idx, B, gb, step);
     CACTO_CHECK_HIP(hipGetLastError());
     return CACTO_OK;
   }
 };
 
 // nct: critic tiles (= actor tiles) of the batch's chain tile size
-// XCDs the paired q4 grid of 2 nct tiles runs on (k_chain_pair_q4): about 8 tiles per XCD, at
-// most all 8 XCDs. Measured (updates/s, 1 MI355X): manipulator B = 64 (32 tiles) on 8 XCDs 33.4 k,
-// on 4 36.2 k; UR5 B = 64 24.3 k / 29.1 k; DI B = 128 (64 tiles) on 8 39.4 k, on 4 38.3 k.
-// CACTO_PAIR_XCDS (1, 2, 4 or 8) overrides it (read once; benchmarks).
-inline int pair_xcds(int nct) {
-  static const int forced = [] {
-    const char* e = std::getenv("CACTO_PAIR_XCDS");
-    const int v = e ? std::atoi(e) : 0;
-    return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 0;
-  }();
-  if (forced) return forced;
-  int nx = 1;
-  while (nx < 8 && 2 * nct > 8 * nx) nx *= 2;
-  return nx;
-}
-
 template <int NJ>
 struct LaunchChainPair {
-  static int run(const cacto_sys* sys, NetView C, NetView Tg, NetView Ac, ChainScalars cs, const double* storage,
-                 const int32_t* idx_c, const float* isw, const int32_t* idx_a, int B, GradBufs gbc, GradBufs gba,
-                 float* y, float* V, int32_t* step, hipStream_t st) {
-    const int Bp = gbc.Bp;
-    if (chain_tile(C.t, Bp) == Q4_TILE) {
+  static int run(const cacto_sys* sys, const LearnRoute& r, NetView C, NetView Tg, NetView Ac, ChainScalars cs,
+                 const double* storage, const int32_t* idx_c, const float* isw, const int32_t* idx_a, int B,
+                 GradBufs gbc, GradBufs gba, float* y, float* V, int32_t* step, hipStream_t st) {
+    const int Bp = r.Bp;
+    if (r.tile == Q4_TILE) {
       const int nct = Bp / Q4_TILE;
-      const int nx = pair_xcds(nct);
+      const int nx = r.pair_xcds;
       hipLaunchKernelGGL(k_chain_pair_q4<NJ>, dim3(8 * ceil_div(2 * nct, nx)), dim3(Q4_THREADS), 0, st, sys->dev, C,
                          Tg, Ac, cs, storage, idx_c, isw, idx_a, B, nct, gbc, gba, y, V, step, nx);
     } else {
@@ -1099,35 +1104,16 @@ struct LaunchChainPair {
   }
 };
 
-// Rows per weight-gradient chunk (one slab each): small batches use short chunks so the grid
-// still fills the chip; large ones long chunks so Adam sums few slabs.
-// Row chunk of the split-K weight-gradient GEMM. CACTO_WG_CHUNK overrides it above 1024 rows
-// (read once; benchmarks) — the fused small-batch path always takes 64-row chunks.
-inline int wg_chunk_big() {
-  static const int v = [] {
-    const char* e = std::getenv("CACTO_WG_CHUNK");
-    return e ? std::atoi(e) : 0;
-  }();
-  return v;
-}
-// Row chunk of the weight-gradient GEMM. From 4096 rows on 256-row chunks: k_wgrad_big walks a whole
-// chunk per wave, so longer chunks amortise its pipeline fill (r05, updates/s: DI B = 4096 — the actor's
-// 4096 rows — 12.97 k at 128 rows, 13.25 k at 256; car_park PER B = 4096 10.14 k / 9.86 k; 512 rows
-// 12.49 k); CACTO_WG_CHUNK overrides it above 1024 rows (read once; benchmarks).
-int wg_chunk(int rows) {
-  if (rows > 1024 && wg_chunk_big() > 0) return wg_chunk_big();
-  return rows <= 1024 ? 64 : rows < 4096 ? 128 : 256;
-}
-
-static WgArgs wg_args(const NetTopo& t, const GradBufs& gb, int r_begin, int r_end, int bias_r0) {
+// the GEMM's arguments for a network's n.rows gradient rows, which end at r_end
+static WgArgs wg_args(const NetTopo& t, const GradBufs& gb, const NetRoute& n, int r_end, int bias_r0) {
   WgArgs a{};
   a.nl = t.L;
   a.ld = gb.ld;
-  a.r_begin = r_begin;
+  a.r_begin = r_end - n.rows;
   a.r_end = r_end;
   a.bias_r0 = bias_r0;
-  a.CH = wg_chunk(r_end - r_begin);
-  a.nch = ceil_div(r_end - r_begin, a.CH);
+  a.CH = n.chunk;
+  a.nch = n.nch;
   a.P = t.params;
   int tpc = 0;  // workgroups per chunk: 4x4 tile blocks + groups of 4 bias tiles, per layer
   for (int l = 0; l < t.L; ++l) {
@@ -1150,72 +1136,42 @@ static WgArgs wg_args(const NetTopo& t, const GradBufs& gb, int r_begin, int r_e
   std::stable_sort(cost.begin(), cost.end(), [](const std::pair<int, int>& x, const std::pair<int, int>& y) {
     return x.first < y.first;
   });
-  static const bool perm_on = [] {  // CACTO_WG_PERM=0: chunk-major item order (A/B; read once)
-    const char* e = std::getenv("CACTO_WG_PERM");
-    return !(e && e[0] == '0');
-  }();
-  for (int k = 0; k < 64; ++k) a.perm[k] = k < tpc ? (unsigned char)(perm_on ? cost[k].second : k) : 0;
+  for (int k = 0; k < 64; ++k) a.perm[k] = k < tpc ? (unsigned char)cost[k].second : 0;
   return a;
 }
 
-// k_wgrad_big for more than 1024 gradient rows (B > 512 for the actor, the critic's two halves), when
-// every 4 x 4 tile block of the network is 4 x 4, 1 x 4 or 4 x 1 tiles (all the configs' networks).
-// A function of the network and the row count only, so every path of one batch size takes the same
-// kernel. CACTO_WG_BIG=0 keeps k_wgrad (A/B; read once).
-bool wgrad_big(const NetTopo& t, int rows) {
-  static const bool env_on = [] {
-    const char* e = std::getenv("CACTO_WG_BIG");
-    return !(e && e[0] == '0');
-  }();
-  if (!env_on || rows <= 1024) return false;
-  for (int l = 0; l < t.L; ++l)
-    for (int i0 = 0; i0 < t.KT[l]; i0 += WG_BLK)
-      for (int o0 = 0; o0 < t.OT[l]; o0 += WG_BLK) {
-        const int ni = std::min(WG_BLK, t.KT[l] - i0), no = std::min(WG_BLK, t.OT[l] - o0);
-        if (!((ni == 4 && (no == 4 || no == 1)) || (ni == 1 && no == 4))) return false;
-      }
-  return true;
-}
-
-// the weight-gradient GEMM of one network into its slabs; returns the chunk count k_adam sums
-static int launch_wgrad(const NetTopo& t, const GradBufs& gb, int r_begin, int r_end, int bias_r0, float* slab,
-                        hipStream_t st, int* nch, unsigned long long* sig_p, unsigned long long sig_v,
+// the split weight-gradient GEMM of one network into its n.nch slabs (the kernel of a fused batch's
+// slab form is k_wgrad: its rows fit 64-row chunks)
+static int launch_wgrad(const NetTopo& t, const GradBufs& gb, const NetRoute& n, int r_end, int bias_r0, float* slab,
+                        hipStream_t st, unsigned long long* sig_p, unsigned long long sig_v,
                         const PerRunArgs* per_run) {
-  const WgArgs a = wg_args(t, gb, r_begin, r_end, bias_r0);
-  // chunks grouped by XCD from 8 chunks on (CACTO_WG_XCD=0 / 1 forces it off / on; benchmarks)
-  static const int forced = [] {
-    const char* e = std::getenv("CACTO_WG_XCD");
-    return e ? std::atoi(e) : -1;
-  }();
-  const int xcd = forced >= 0 ? forced : a.nch >= 8;
-  const int grid = xcd ? 8 * ceil_div(a.nch, 8) * a.tpc : a.nch * a.tpc;
-  if (per_run) {  // the PER loop's fused form (the caller checked wgrad_big and the tree's shape)
+  const WgArgs a = wg_args(t, gb, n, r_end, bias_r0);
+  // (k_wgrad_big's rows, more than 1024 in chunks of 128 or 256, make 9 chunks or more: always by XCD)
+  const int grid = n.xcd ? 8 * ceil_div(a.nch, 8) * a.tpc : a.nch * a.tpc;
+  if (per_run) {  // the PER loop's fused form (the caller checked route.per_overlap and the tree's shape)
     const int nroot = (int)(per_run->cap / PER_RUN_SUB);
-    hipLaunchKernelGGL(k_wgrad_big_per, dim3(grid + nroot), dim3(256), 0, st, a, slab, xcd, grid, *per_run, nroot);
-  } else if (wgrad_big(t, r_end - r_begin)) {
-    hipLaunchKernelGGL(k_wgrad_big, dim3(grid), dim3(256), 0, st, a, slab, xcd, sig_p, sig_v);
+    hipLaunchKernelGGL(k_wgrad_big_per, dim3(grid + nroot), dim3(256), 0, st, a, slab, grid, *per_run, nroot);
+  } else if (n.gemm == WG_BIG) {
+    hipLaunchKernelGGL(k_wgrad_big, dim3(grid), dim3(256), 0, st, a, slab, sig_p, sig_v);
   } else {
-    hipLaunchKernelGGL(k_wgrad, dim3(grid), dim3(256), 0, st, a, slab, xcd, sig_p, sig_v);
+    hipLaunchKernelGGL(k_wgrad, dim3(grid), dim3(256), 0, st, a, slab, n.xcd, sig_p, sig_v);
   }
   CACTO_CHECK_HIP(hipGetLastError());
-  *nch = a.nch;
   return CACTO_OK;
 }
 
-// the critic's gradient rows: the Sobolev half [0, Bp) only with w_S != 0, the plain half [Bp, 2 Bp) always
-static int critic_r0(bool sobolev, const Workspace& w) { return sobolev ? 0 : w.Bp; }
-
-int launch_critic_wgrad(const cacto_sys* sys, bool sobolev, const Workspace& w, hipStream_t st,
-                        int* nch, const PerRunArgs* per_run) {
-  return launch_wgrad(sys->critic, w.crit, critic_r0(sobolev, w), 2 * w.Bp, w.Bp, w.slab, st, nch, nullptr, 0, per_run);
+// the critic's gradient rows end at 2 Bp: the plain half [Bp, 2 Bp) always, the Sobolev half [0, Bp)
+// before it with w_S != 0; its biases sum over the plain half
+int launch_critic_wgrad(const cacto_sys* sys, const Workspace& w, hipStream_t st, const PerRunArgs* per_run) {
+  return launch_wgrad(sys->critic, w.crit, w.route.critic, 2 * w.Bp, w.Bp, w.slab, st, nullptr, 0, per_run);
 }
 
-int launch_actor_wgrad(const cacto_sys* sys, const Workspace& w, hipStream_t st, int* nch, unsigned long long* sig_p,
+int launch_actor_wgrad(const cacto_sys* sys, const Workspace& w, hipStream_t st, unsigned long long* sig_p,
                        unsigned long long sig_v) {
-  return launch_wgrad(sys->actor, w.act, 0, w.Bp, 0, w.slab_a, st, nch, sig_p, sig_v, nullptr);
+  return launch_wgrad(sys->actor, w.act, w.route.actor, w.Bp, 0, w.slab_a, st, sig_p, sig_v, nullptr);
 }
 
-ChainScalars chain_scalars(const cacto_update_cfg* cfg, int B) {
+ChainScalars chain_scalars(const cacto_update_cfg* cfg, const LearnRoute& r, int B) {
   ChainScalars cs;
   cs.w_S = (float)cfg->w_S;
   cs.MC = cfg->MC;
@@ -1224,13 +1180,7 @@ ChainScalars chain_scalars(const cacto_update_cfg* cfg, int B) {
   cs.wait_p = nullptr;
   cs.wait_v = 0;
   cs.wait_at_start = 0;
-  // CACTO_CHAIN_XCD=0 keeps the tiles in block order (A/B; read once)
-  static const bool xcd_env = [] {
-    const char* e = std::getenv("CACTO_CHAIN_XCD");
-    return !(e && e[0] == '0');
-  }();
-  const int Bp = (B + 15) / 16 * 16;
-  cs.xcd_tiles = xcd_env && (Bp / CACTO_TILE) % 128 == 0 && wg_chunk(Bp) == 256 && wg_chunk(2 * Bp) == 256;
+  cs.xcd_tiles = r.xcd_tiles;
   return cs;
 }
 
@@ -1253,13 +1203,13 @@ int launch_critic_chain(const cacto_sys* sys, const cacto_nets* nets, const cact
                         float* Vt, const Workspace& w, hipStream_t st) {
   NetView C = cacto_make_view(sys, CACTO_NET_CRITIC, nets->critic_d);
   NetView Tg = cacto_make_view(sys, CACTO_NET_CRITIC, nets->target_d);
-  const ChainScalars cs = chain_scalars(cfg, B);
+  const ChainScalars cs = chain_scalars(cfg, w.route, B);
   float* yb = y ? y : w.scal;
   float* Vb = V ? V : w.scal + w.Bp;
   float* Vtb = Vt ? Vt : w.scal + 2 * w.Bp;
-  if (is_elu_topo(sys->critic))
+  if (w.route.elu)
     return launch_critic_chain_elu(sys, C, Tg, cs, storage, idx, isw, B, w.crit, yb, Vb, Vtb, nets->step_d, st);
-  if (chain_tile(sys->critic, w.Bp) == Q4_TILE)
+  if (w.route.tile == Q4_TILE)
     hipLaunchKernelGGL(k_critic_grad_q4, dim3(w.Bp / Q4_TILE), dim3(Q4_THREADS), 0, st, sys->dev, C, Tg, cs,
                        storage, idx, isw, B, w.crit, yb, Vb, Vtb, nets->step_d);
   else
@@ -1274,11 +1224,11 @@ int launch_actor_chain(const cacto_sys* sys, const cacto_nets* nets, const cacto
                        const unsigned long long* wait_p, unsigned long long wait_v, int wait_at_start) {
   NetView Ac = cacto_make_view(sys, CACTO_NET_ACTOR, nets->actor_d);
   NetView C = cacto_make_view(sys, CACTO_NET_CRITIC, nets->critic_d);
-  ChainScalars cs = chain_scalars(cfg, B);
+  ChainScalars cs = chain_scalars(cfg, w.route, B);
   cs.wait_p = wait_p;
   cs.wait_v = wait_v;
   cs.wait_at_start = wait_at_start;
-  return dispatch_nj<LaunchActorChain>(sys->host.p, sys, Ac, C, cs, storage, idx, B, w.act, nets->step_d, st);
+  return dispatch_nj<LaunchActorChain>(sys->host.p, sys, w.route, Ac, C, cs, storage, idx, B, w.act, nets->step_d, st);
 }
 
 // the critic chain of one update and the actor chain of the one before as one grid (small batches)
@@ -1286,10 +1236,10 @@ int launch_chain_pair(const cacto_sys* sys, const NetView& C, const NetView& Tg,
                       const ChainScalars& cs, const double* storage, const int32_t* idx_c, const float* isw,
                       const int32_t* idx_a, int B, const Workspace& w, float* y, float* V, int32_t* step,
                       hipStream_t st) {
-  if (is_elu_topo(sys->critic))
+  if (w.route.elu)
     return launch_chain_pair_elu(sys, C, Tg, Ac, cs, storage, idx_c, isw, idx_a, B, w.crit, w.act, y, V, step, st);
-  return dispatch_nj<LaunchChainPair>(sys->host.p, sys, C, Tg, Ac, cs, storage, idx_c, isw, idx_a, B, w.crit, w.act, y,
-                                      V, step, st);
+  return dispatch_nj<LaunchChainPair>(sys->host.p, sys, w.route, C, Tg, Ac, cs, storage, idx_c, isw, idx_a, B, w.crit,
+                                      w.act, y, V, step, st);
 }
 
 // src: the weights the step starts from (nullptr = in place; cacto_update_n steps the critic from one
@@ -1306,50 +1256,34 @@ int launch_adam(const cacto_sys* sys, const cacto_nets* nets, const cacto_update
   float4* tpk = reinterpret_cast<float4*>(nets->target_d + flat_span(t));
   const AdamArgs aa = adam_args(cfg, which, soft && which == CACTO_NET_CRITIC);
   const float* s0 = src ? src : nb;
-  // one parameter per thread with all chunk partials in flight (k_adam<NCH>), else the looped kernel
-  const int full = (t.params + 255) / 256;
-  auto go = [&](auto kern, int grid) {
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, slab, nch, t, s0, nb, pk, m, v, nets->step_d, aa,
-                       nets->target_d, tpk, wait_p, wait_v, sig_p, sig_v, thru);
-  };
-  if (sample) {  // the PER loop's fused form (the caller checked nch <= 64)
-    if ((sig_p && !thru) || nch > 64) {
-      set_error("k_adam_sample: a publishing Adam writes through; at most 64 chunks");
-      return CACTO_EINVAL;
-    }
-    const int ns = (sample->B + 255) / 256;
-    auto gs = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(full + ns), dim3(256), 0, st, slab, nch, t, s0, nb, pk, m, v, nets->step_d, aa,
-                         nets->target_d, tpk, wait_p, wait_v, full, *sample, sig_p, sig_v, thru);
-    };
-    if (nch <= 8) gs(k_adam_sample<8>);
-    else if (nch <= 16) gs(k_adam_sample<16>);
-    else if (nch <= 32) gs(k_adam_sample<32>);
-    else gs(k_adam_sample<64>);
-    CACTO_CHECK_HIP(hipGetLastError());
-    return CACTO_OK;
+  if (sample && ((sig_p && !thru) || nch > 64)) {  // the PER loop's fused form (route.per_overlap: nch <= 64)
+    set_error("k_adam_sample: a publishing Adam writes through; at most 64 chunks");
+    return CACTO_EINVAL;
   }
-  if (nch <= 8) go(k_adam<8>, full);
-  else if (nch <= 16) go(k_adam<16>, full);
-  else if (nch <= 32) go(k_adam<32>, full);
-  else if (nch <= 64) go(k_adam<64>, full);
-  else go(k_adam<0>, std::min(full, 1024));
+  // one parameter per thread with all chunk partials in flight (<NCH>), else the looped kernel
+  nch_dispatch(nch, (t.params + 255) / 256, [&](auto n, int grid) {
+    constexpr int NCH = decltype(n)::value;
+    if constexpr (NCH > 0) {
+      if (sample) {
+        const int ns = (sample->B + 255) / 256;
+        hipLaunchKernelGGL(k_adam_sample<NCH>, dim3(grid + ns), dim3(256), 0, st, slab, nch, t, s0, nb, pk, m, v,
+                           nets->step_d, aa, nets->target_d, tpk, wait_p, wait_v, grid, *sample, sig_p, sig_v, thru);
+        return;
+      }
+    }
+    hipLaunchKernelGGL(k_adam<NCH>, dim3(grid), dim3(256), 0, st, slab, nch, t, s0, nb, pk, m, v, nets->step_d, aa,
+                       nets->target_d, tpk, wait_p, wait_v, sig_p, sig_v, thru);
+  });
   CACTO_CHECK_HIP(hipGetLastError());
   return CACTO_OK;
 }
 
-// The fused weight-gradient + Adam launch serves batches whose gradient rows (critic: 2 Bp with the
-// Sobolev half, actor: Bp) all fall in 64-row chunks; larger batches keep k_wgrad's split-K slabs
-// (many workgroups per tile) and k_adam. A function of B only, so every update path of one batch
-// size takes the same kernels (bit-identical results).
-bool fused_adam(int Bp) { return 2 * Bp <= 1024; }
-
 static AdamNet adam_net(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg, int which,
-                        const GradBufs& gb, int r_begin, int r_end, int bias_r0, int soft, const float* src,
+                        const GradBufs& gb, const NetRoute& nr, int r_end, int bias_r0, int soft, const float* src,
                         float* nb) {
   AdamNet n{};
   const NetTopo& t = topo(sys, which);
-  n.wg = wg_args(t, gb, r_begin, r_end, bias_r0);
+  n.wg = wg_args(t, gb, nr, r_end, bias_r0);
   n.t = t;
   n.nb = nb;
   n.src = src ? src : nb;
@@ -1373,19 +1307,19 @@ static AdamNet adam_net(const cacto_sys* sys, const cacto_nets* nets, const cact
 
 AdamNet critic_adam_net(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg, const Workspace& w,
                         int soft, const float* src, float* nb) {
-  return adam_net(sys, nets, cfg, CACTO_NET_CRITIC, w.crit, critic_r0(cfg->w_S != 0.0, w), 2 * w.Bp, w.Bp, soft, src, nb);
+  return adam_net(sys, nets, cfg, CACTO_NET_CRITIC, w.crit, w.route.critic, 2 * w.Bp, w.Bp, soft, src, nb);
 }
 
 AdamNet actor_adam_net(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg, const Workspace& w) {
-  return adam_net(sys, nets, cfg, CACTO_NET_ACTOR, w.act, 0, w.Bp, 0, 0, nullptr, nets->actor_d);
+  return adam_net(sys, nets, cfg, CACTO_NET_ACTOR, w.act, w.route.actor, w.Bp, 0, 0, nullptr, nets->actor_d);
 }
 
 // mode 0: critic alone (n0), 1: actor alone (n0), 2: critic (n0) and actor (n1)
 int launch_wgrad_adam(const cacto_sys* sys, int mode, const AdamNet& n0, const AdamNet* n1, const int32_t* step,
                       hipStream_t st) {
   const int stride = sys->wa_stride[mode];
-  // one item per workgroup (the 4 waves split its chunks); fused_adam keeps every row set within
-  // WA_MAXCH chunks of 64
+  // one item per workgroup (the 4 waves split its chunks); a paired batch's (learn_route) row sets
+  // are within WA_MAXCH chunks of 64
   if (n0.wg.nch > WA_MAXCH || (n1 && n1->wg.nch > WA_MAXCH)) {
     set_error("k_wgrad_adam: more than WA_MAXCH row chunks");
     return CACTO_EINVAL;

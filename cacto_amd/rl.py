@@ -179,6 +179,15 @@ class RL_AC:
             self._ws_B = B
         return self._ws
 
+    def update_plan(self, B):
+        """cacto_update_plan: which kernels the update calls run for a batch of B with this
+        learner's w_S — chain tile, paired or two-stream pipeline, and per network the gradient rows,
+        chunk, chunk count, GEMM kind (0 fused with Adam, 1 k_wgrad, 2 k_wgrad_big), XCD deal and Adam
+        instance; see cacto_upd_plan in the header. Launches nothing."""
+        plan = L.UpdPlan()
+        L.lib().call("cacto_update_plan", self.sys.handle, int(float(self.w_S) != 0.0), int(B), C.byref(plan))
+        return {name: getattr(plan, name) for name, _ in L.UpdPlan._fields_}
+
     def _cfg_for(self, B, want_vt=False):
         """Loss means are over the global batch: B per rank times the data-parallel world."""
         cfg = L.UpdateCfg.from_buffer_copy(self.cfg)

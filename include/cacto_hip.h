@@ -226,6 +226,52 @@ typedef struct {
 /* Bytes of workspace cacto_critic_grad / cacto_actor_grad / cacto_update need for batch B. */
 size_t cacto_workspace_bytes(const cacto_sys* sys, int B);
 
+/* Which kernels the update calls run for a batch of B (the role cacto_rollout_plan plays for the
+ * rollout), decided by the same function every update path reads: a function of the handle's two
+ * networks, of whether the critic's Sobolev half is on (w_S != 0), of B and of the CU count — never of
+ * the process environment. Bp = B rounded up to 16. A network's gradient rows: critic 2 Bp with the
+ * Sobolev half, else Bp; actor Bp.
+ *   chain tile  4 samples per chain workgroup up to Bp = 512, 16 above and always for the elu critic
+ *   paired      2 Bp <= 1024: cacto_update_n[_per] runs one stream with the critic chain of update t
+ *               and the actor chain of t - 1 as one grid, and every update call runs a network's
+ *               weight-gradient GEMM and Adam step as one launch (gemm 0); else two streams, split
+ *   chunk       64 rows up to 1024 rows, 128 below 4096, 256 from there on
+ *   gemm        2 above 1024 rows when every 4 x 4 tile block of the network is 4 x 4, 1 x 4 or
+ *               4 x 1 tiles (not the elu critic), else 1; 0 when paired (cacto_critic_grad,
+ *               cacto_actor_grad and the data-parallel calls keep the slabs: kernel 1 there)
+ *   xcd         the split GEMM's workgroups dealt by XCD: from 8 chunks on
+ *   adam_nch    the smallest of 8, 16, 32, 64 that holds the chunk count, else 0 (looped) */
+typedef struct {
+  int32_t Bp;
+  int32_t chain_tile;      /* samples per chain workgroup: 4 or 16 */
+  int32_t elu;             /* 1: the elu critic's chain kernels */
+  int32_t paired;
+  int32_t critic_rows;
+  int32_t critic_chunk;
+  int32_t critic_nch;      /* chunks = slabs */
+  int32_t critic_gemm;     /* 0 k_wgrad_adam (fused with Adam), 1 k_wgrad, 2 k_wgrad_big */
+  int32_t critic_xcd;
+  int32_t critic_adam_nch; /* the k_adam<NCH> / k_reduce<NCH> instance */
+  int32_t actor_rows;
+  int32_t actor_chunk;
+  int32_t actor_nch;
+  int32_t actor_gemm;
+  int32_t actor_xcd;
+  int32_t actor_adam_nch;
+  int32_t xcd_tiles;       /* 1: the 16-sample chain tiles dealt to the XCD that runs their 256-row GEMM
+                            * chunk (Bp / 16 a multiple of 128, both networks on 256-row chunks) */
+  int32_t pair_xcds;       /* XCDs the paired 4-sample chain grid runs on; 0 above Bp = 512 and for elu */
+  int32_t per_overlap;     /* 1: cacto_update_n_per may run the priority update and the next sample
+                            * inside the critic's GEMM and Adam launches (critic_gemm 2, adam_nch != 0);
+                            * the tree's shape and CACTO_PER_OVERLAP decide the rest */
+  int32_t devwait_actor;   /* 1: the two-stream pipeline may order the actor chain after the critic's
+                            * Adam with a device-side wait (16-sample tiles, Bp / 16 <= cus) */
+  int32_t cus;             /* the compute-unit count the decision used */
+} cacto_upd_plan;
+
+/* sobolev: w_S != 0. CACTO_EINVAL for a null argument or B <= 0; no device work, nothing enqueued. */
+int cacto_update_plan(const cacto_sys* sys, int sobolev, int B, cacto_upd_plan* out);
+
 /* Critic gradient (flat, Keras order, summed over the B local rows with 1/B_global scaling).
  * rows: storage_d indexed by idx_d[B] (int32); is_w_d = IS weights [B] or NULL (= 1).
  * Outputs: grad_d [PC]; y_d [B] (reward_to_go), V_d [B], Vt_d [B] (if cfg->want_target_V). */
