@@ -80,10 +80,19 @@ class UpdPlan(C.Structure):
         "xcd_tiles", "pair_xcds", "per_overlap", "devwait_actor", "cus")]
 
 
+class PerPlan(C.Structure):
+    """struct cacto_per_plan: which PER kernels a batch takes on a tree (cacto_per_plan)."""
+    _fields_ = [(n, C.c_int32) for n in (
+        "sampler", "sampler_top", "sampler_wgs", "count_deferred", "update", "update_sub", "update_roots",
+        "overlap_shape")]
+
+
 RO_KIND_TEAM, RO_KIND_TWO_TEAMS, RO_KIND_WAVE_SLOT = 0, 1, 2
 WG_FUSED, WG_SPLIT, WG_BIG = 0, 1, 2
 CACTO_TO_CONVERGED, CACTO_TO_MAXITER, CACTO_TO_FAILED = 0, 1, 2
 CACTO_TO_PATH_DEFAULT, CACTO_TO_PATH_WAVE = 0, 1
+PER_UPDATE_SET, PER_UPDATE_SUB, PER_UPDATE_CHAIN = 0, 1, 2
+PER_RUN_SUB, PER_RUN_EMPTY = 256, 0x7f7f7f7f
 
 vp, i32, i64, dbl, flt, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_float, C.c_size_t
 _SIGS = {
@@ -155,6 +164,8 @@ _SIGS = {
     "cacto_per_set_range": (C.c_int, [vp, vp, i64, i64, i64, i64, dbl, vp]),
     "cacto_per_set_range_max": (C.c_int, [vp, vp, i64, i64, i64, i64, vp, dbl, vp]),
     "cacto_per_sample": (C.c_int, [vp, vp, i64, i64, dbl, vp, C.c_int, vp, vp, vp, vp]),
+    "cacto_per_plan": (C.c_int, [i64, C.c_int, C.POINTER(PerPlan)]),
+    "cacto_per_sample_runs": (C.c_int, [vp, vp, i64, i64, dbl, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp]),
     "cacto_per_shard_stats": (C.c_int, [vp, vp, i64, vp, vp]),
     "cacto_per_sample_global": (C.c_int, [vp, vp, i64, i64, dbl, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
     "cacto_per_update": (C.c_int, [vp, vp, i64, vp, vp, vp, vp, dbl, dbl, dbl, vp, C.c_int, vp]),

@@ -56,15 +56,18 @@ int cacto_build_wgrad_adam_items(cacto_sys* sys);  // learn_kernels.hip
 // ddp_kernels.hip: the handle's grow-only device workspace (derivative records), at least `bytes`
 int cacto_ddp_workspace(cacto_sys* sys, size_t bytes, double** out);
 void cacto_dp_release(cacto_sys* sys);  // learn_host.hip: the RCCL communicators and buffers
-// replay_kernels.hip: batches from this size on take the multi-workgroup PER kernels; the update
-// pipelines (learn_host.hip) then issue the sample's exp_counter increment just before the priority update (its only
-// reader), off the sample -> critic chain path
-int cacto_per_mw_min();
+// replay_kernels.hip: the one PER route (which sampler and priority update a batch of B takes on a
+// tree of `capacity` leaves, whether the pipelined loops defer the sampler's count into the priority
+// update, whether the tree's shape allows the overlapped form); launches nothing. Reported by
+// cacto_per_plan, whose struct it is.
+namespace cacto {
+using PerRoute = struct ::cacto_per_plan;
+enum { PER_UPDATE_SET = 0, PER_UPDATE_SUB = 1, PER_UPDATE_CHAIN = 2 };
+PerRoute per_route(int64_t capacity, int B);
+}  // namespace cacto
+// ... and the two launches of a deferred count no public entry covers: the count alone, and the
+// priority update with the count applied first
 int cacto_per_count_launch(const int32_t* idx_d, int B, double* exp_counter_d, hipStream_t st);
 int cacto_per_update_count(double* sum_tree_d, double* min_tree_d, int64_t capacity, const int32_t* idx_d,
                            const float* y_d, const float* V_d, double* exp_counter_d, double fresh_factor, double eps,
                            double alpha, double* max_priority_d, int B, hipStream_t st);
-int cacto_per_sample_runs_launch(const double* sum_tree_d, const double* min_tree_d, int64_t capacity, int64_t max_idx,
-                                 double beta, const double* uniforms_d, int B, int32_t* idx_d, float* is_w_d,
-                                 int32_t* runs_d, hipStream_t st, const double* shards_d = nullptr,
-                                 int n_shards = 0);

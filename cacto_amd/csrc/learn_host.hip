@@ -278,20 +278,13 @@ struct PerArgs {
   double *exp_counter, *max_priority;
 };
 
-// Whether the PER loop of this batch can take the overlapped form: the count deferred into the
-// priority update (large batches), a priority update at all (alpha != 0), 256-leaf subtrees whose
-// roots fit one workgroup, and the route's half (the large-batch critic GEMM and an Adam step with
-// all chunks in flight).
-// CACTO_PER_OVERLAP (default 1): the pipelined PER loop's priority update and next sample share the
-// critic GEMM's and Adam's launches (k_wgrad_big_per, k_adam_sample) instead of following them.
+// Whether the PER loop of this batch takes the overlapped form — the priority update and the next
+// sample inside the critic GEMM's and Adam's launches (k_wgrad_big_per, k_adam_sample) instead of
+// following them: the PER route's half (the count deferred, 256-leaf subtrees whose roots fit one
+// workgroup), a priority update at all (alpha != 0), and the update route's half (the large-batch
+// critic GEMM and an Adam step with all chunks in flight).
 bool per_overlap_ok(const PerArgs* per, int B, const Workspace& w) {
-  static const bool on = [] {
-    const char* e = std::getenv("CACTO_PER_OVERLAP");
-    return !(e && e[0] == '0');
-  }();
-  if (!per || !on || B < cacto_per_mw_min() || per->alpha == 0.0) return false;
-  if (per->cap < 2 * PER_RUN_SUB || per->cap > (int64_t)PER_RUN_SUB * PER_RUN_SUB || per->cap % PER_RUN_SUB) return false;
-  return w.route.per_overlap != 0;
+  return per && per_route(per->cap, B).overlap_shape && per->alpha != 0.0 && w.route.per_overlap;
 }
 
 // The priority update of one PER step (RL.py:129-131). late_count: the sampler left its
@@ -327,7 +320,7 @@ int update_pipeline_pair(const cacto_sys* sys, const cacto_nets* nets, const cac
   const NetView Ac = cacto_make_view(sys, CACTO_NET_ACTOR, nets->actor_d);
   const AdamNet cn = critic_adam_net(sys, nets, cfg, w, soft, nullptr, nets->critic_d);
   const AdamNet an = actor_adam_net(sys, nets, cfg, w);
-  const bool late_count = per && B >= cacto_per_mw_min();  // exp_counter += 1 just before the priority update
+  const bool late_count = per && per_route(per->cap, B).count_deferred;  // the count moves to the priority update
   const int32_t* idx_prev = nullptr;
   for (int t = 0; t <= K; ++t) {
     const int32_t* idx = nullptr;
@@ -493,8 +486,8 @@ int per_first_sample(const PerArgs* per, int B, int32_t* pi, const Workspace& w,
   CACTO_CHECK_HIP(hipMemsetAsync(w.runs, 0x7f, (size_t)nroot * sizeof(int32_t), st));
   CACTO_CHECK_HIP(hipMemsetAsync(w.runs + nroot, 0, (size_t)nroot * sizeof(int32_t), st));
   if (int e = gather()) return e;
-  return cacto_per_sample_runs_launch(per->sum_tree, per->min_tree, per->cap, per->max_idx, per->beta, per->uniforms,
-                                      B, pi, w.pisw, w.runs, st, shards, world);
+  return cacto_per_sample_runs(per->sum_tree, per->min_tree, per->cap, per->max_idx, per->beta, per->uniforms, B, pi,
+                               w.pisw, nullptr, w.runs, shards, shards ? world : 0, st);
 }
 // ... and what the critic GEMM's and Adam's launches of update t carry: the priority update of t (idx:
 // its rows; stats: where a data-parallel rank leaves its shard's statistics) and the sample of t + 1
@@ -519,7 +512,7 @@ int update_pipeline_body(const cacto_sys* sys, const cacto_nets* nets, const cac
   float* const buf[3] = {nets->critic_d, w.cshadow, w.cshadow + critic_buf_stride(sys->critic)};
   float* const y = w.scal;
   float* const V = w.scal + w.Bp;
-  const bool late_count = per && B >= cacto_per_mw_min();  // exp_counter += 1 just before the priority update
+  const bool late_count = per && per_route(per->cap, B).count_deferred;  // the count moves to the priority update
   const bool every2 = per != nullptr;  // queue markers (devwait off): marker_wait
   // devwait: the critic stream's ordering against the side stream without queue markers — the
   // actor's GEMM (the launch after each actor chain) publishes the count of finished actor chains on

@@ -208,6 +208,14 @@ class PrioritizedReplayBuffer(ReplayBuffer):
         L.lib().call("cacto_per_set_range", dptr(self.sum_tree), dptr(self.min_tree), self.cap, self.N, start, n,
                      leaf, stream())
 
+    def plan(self, B):
+        """cacto_per_plan: which PER kernels a sample and a priority update of B take on this
+        buffer's tree, as a dict; see struct cacto_per_plan in the header. Launches nothing."""
+        import ctypes as C
+        plan = L.PerPlan()
+        L.lib().call("cacto_per_plan", self.cap, int(B), C.byref(plan))
+        return {name: getattr(plan, name) for name, _ in L.PerPlan._fields_}
+
     def sample_device(self, uniforms=None):
         """_sample_proportional + IS weights + exp_counter (replay_buffer.py:139-188)."""
         if isinstance(uniforms, torch.Tensor):      # device uniforms (e.g. pre-drawn for many steps)

@@ -36,7 +36,8 @@
  *   cacto_rl_solve_add     RL_AC.RL_Solve n-step targets RL.py:145-189 fused with the
  *                          buffer.add of its output (main.py:240)
  *   cacto_per_*            PrioritizedReplayBuffer + segment trees replay_buffer.py:87-218,
- *                          segment_tree.py:4-145
+ *                          segment_tree.py:4-145 (cacto_per_plan: which kernels a batch takes; no
+ *                          reference counterpart)
  *
  * Conventions
  *   - Every pointer argument named *_d is DEVICE memory (e.g. torch tensor .data_ptr()), contiguous
@@ -263,7 +264,8 @@ typedef struct {
   int32_t pair_xcds;       /* XCDs the paired 4-sample chain grid runs on; 0 above Bp = 512 and for elu */
   int32_t per_overlap;     /* 1: cacto_update_n_per may run the priority update and the next sample
                             * inside the critic's GEMM and Adam launches (critic_gemm 2, adam_nch != 0);
-                            * the tree's shape and CACTO_PER_OVERLAP decide the rest */
+                            * they do when per_overlap && cacto_per_plan's overlap_shape && alpha != 0 and
+                            * the pipeline orders its streams on the device */
   int32_t devwait_actor;   /* 1: the two-stream pipeline may order the actor chain after the critic's
                             * Adam with a device-side wait (16-sample tiles, Bp / 16 <= cus) */
   int32_t cus;             /* the compute-unit count the decision used */
@@ -661,6 +663,42 @@ int cacto_per_set_range_max(double* sum_tree_d, double* min_tree_d, int64_t capa
 int cacto_per_sample(const double* sum_tree_d, const double* min_tree_d, int64_t capacity, int64_t max_idx,
                      double beta, const double* uniforms_d, int B, int32_t* idx_d, float* is_w_d,
                      double* exp_counter_d, void* stream);
+/* Which PER kernels a sample of B and a priority update of B run on a tree of `capacity` leaves (the
+ * role cacto_update_plan plays for the update calls): a function of capacity and B alone, decided by
+ * the one function every PER entry and the pipelined loops read. With sub = min(1024, capacity) and
+ * roots = capacity / sub:
+ *   sampler         0 for B < 512: one workgroup, a 1,024-node top staged in LDS, the exp_counter
+ *                   increment inside; 1 from there on: ceil(B / 256) workgroups, an 8,192-node top,
+ *                   the increment as its own launch
+ *   count_deferred  1 (B >= 512): cacto_update_n[_per] leave the sampler's increment to the priority
+ *                   update, its only reader
+ *   update          1 for B >= 512 && roots <= 1024: one launch over the subtrees; 0 for B < 512 or
+ *                   roots > 2048: one workgroup; else 2 (capacity 2^21): leaves, subtrees, top as
+ *                   three launches
+ *   overlap_shape   1 for B >= 512 && 512 <= capacity <= 65536: see cacto_upd_plan.per_overlap */
+struct cacto_per_plan {
+  int32_t sampler;
+  int32_t sampler_top;     /* nodes of the sum tree the sampler stages in LDS */
+  int32_t sampler_wgs;
+  int32_t count_deferred;
+  int32_t update;
+  int32_t update_sub;      /* leaves per subtree */
+  int32_t update_roots;
+  int32_t overlap_shape;
+};
+/* CACTO_EINVAL for a null out, a capacity that is no power of two or B outside [1, 8192]; no device
+ * work, nothing enqueued. (The struct has no typedef: in C a typedef could not share the entry's name.) */
+int cacto_per_plan(int64_t capacity, int B, struct cacto_per_plan* out);
+/* cacto_per_sample[_global] by the sampler of the overlapped loop at any B: one sample per thread over
+ * ceil(B / 256) workgroups with a 4,096-node top. shard_stats_d / n_shards: as cacto_per_sample_global,
+ * or NULL / 0. runs_d (2 * capacity / 256 int32, or NULL; needs capacity >= 512): on entry
+ * PER_RUN_EMPTY = 0x7f7f7f7f in the first half and 0 in the second; on return runs_d[s] is the first
+ * sample index and runs_d[capacity / 256 + s] the sample count of the 256-leaf subtree s, untouched
+ * subtrees keeping the fill. Indices, weights and counters equal cacto_per_sample's bit for bit. */
+int cacto_per_sample_runs(const double* sum_tree_d, const double* min_tree_d, int64_t capacity, int64_t max_idx,
+                          double beta, const double* uniforms_d, int B, int32_t* idx_d, float* is_w_d,
+                          double* exp_counter_d, int32_t* runs_d, const double* shard_stats_d, int n_shards,
+                          void* stream);
 /* Data-parallel PER: stats_d [3] = (total sum, min leaf, max_idx) of this shard,
  * for an all-gather into shard_stats_d [n_shards, 3]. cacto_per_sample_global then samples B
  * stratified indices from the local tree exactly as cacto_per_sample, with IS weights taken

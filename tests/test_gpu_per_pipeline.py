@@ -1,31 +1,32 @@
 """The large-batch PER loop (configs[3]: car_park, B = 4096) pipelined (cacto_update_n_per) against
 the sequential sample -> update_rows -> update_priorities_device loop, bit for bit, under every
-build-time-free schedule knob the pipeline reads once per process — so each combination runs in
-its own child process:
+schedule the pipeline can take. The stream ordering is read once per process — so each runs in its
+own child process:
   * CACTO_PIPE_DEVWAIT = 0: cross-stream queue markers (every other iteration with PER, every
     iteration without), the three-buffer critic rotation and the pidx[t % 3] ring; = 1: the
     ordering on the device (the actor's GEMM publishes finished chains, the critic's Adam polls;
     the critic's Adam writes the critic through to memory and publishes, the actor chain polls
     relaxed), with a four-buffer PER index ring; unset: the library's own choice (device waits
-    after the handle's one-time concurrency probe);
-  * CACTO_PER_FUSED = 0 / 1: the priority update (with the sampler's deferred exp_counter += 1) as
-    the one-launch subtree kernel k_per_update_sub, or the round-3 chain k_per_count ->
-    k_per_leaves_mw -> k_per_subtrees -> k_per_top;
-  * CACTO_PER_DEEP_TOP = 0 / 1: the multi-workgroup sampler of round 4 or the 8,192-node one;
-  * CACTO_PER_OVERLAP = 0 / 1: (with device waits, the default) the priority update of update t
-    inside the critic GEMM's launch (k_wgrad_big_per: 256-leaf subtrees, the runs recorded by the
-    sampler) and the sample of t + 1 inside the critic Adam's (k_adam_sample: 4,096-node top), or
-    both on the critic stream between its launches.
+    after the handle's one-time concurrency probe).
+The PER form is chosen by shape (cacto_per_plan, asserted by every child):
+  * the configured replay size (a 2^16-leaf tree): overlap_shape 1 — with device waits the priority
+    update of update t runs inside the critic GEMM's launch (k_wgrad_big_per: 256-leaf subtrees, the
+    runs recorded by the sampler) and the sample of t + 1 inside the critic Adam's (k_adam_sample:
+    4,096-node top);
+  * REPLAY_SIZE = 2^17: overlap_shape 0 — the sample (k_per_sample_mw) and the priority update with
+    the sampler's deferred exp_counter += 1 (k_per_update_sub) on the critic stream between its launches.
 The 4,096-node sampler is also checked standalone against the oracle at every descent split
-(CACTO_PER_TOP=4096, its own child). A device-side wait that times out (forced once per process by
+(cacto_per_sample_runs, with the runs it records), and the priority update's three routes against
+each other. A device-side wait that times out (forced once per process by
 CACTO_PIPE_FAULT_INJECT=1) makes the learn_and_update call that ran it raise, and the handle runs
 again after that report (its own child).
 K = 6 and 7 (even / odd: the critic ends in the caller's buffer or a workspace copy), and the
 non-PER loop (DI, B = 1024, K = 7, and B = 8192, K = 5: more actor tiles than CUs, so the side
-stream keeps its queue marker) against sequential updates under the same knobs. Every child
+stream keeps its queue marker) against sequential updates under the same ordering. Every child
 also writes the trees after a priority update with an unsorted index list holding duplicates
 (B = 1024, the fused kernel's filter path), and all children must agree on every byte.
 replay_buffer.py:139-218, RL.py:120-143."""
+import ctypes
 import hashlib
 import json
 import os
@@ -69,21 +70,27 @@ def _child():
         return [t.cpu().numpy() for t in ts]
 
     out = {}
-    for K in (6, 7):
-        U = torch.as_tensor(np.random.default_rng(100 + K).uniform(size=(K, B)), device="cuda")
-        seq, sbuf = setup()
-        y = torch.empty(B, dtype=torch.float32, device="cuda")
-        V = torch.empty_like(y)
-        for k in range(K):
-            idx, w = sbuf.sample_device(U[k])
-            seq.update_rows(sbuf.storage, idx, w, y, V)
-            sbuf.update_priorities_device(idx, y, V)
-        pipe, pbuf = setup()
-        pipe.update_rows_n_per(pbuf, U)
-        torch.cuda.synchronize()
-        a, b = state(seq, sbuf), state(pipe, pbuf)
-        out["K%d_equal" % K] = all(np.array_equal(x, z) for x, z in zip(a, b))
-        out["K%d_hash" % K] = hashlib.sha256(b"".join(x.tobytes() for x in b)).hexdigest()
+    default_replay_size = conf.REPLAY_SIZE
+    # the configured replay size (overlap_shape 1), then a 2^17-leaf tree (overlap_shape 0)
+    for tag, replay_size in (("", None), ("big_", 2 ** 17)):
+        if replay_size is not None:
+            conf.REPLAY_SIZE = replay_size
+        for K in (6, 7):
+            U = torch.as_tensor(np.random.default_rng(100 + K).uniform(size=(K, B)), device="cuda")
+            seq, sbuf = setup()
+            out[tag + "plan"] = sbuf.plan(B)
+            y = torch.empty(B, dtype=torch.float32, device="cuda")
+            V = torch.empty_like(y)
+            for k in range(K):
+                idx, w = sbuf.sample_device(U[k])
+                seq.update_rows(sbuf.storage, idx, w, y, V)
+                sbuf.update_priorities_device(idx, y, V)
+            pipe, pbuf = setup()
+            pipe.update_rows_n_per(pbuf, U)
+            torch.cuda.synchronize()
+            a, b = state(seq, sbuf), state(pipe, pbuf)
+            out["%sK%d_equal" % (tag, K)] = all(np.array_equal(x, z) for x, z in zip(a, b))
+            out["%sK%d_hash" % (tag, K)] = hashlib.sha256(b"".join(x.tobytes() for x in b)).hexdigest()
     # the non-PER two-stream loop (DI, B = 1024) under the same knobs
     dconf = load_conf("double_integrator", fresh=True)
     denv = make_env(dconf)
@@ -133,6 +140,7 @@ def _child():
         out["probe"] = int(st[3])
     out["latch"] = latch
     # an unsorted index list with duplicates through the public priority update
+    conf.REPLAY_SIZE = default_replay_size
     _, buf = setup()
     idx = torch.as_tensor(np.random.default_rng(7).integers(0, 600, size=1024).astype(np.int32), device="cuda")
     y = torch.as_tensor(np.random.default_rng(8).normal(size=1024).astype(np.float32), device="cuda")
@@ -150,9 +158,8 @@ def test_pipelined_per_b4096_equals_sequential_every_schedule():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     res = {}
-    for fused, devwait, deep, overlap in (("1", "0", "1", "1"), ("0", "0", "0", "1"), ("1", "1", "1", "1"),
-                                          ("1", "1", "1", "0"), ("0", "1", "0", "0"), ("1", None, "1", "1")):
-        env = dict(os.environ, CACTO_PER_FUSED=fused, CACTO_PER_DEEP_TOP=deep, CACTO_PER_OVERLAP=overlap)
+    for devwait in ("0", "1", None):
+        env = dict(os.environ)
         env.pop("CACTO_PIPE_DEVWAIT", None)
         if devwait is not None:
             env["CACTO_PIPE_DEVWAIT"] = devwait
@@ -160,36 +167,52 @@ def test_pipelined_per_b4096_equals_sequential_every_schedule():
                            timeout=300)
         assert r.returncode == 0, r.stderr[-3000:]
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
-        res[(fused, devwait, deep, overlap)] = json.loads(line[len("RESULT "):])
+        res[devwait] = json.loads(line[len("RESULT "):])
     for key, r in res.items():
         assert r["K6_equal"] and r["K7_equal"] and r["di_equal"] and r["di8192_equal"] and r["latch"] == 0, key
+        assert r["big_K6_equal"] and r["big_K7_equal"], key
+        # which form ran, by shape: the overlapped one on the 2^16-leaf tree (where the streams are
+        # ordered on the device), sample and priority update between the launches on the 2^17-leaf one
+        assert r["plan"]["overlap_shape"] == 1 and r["plan"]["update_sub"] * r["plan"]["update_roots"] == 2 ** 16, r
+        assert r["big_plan"]["overlap_shape"] == 0 and r["big_plan"]["update_roots"] == 128, r
+        for plan in (r["plan"], r["big_plan"]):
+            assert (plan["sampler"], plan["count_deferred"], plan["update"]) == (1, 1, 1), plan
     # the library's own choice on a GPU box: the two streams run concurrently, so device-side waits
-    assert res[("1", None, "1", "1")]["probe"] == 2, res[("1", None, "1", "1")]
-    for field in ("K6_hash", "K7_hash", "unsorted_hash"):
+    assert res[None]["probe"] == 2, res[None]
+    for field in ("K6_hash", "K7_hash", "big_K6_hash", "big_K7_hash", "unsorted_hash"):
         assert len({r[field] for r in res.values()}) == 1, field
 
 
-def _sampler_child():
-    """k_per_sample_runs' 4,096-node form (CACTO_PER_TOP=4096) at every descent split, against the oracle."""
+def _consistent_trees(leaves):
+    """Both trees (numpy, 2 cap) over the given leaves, in the device's node layout and tie rule."""
+    cap = len(leaves)
+    st, mt = np.zeros(2 * cap), np.full(2 * cap, np.inf)
+    st[cap:], mt[cap:] = leaves, np.where(leaves > 0, leaves, np.inf)
+    lo = cap // 2
+    while lo >= 1:
+        k = np.arange(lo, 2 * lo)
+        st[k] = st[2 * k] + st[2 * k + 1]
+        mt[k] = np.where(mt[2 * k + 1] < mt[2 * k], mt[2 * k + 1], mt[2 * k])
+        lo //= 2
+    return st, mt
+
+
+@pytest.mark.gpu
+def test_sampler_4096_top_every_depth():
+    """k_per_sample_runs' 4,096-node form (cacto_per_sample_runs) at every descent split, against the
+    oracle; from 512 leaves on also the per-subtree runs it records, against numpy."""
     import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
     sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
     from oracle import buffer as obuf
     from cacto_amd import _lib as L
     from cacto_amd.system import dptr, stream
-    ok = True
     for cap in (2, 1024, 4096, 8192, 1 << 16, 1 << 17, 1 << 20):
         rng = np.random.default_rng(cap + 1)
         leaves = rng.uniform(0.01, 2.0, size=cap) ** 0.6
         leaves[rng.integers(0, cap, size=max(1, cap // 7))] = 0.0
-        st, mt = np.zeros(2 * cap), np.full(2 * cap, np.inf)
-        st[cap:], mt[cap:] = leaves, np.where(leaves > 0, leaves, np.inf)
-        lo = cap // 2
-        while lo >= 1:
-            k = np.arange(lo, 2 * lo)
-            st[k] = st[2 * k] + st[2 * k + 1]
-            mt[k] = np.where(mt[2 * k + 1] < mt[2 * k], mt[2 * k + 1], mt[2 * k])
-            lo //= 2
+        st, mt = _consistent_trees(leaves)
         o = obuf.PrioritizedReplayBuffer(cap, 1, 0.6, 0.6, 1e-2, 0.95, 0)
         o.it_sum.value, o.it_min.value = list(st), list(mt)
         max_idx = cap if cap <= 8192 else cap - 5
@@ -202,24 +225,94 @@ def _sampler_child():
         sd, md, ud = (torch.as_tensor(x, device="cuda") for x in (st, mt, u))
         idx = torch.empty(B, dtype=torch.int32, device="cuda")
         w = torch.empty(B, dtype=torch.float32, device="cuda")
-        L.lib().call("cacto_per_sample", dptr(sd), dptr(md), cap, max_idx, 0.6, dptr(ud), B, dptr(idx), dptr(w),
-                     None, stream())
-        ok &= bool(np.array_equal(idx.cpu().numpy(), oidx))
-        ok &= bool(np.allclose(w.cpu().numpy(), ow.astype(np.float32), rtol=1e-6))
-    print("RESULT " + json.dumps({"ok": ok}), flush=True)
+        runs, nsub = None, cap // L.PER_RUN_SUB
+        if cap >= 512:
+            runs = torch.cat([torch.full((nsub,), L.PER_RUN_EMPTY, dtype=torch.int32),
+                              torch.zeros(nsub, dtype=torch.int32)]).cuda()
+        L.lib().call("cacto_per_sample_runs", dptr(sd), dptr(md), cap, max_idx, 0.6, dptr(ud), B, dptr(idx), dptr(w),
+                     None, dptr(runs) if runs is not None else None, None, 0, stream())
+        got = idx.cpu().numpy()
+        assert np.array_equal(got, oidx), cap
+        assert np.allclose(w.cpu().numpy(), ow.astype(np.float32), rtol=1e-6), cap
+        if runs is not None:
+            sub = np.asarray(oidx) // L.PER_RUN_SUB
+            first = np.full(nsub, L.PER_RUN_EMPTY, dtype=np.int32)
+            np.minimum.at(first, sub, np.arange(B, dtype=np.int32))
+            count = np.bincount(sub, minlength=nsub).astype(np.int32)
+            assert np.array_equal(runs.cpu().numpy(), np.concatenate([first, count])), cap
+
+
+@pytest.fixture(scope="module")
+def route_inputs():
+    """3,000 live rows with seeded counters, and a 512-entry index list over them with duplicates:
+    entries [0, 511) avoid row 2999, which entry 511 alone names (with y == V: priority eps)."""
+    rng = np.random.default_rng(77)
+    rows = 3000
+    counters = rng.integers(0, 6, size=rows).astype(np.float64)
+    base = np.concatenate([rng.integers(0, rows - 1, size=400), rng.integers(100, 140, size=111)]).astype(np.int32)
+    y = rng.normal(size=512).astype(np.float32)
+    V = rng.normal(size=512).astype(np.float32)
+    V[511] = y[511]
+    leaves0 = rng.uniform(0.01, 2.0, size=rows) ** 0.6
+    return rows, counters, base, y, V, leaves0
 
 
 @pytest.mark.gpu
-def test_sampler_4096_top_every_depth():
+@pytest.mark.parametrize("order", ["sorted", "unsorted"])
+def test_priority_update_routes_agree(route_inputs, order):
+    """cacto_per_update on k_per_update_sub (n = 512, 2^20 leaves), the chain (2^21) and k_per_set
+    (2^22; and n = 511 on 2^20) writes the same leaves and max_priority, and leaves both trees
+    consistent with the done word back at +0.0. Exact: the routes run the same arithmetic."""
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    env = dict(os.environ, CACTO_PER_TOP="4096")
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "sampler"], env=env, capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
-    assert json.loads(line[len("RESULT "):])["ok"]
+    sys.path.insert(0, ROOT)
+    from cacto_amd import _lib as L
+    from cacto_amd.system import dptr, stream
+    rows, counters, base, y, V, leaves0 = route_inputs
+    head = np.sort(base) if order == "sorted" else base
+    assert len(np.unique(head)) < 511 and 2999 not in head
+    idx512 = np.concatenate([head, [2999]]).astype(np.int32)     # still sorted in the sorted case
+    yd, Vd = torch.as_tensor(y, device="cuda"), torch.as_tensor(V, device="cuda")
+
+    def run(cap, n, expect_route):
+        plan = L.PerPlan()
+        L.lib().call("cacto_per_plan", cap, n, ctypes.byref(plan))
+        assert plan.update == expect_route, (cap, n, plan.update)
+        leaves = np.zeros(cap)
+        leaves[:rows] = leaves0
+        st, mt = _consistent_trees(leaves)
+        sd, md = torch.as_tensor(st, device="cuda"), torch.as_tensor(mt, device="cuda")
+        cnt = torch.as_tensor(counters, device="cuda")
+        mp = torch.ones(1, dtype=torch.float64, device="cuda")
+        idx = torch.as_tensor(idx512[:n].copy(), device="cuda")
+        L.lib().call("cacto_per_update", dptr(sd), dptr(md), cap, dptr(idx), dptr(yd), dptr(Vd), dptr(cnt), 0.95, 1e-2,
+                     0.6, dptr(mp), n, stream())
+        torch.cuda.synchronize()
+        s, m = sd.cpu().numpy(), md.cpu().numpy()
+        # every internal node from its children, with tree_min's tie rule; the done word at +0.0
+        k = np.arange(1, cap)
+        assert np.array_equal(s[k].view(np.uint64), (s[2 * k] + s[2 * k + 1]).view(np.uint64)), (cap, n)
+        want_min = np.where(m[2 * k + 1] < m[2 * k], m[2 * k + 1], m[2 * k])
+        assert np.array_equal(m[k].view(np.uint64), want_min.view(np.uint64)), (cap, n)
+        assert s[:1].view(np.uint64)[0] == 0, (cap, n)
+        assert np.array_equal(cnt.cpu().numpy(), counters)       # cacto_per_update does not count
+        return s[cap:cap + rows].copy(), m[cap:cap + rows].copy(), mp.cpu().numpy().copy()
+
+    ref = run(2 ** 20, 512, L.PER_UPDATE_SUB)
+    assert not np.array_equal(ref[0], leaves0)                   # the update wrote leaves
+    for cap, route in ((2 ** 21, L.PER_UPDATE_CHAIN), (2 ** 22, L.PER_UPDATE_SET)):
+        got = run(cap, 512, route)
+        for a, b in zip(ref, got):
+            assert np.array_equal(a.view(np.uint64), b.view(np.uint64)), cap
+    # n = 511: the same entries without the last, whose row no other entry names
+    got = run(2 ** 20, 511, L.PER_UPDATE_SET)
+    keep = np.arange(rows) != 2999
+    for a, b in zip(ref[:2], got[:2]):
+        assert np.array_equal(a[keep].view(np.uint64), b[keep].view(np.uint64))
+    assert got[0][2999] == leaves0[2999] and ref[0][2999] != leaves0[2999]
+    # max_priority: entry 511 has y == V, so its priority (eps) is never the maximum and all four agree
+    assert got[2].view(np.uint64)[0] == ref[2].view(np.uint64)[0] and ref[2][0] > 1.0
 
 
 def _timeout_child():
@@ -275,9 +368,7 @@ def test_timed_out_device_wait_raises_in_the_same_learn_and_update_call():
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "sampler":
-        _sampler_child()
-    elif len(sys.argv) > 1 and sys.argv[1] == "timeout":
+    if len(sys.argv) > 1 and sys.argv[1] == "timeout":
         _timeout_child()
     else:
         _child()

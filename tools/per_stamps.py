@@ -3,7 +3,8 @@ workgroup): staging + batch scalars, LDS descent, tail (global levels + leaf), I
 B = 4096 on a full 2^16 tree; prints the mean ticks per phase over the workgroups of the last call.
 
     python -c "from cacto_amd import build; build.build_variant('libcacto_diag', ['CACTO_STAMPS'])"
-    CACTO_HIP_LIB=cacto_amd/libcacto_diag.so [CACTO_PER_TOP=4096] python tools/per_stamps.py
+    CACTO_HIP_LIB=cacto_amd/libcacto_diag.so python tools/per_stamps.py [4096]
+(4096: the overlapped loop's 4,096-node form, cacto_per_sample_runs, instead of the 8,192-node one)
 """
 import ctypes
 import os
@@ -17,6 +18,7 @@ from cacto_amd import _lib as L  # noqa: E402
 from cacto_amd.system import dptr, stream  # noqa: E402
 
 B, cap = 4096, 1 << 16
+TOP4K = len(sys.argv) > 1 and sys.argv[1] == "4096"
 rng = np.random.default_rng(0)
 leaves = rng.uniform(0.01, 2.0, size=cap) ** 0.6
 st, mt = np.zeros(2 * cap), np.full(2 * cap, np.inf)
@@ -35,7 +37,12 @@ sub = np.zeros(3)
 n = 0
 for it in range(50):
     u = torch.as_tensor(rng.uniform(size=B), device="cuda")
-    L.lib().call("cacto_per_sample", dptr(sd), dptr(md), cap, cap, 0.6, dptr(u), B, dptr(idx), dptr(w), None, stream())
+    if TOP4K:
+        L.lib().call("cacto_per_sample_runs", dptr(sd), dptr(md), cap, cap, 0.6, dptr(u), B, dptr(idx), dptr(w), None,
+                     None, None, 0, stream())
+    else:
+        L.lib().call("cacto_per_sample", dptr(sd), dptr(md), cap, cap, 0.6, dptr(u), B, dptr(idx), dptr(w), None,
+                     stream())
     torch.cuda.synchronize()
     if it < 10:
         continue
