@@ -17,7 +17,7 @@ SHARED = dict(
     prioritized_replay_alpha=0, prioritized_replay_beta=0.6, prioritized_replay_beta_iters=None,
     env_RL=0, EP_UPDATE=200, LR_SCHEDULE=0, save_flag=1, profile=0, offset_cost_fun=0,
     scale_cost_fun=1e-5, simulate_coulomb_friction=0, simulation_type="euler",
-    integration_scheme="E-Euler", end_effector_frame_id="EE",
+    integration_scheme="E-Euler", end_effector_frame_id="EE", Fig_path=None,
 )
 
 
@@ -43,3 +43,5 @@ def finalize(g):
     g["nb_action"] = len(g["u_max"])
     g["TARGET_STATE"] = np.asarray(g["TARGET_STATE"], dtype=np.float64)
     g["save_interval"] = g.get("save_interval", 5000) if g["save_flag"] else np.inf
+    if not g["plot_flag"]:
+        g["plot_rollout_interval"] = g["plot_rollout_interval_diff_loc"] = np.inf

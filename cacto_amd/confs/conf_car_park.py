@@ -17,6 +17,7 @@ BATCH_SIZE = 64
 TD_DIV = 2
 save_interval = 10000
 plot_flag = 0
+plot_rollout_interval, plot_rollout_interval_diff_loc = 400, 6000    # in updates; inf without plot_flag
 prioritized_replay_eps = 1e-2
 fresh_factor = 0.95
 

@@ -15,6 +15,7 @@ BATCH_SIZE = 128
 TD_DIV = 4
 save_interval = 5000
 plot_flag = 1
+plot_rollout_interval, plot_rollout_interval_diff_loc = 400, 6000    # in updates; inf without plot_flag
 prioritized_replay_eps = 1e-4
 fresh_factor = 1
 

@@ -16,6 +16,7 @@ BATCH_SIZE = 64
 TD_DIV = 2
 save_interval = 15000
 plot_flag = 0
+plot_rollout_interval, plot_rollout_interval_diff_loc = 400, 24000    # in updates; inf without plot_flag
 LR_SCHEDULE = 1
 prioritized_replay_eps = 1e-2
 fresh_factor = 0.95
@@ -41,6 +42,7 @@ dt = 0.05
 tau_coulomb_max = 0 * np.ones(robot.na)
 q_init, v_init = np.array([math.pi, math.pi, math.pi]), np.zeros(robot.nv)
 x_base, y_base = -7.0, 0.0
+l = 10.0    # link length (urdf/planar_manipulator_3dof.urdf), PLOT.compute_ICS's planar IK
 nb_state = robot.nq + robot.nv + 1
 _pi, _p4 = math.pi, math.pi / 4
 x_min = np.array([-np.inf] * 6 + [0])
