@@ -18,6 +18,10 @@
 //              after an accepted step (0 once below mu_min).
 // The derivatives are those of cacto_ddp_backward (ddp_device.h; they are the reward's, so the
 // signs flip on the way in). Everything is float64 VALU and LDS; there is no matrix-core work here.
+// With cacto_to_opts.hessian = CACTO_TO_HESS_PSD every node's l_xx is first replaced by its projection
+// onto the positive semidefinite cone (psd_project.h): a bool template parameter of the solving
+// kernels, and for the records of the label pass's derivative kernels one more kernel
+// (k_to_psd_records); nothing else of the algorithm changes.
 //
 //
 // The file, in order:
@@ -44,6 +48,7 @@
 //   The library is built with -ffp-contract=off and the solvers share these functions, so the two
 //   solvers of a system give the same numbers bit for bit.
 #include "ddp_device.h"
+#include "psd_project.h"
 
 namespace cacto {
 
@@ -279,8 +284,9 @@ struct ToRec {
 };
 
 // The record of node t of one closed-form episode (terminal, t == Te: l_x, l_xx of the terminal
-// weights only). A caller that knows terminal at compile time keeps the weights uniform.
-template <int NJ>
+// weights only). A caller that knows terminal at compile time keeps the weights uniform. PSD: l_xx is
+// replaced by its projection onto the positive semidefinite cone (the "psd" Hessian mode).
+template <int NJ, bool PSD>
 __device__ inline void to_node_record(const SysDevice& sd, const double* Minv, const Traj& cur, int t, bool terminal,
                                       double* r) {
   using TR = ToRec<NJ>;
@@ -295,8 +301,16 @@ __device__ inline void to_node_record(const SysDevice& sd, const double* Minv, c
   ddp_lx<NJ>(sd, w, x, lx, lxx);
 #pragma unroll
   for (int k = 0; k < N; ++k) r[RC::LX + k] = -lx[k];
+  if constexpr (PSD) {
 #pragma unroll
-  for (int k = 0; k < N * N; ++k) r[RC::LXX + k] = -lxx[k];
+    for (int k = 0; k < N * N; ++k) lxx[k] = -lxx[k];
+    psd_project<N>(lxx);
+#pragma unroll
+    for (int k = 0; k < N * N; ++k) r[RC::LXX + k] = lxx[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < N * N; ++k) r[RC::LXX + k] = -lxx[k];
+  }
   if (terminal) return;
   double A[N * N], B[N * M];
   ddp_jacobians<NJ>(sd, x, Minv, A, B);
@@ -345,12 +359,12 @@ __device__ inline int to_backward_thread(Node node, int Te, double mu, const Gai
   return -1;
 }
 // ... with every node evaluated on this thread
-template <int NJ>
+template <int NJ, bool PSD>
 __device__ inline int to_backward_eval(const SysDevice& sd, const double* Minv, const Traj& cur, int Te, double mu,
                                        const Gains& g, double* dJ) {
   return to_backward_thread<NJ>(
       [&](int t, bool terminal, double* buf) -> const double* {
-        to_node_record<NJ>(sd, Minv, cur, t, terminal, buf);
+        to_node_record<NJ, PSD>(sd, Minv, cur, t, terminal, buf);
         return buf;
       },
       Te, mu, g, dJ);
@@ -430,7 +444,7 @@ __device__ __forceinline__ Gains api_gains(double* k, double* K, int64_t ldU, in
 }
 
 // cacto_to_backward_gains, closed-form family: one thread per episode.
-template <int NJ>
+template <int NJ, bool PSD>
 __global__ void __launch_bounds__(64) k_to_gains_thread(const SysDevice* __restrict__ sdp, const double* S, int64_t ldS,
                                                          const double* U, int64_t ldU,
                                                          const int32_t* __restrict__ nsteps, int n_ep, double mu,
@@ -444,7 +458,7 @@ __global__ void __launch_bounds__(64) k_to_gains_thread(const SysDevice* __restr
   const Traj cur = api_traj<NJ>(const_cast<double*>(S), ldS, const_cast<double*>(U), ldU, e);
   const ToMinv<NJ> Minv(sd, cur);
   double dJ[3];
-  const int pd = to_backward_eval<NJ>(sd, Minv.a, cur, Te, mu, api_gains<NJ>(k_out, K_out, ldU, e), dJ);
+  const int pd = to_backward_eval<NJ, PSD>(sd, Minv.a, cur, Te, mu, api_gains<NJ>(k_out, K_out, ldU, e), dJ);
   pd_out[e] = pd;
 #pragma unroll
   for (int k = 0; k < 3; ++k) dJ_out[(size_t)e * 3 + k] = dJ[k];
@@ -777,7 +791,7 @@ __global__ void __launch_bounds__(256) k_to_order(const int32_t* __restrict__ ns
 // end. Its own phases: the backward pass with every node evaluated on the spot, and sequential
 // backtracking that stops at the first admissible step — a candidate's cost is evaluated without
 // storing it, and the accepted one is rolled out again in place.
-template <int NJ>
+template <int NJ, bool PSD>
 __global__ void __launch_bounds__(64) k_to_solve_thread(const SysDevice* __restrict__ sdp, const double* __restrict__ S0,
                                                          const double* __restrict__ U_init, int64_t ldU,
                                                          const int32_t* __restrict__ nsteps, int n_ep, int64_t ldS,
@@ -803,7 +817,7 @@ __global__ void __launch_bounds__(64) k_to_solve_thread(const SysDevice* __restr
     const ToMinv<NJ> Minv(sd, cur);
     double dJ[3];
     for (int it = 0; it < cfg.max_iter && s.running(); ++it) {
-      const ToVerdict v = to_verdict(cfg, to_backward_eval<NJ>(sd, Minv.a, cur, Te, s.mu, g, dJ), dJ);
+      const ToVerdict v = to_verdict(cfg, to_backward_eval<NJ, PSD>(sd, Minv.a, cur, Te, s.mu, g, dJ), dJ);
       int sel = -1;
       for (int j = 0; v == TO_SEARCH && j <= cfg.max_ls && sel < 0; ++j)
         if (!isnan(to_ls_candidate<NJ>(sd, cfg, cur, g, Te, j, s.J, dJ, cost))) sel = j;
@@ -835,7 +849,7 @@ struct ToWaveLds {
 // stride over the nodes for the records and lane 0 runs the recursion from them; lane
 // j <= max_ls evaluates the cost of alpha = 2^-j without storing it, and the lane of the
 // smallest admissible j rolls that step out in place.
-template <int NJ>
+template <int NJ, bool PSD>
 __global__ void __launch_bounds__(64) k_to_solve_wave(const SysDevice* __restrict__ sdp, const double* __restrict__ S0,
                                                        const double* U_init, int64_t ldU,
                                                        const int32_t* __restrict__ nsteps, int n_ep, int64_t ldS,
@@ -862,7 +876,7 @@ __global__ void __launch_bounds__(64) k_to_solve_wave(const SysDevice* __restric
   if (s.running()) {
     const ToMinv<NJ> Minv(sd, cur);
     for (int it = 0; it < cfg.max_iter && s.running(); ++it) {
-      for (int t = lane; t <= Te; t += 64) to_node_record<NJ>(sd, Minv.a, cur, t, t == Te, rec + (size_t)t * TR::R);
+      for (int t = lane; t <= Te; t += 64) to_node_record<NJ, PSD>(sd, Minv.a, cur, t, t == Te, rec + (size_t)t * TR::R);
       __syncthreads();
       if (lane == 0) {
         double d[3];
@@ -885,6 +899,33 @@ __global__ void __launch_bounds__(64) k_to_solve_wave(const SysDevice* __restric
     }
   }
   if (lane == 0) to_iter_store(s, out, e);
+}
+
+// The "psd" Hessian mode on a split-family node's record: the l_xx block (the reward's, as the
+// derivative kernels leave it) replaced by -P(-l_xx), the projection taken in the cost convention.
+// rec, es as ddp_derivs_node.
+template <int NJ>
+__device__ __forceinline__ void to_psd_record(double* rec, size_t es) {
+  using RC = DdpRec<NJ>;
+  constexpr int N = RC::N;
+  double h[N * N];
+#pragma unroll
+  for (int k = 0; k < N * N; ++k) h[k] = -rec[(size_t)(RC::LXX + k) * es];
+  psd_project<N>(h);
+#pragma unroll
+  for (int k = 0; k < N * N; ++k) rec[(size_t)(RC::LXX + k) * es] = -h[k];
+}
+
+// ... as a kernel of its own over the [t][k][e] records of the label pass's derivative kernels
+// (the host-issued solver and cacto_to_backward_gains), one thread per (episode, step), run after
+// them: k_ddp_lx<3/6> already spills, and the label pass must keep the exact Hessian.
+template <int NJ>
+__global__ void __launch_bounds__(64) k_to_psd_records(const int32_t* __restrict__ nsteps, int n_ep, double* __restrict__ ws) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  const int t = blockIdx.y;
+  if (e >= n_ep) return;
+  if (t > nsteps[e]) return;  // also Te < 0: skipped, as k_ddp_derivs
+  to_psd_record<NJ>(ws + (size_t)t * DdpRec<NJ>::R * n_ep + e, (size_t)n_ep);
 }
 
 // LDS of the backward pass of one split-family episode (operands, products, gains of one step)
@@ -1189,7 +1230,7 @@ struct ToSplitLds {
 // The revolute chains are not instantiated: their derivative phase needs the tangent pass's LDS
 // slabs and the bodies of k_ddp_prim / k_ddp_tan / k_ddp_lx, and a build of this kernel with them
 // faulted on the GPU for a reason that has not been found.
-template <int NJ, int BT>
+template <int NJ, int BT, bool PSD>
 __global__ void __launch_bounds__(BT) k_to_solve_split(const SysDevice* __restrict__ sdp, const double* __restrict__ S0,
                                                         const double* U_init, int64_t ldU,
                                                         const int32_t* __restrict__ nsteps, int n_ep, int64_t ldS,
@@ -1212,8 +1253,10 @@ __global__ void __launch_bounds__(BT) k_to_solve_split(const SysDevice* __restri
   __syncthreads();
   ToIter s = to_iter_begin(Te, lds.pass[3]);
   for (int it = 0; it < cfg.max_iter && s.running(); ++it) {
-    for (int t = tid; t <= Te; t += BT)
+    for (int t = tid; t <= Te; t += BT) {
       ddp_derivs_node<NJ>(sd, &cur.S.at(t, 0), t < Te ? &cur.U.at(t, 0) : nullptr, t == Te, rec + (size_t)t * RC::R, 1);
+      if constexpr (PSD) to_psd_record<NJ>(rec + (size_t)t * RC::R, 1);
+    }
     __syncthreads();
     const ToPass bp = to_gains_episode<NJ, BT>(lds.gains, sd.p, cur.U.p, Te, s.mu, rec, (size_t)RC::R, 1, g.k.p, g.K.p, tid);
     if (tid == 0) {
@@ -1244,6 +1287,13 @@ namespace {
 
 inline bool to_path_ok(int path) { return path == CACTO_TO_PATH_DEFAULT || path == CACTO_TO_PATH_WAVE; }
 
+// cacto_to_opts: NULL means the defaults; anything but a known hessian and zero reserved words is refused
+inline bool to_opts_ok(const cacto_to_opts* o) {
+  return !o || ((o->hessian == CACTO_TO_HESS_EXACT || o->hessian == CACTO_TO_HESS_PSD) && o->reserved[0] == 0 &&
+                o->reserved[1] == 0 && o->reserved[2] == 0);
+}
+inline bool to_opts_psd(const cacto_to_opts* o) { return o && o->hessian == CACTO_TO_HESS_PSD; }
+
 // the (dynamics, reward) combinations of the six systems, as cacto_ddp_backward
 template <int NJ>
 bool to_supported(const cacto_sys* sys, const char* who) {
@@ -1260,10 +1310,11 @@ bool to_supported(const cacto_sys* sys, const char* who) {
   return ok;
 }
 
-// the derivative kernels of the label pass over (episode, step)
+// the derivative kernels of the label pass over (episode, step); psd: then the projection of the
+// records' l_xx blocks (one launch more)
 template <int NJ>
 int to_launch_derivs(const cacto_sys* sys, const double* S, int64_t ldS, const double* U, int64_t ldU, const int32_t* n,
-                     int n_ep, double* rec, hipStream_t st) {
+                     int n_ep, double* rec, bool psd, hipStream_t st) {
   const dim3 g(ceil_div(n_ep, 64), (unsigned)ldS);
   if constexpr (NJ > 2) {
     double* pw = rec + (size_t)ldS * DdpRec<NJ>::R * n_ep;
@@ -1276,26 +1327,34 @@ int to_launch_derivs(const cacto_sys* sys, const double* S, int64_t ldS, const d
     hipLaunchKernelGGL(k_ddp_derivs<NJ>, g, dim3(64), 0, st, sys->dev, S, ldS, U, ldU, n, n_ep, rec);
   }
   CACTO_CHECK_HIP(hipGetLastError());
+  if (psd) {
+    hipLaunchKernelGGL(k_to_psd_records<NJ>, g, dim3(64), 0, st, n, n_ep, rec);
+    CACTO_CHECK_HIP(hipGetLastError());
+  }
   return CACTO_OK;
 }
 
 template <int NJ>
 struct LaunchToGains {
   static int run(const cacto_sys* sys, const double* S, int64_t ldS, const double* U, int64_t ldU, const int32_t* n,
-                 int n_ep, double mu, double* k, double* K, double* dJ, int32_t* pd, hipStream_t st) {
+                 int n_ep, double mu, bool psd, double* k, double* K, double* dJ, int32_t* pd, hipStream_t st) {
     if (!to_supported<NJ>(sys, "cacto_to_backward_gains")) return CACTO_EUNSUPPORTED;
     if constexpr (DdpDims<NJ>::ok) {
       if constexpr (to_split<NJ>()) {
         double* rec = nullptr;
         const int rc = cacto_ddp_workspace(const_cast<cacto_sys*>(sys), to_rec_doubles<NJ>(n_ep, ldS) * sizeof(double), &rec);
         if (rc != CACTO_OK) return rc;
-        const int rc2 = to_launch_derivs<NJ>(sys, S, ldS, U, ldU, n, n_ep, rec, st);
+        const int rc2 = to_launch_derivs<NJ>(sys, S, ldS, U, ldU, n, n_ep, rec, psd, st);
         if (rc2 != CACTO_OK) return rc2;
         hipLaunchKernelGGL(k_to_gains_wave<NJ>, dim3(n_ep), dim3(64), 0, st, sys->dev, U, ldU, n, n_ep, ldS, mu,
                            (const double*)nullptr, rec, k, K, dJ, pd);
       } else {
-        hipLaunchKernelGGL(k_to_gains_thread<NJ>, dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S, ldS, U, ldU, n,
-                           n_ep, mu, k, K, dJ, pd);
+        if (psd)
+          hipLaunchKernelGGL((k_to_gains_thread<NJ, true>), dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S, ldS, U,
+                             ldU, n, n_ep, mu, k, K, dJ, pd);
+        else
+          hipLaunchKernelGGL((k_to_gains_thread<NJ, false>), dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S, ldS, U,
+                             ldU, n, n_ep, mu, k, K, dJ, pd);
       }
       CACTO_CHECK_HIP(hipGetLastError());
     }
@@ -1326,11 +1385,24 @@ struct LaunchToBytes {
   }
 };
 
-// The solvers' launches. A solver is instantiated for the systems to_route can give it.
+// The solvers' launches. A solver is instantiated for the systems to_route can give it, once per
+// Hessian mode: the mode is a template parameter of the solving kernels, so the exact-mode kernels
+// carry no trace of the projection.
 template <int NJ>
 struct LaunchToSolve {
+  template <bool PSD>
+  static void launch_closed_form(ToSolver solver, const cacto_sys* sys, const double* S0, const double* U_init, int64_t ldU,
+                                 const int32_t* n, int n_ep, int64_t ldS, const ToCfgDev& c, const ToWs<NJ>& lay, double* S,
+                                 double* U, double* cost, int32_t* status, int32_t* iters, double* J, hipStream_t st) {
+    if (solver == TO_SOLVER_WAVE)
+      hipLaunchKernelGGL((k_to_solve_wave<NJ, PSD>), dim3(n_ep), dim3(64), 0, st, sys->dev, S0, U_init, ldU, n, n_ep, ldS, c,
+                         lay, S, U, cost, status, iters, J);
+    else
+      hipLaunchKernelGGL((k_to_solve_thread<NJ, PSD>), dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S0, U_init, ldU,
+                         n, n_ep, ldS, c, (const int32_t*)lay.order, lay.lanes, S, U, cost, status, iters, J);
+  }
   static int run(const cacto_sys* sys, const double* S0, const double* U_init, int64_t ldU, const int32_t* n, int n_ep,
-                 int64_t ldS, const cacto_to_cfg* cfg, double* S, double* U, double* cost, int32_t* status,
+                 int64_t ldS, const cacto_to_cfg* cfg, bool psd, double* S, double* U, double* cost, int32_t* status,
                  int32_t* iters, double* J, void* ws, size_t ws_bytes, hipStream_t st) {
     if (!to_supported<NJ>(sys, "cacto_to_solve")) return CACTO_EUNSUPPORTED;
     if constexpr (DdpDims<NJ>::ok) {
@@ -1343,19 +1415,20 @@ struct LaunchToSolve {
       if constexpr (!to_split<NJ>()) {
         hipLaunchKernelGGL(k_to_order, dim3(1), dim3(256), 0, st, n, n_ep, ldS, lay.order, lay.hist);
         CACTO_CHECK_HIP(hipGetLastError());
-        if (solver == TO_SOLVER_WAVE)
-          hipLaunchKernelGGL(k_to_solve_wave<NJ>, dim3(n_ep), dim3(64), 0, st, sys->dev, S0, U_init, ldU, n, n_ep, ldS, c,
-                             lay, S, U, cost, status, iters, J);
+        if (psd)
+          launch_closed_form<true>(solver, sys, S0, U_init, ldU, n, n_ep, ldS, c, lay, S, U, cost, status, iters, J, st);
         else
-          hipLaunchKernelGGL(k_to_solve_thread<NJ>, dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S0, U_init, ldU,
-                             n, n_ep, ldS, c, (const int32_t*)lay.order, lay.lanes, S, U, cost, status,
-                             iters, J);
+          launch_closed_form<false>(solver, sys, S0, U_init, ldU, n, n_ep, ldS, c, lay, S, U, cost, status, iters, J, st);
         CACTO_CHECK_HIP(hipGetLastError());
       } else if (solver == TO_SOLVER_SPLIT) {
         if constexpr (to_persistent<NJ>()) {
           constexpr int BT = TO_SPLIT_THREADS;
-          hipLaunchKernelGGL((k_to_solve_split<NJ, BT>), dim3(n_ep), dim3(BT), 0, st, sys->dev, S0, U_init, ldU, n, n_ep,
-                             ldS, c, lay, S, U, cost, status, iters, J);
+          if (psd)
+            hipLaunchKernelGGL((k_to_solve_split<NJ, BT, true>), dim3(n_ep), dim3(BT), 0, st, sys->dev, S0, U_init, ldU, n,
+                               n_ep, ldS, c, lay, S, U, cost, status, iters, J);
+          else
+            hipLaunchKernelGGL((k_to_solve_split<NJ, BT, false>), dim3(n_ep), dim3(BT), 0, st, sys->dev, S0, U_init, ldU, n,
+                               n_ep, ldS, c, lay, S, U, cost, status, iters, J);
           CACTO_CHECK_HIP(hipGetLastError());
         }
       } else {
@@ -1375,7 +1448,7 @@ struct LaunchToSolve {
             CACTO_CHECK_HIP(hipStreamSynchronize(st));
             if (d >= n_ep) break;
           }
-          const int rc = to_launch_derivs<NJ>(sys, S, ldS, U, ldU, lay.st.live, n_ep, lay.rec, st);
+          const int rc = to_launch_derivs<NJ>(sys, S, ldS, U, ldU, lay.st.live, n_ep, lay.rec, psd, st);
           if (rc != CACTO_OK) return rc;
           hipLaunchKernelGGL(k_to_gains_wave<NJ>, dim3(n_ep), dim3(64), 0, st, sys->dev, U, ldU, lay.st.live, n_ep, ldS,
                              0.0, (const double*)lay.st.mu, lay.rec, lay.k, lay.K, lay.dJ, lay.pd);
@@ -1393,15 +1466,18 @@ struct LaunchToSolve {
 // cacto_to_solve_plan: what LaunchToSolve runs for a path
 template <int NJ>
 struct LaunchToPlan {
-  static int run(const cacto_sys* sys, int path, cacto_to_plan* out) {
+  static int run(const cacto_sys* sys, int path, bool psd, cacto_to_plan* out) {
     if (!to_supported<NJ>(sys, "cacto_to_solve_plan")) return CACTO_EUNSUPPORTED;
     if constexpr (DdpDims<NJ>::ok) {
       switch (to_route<NJ>(path)) {
         case TO_SOLVER_THREAD: *out = cacto_to_plan{1, 64, 0, 0}; break;
         case TO_SOLVER_WAVE: *out = cacto_to_plan{1, 64, (int32_t)sizeof(ToWaveLds), 0}; break;
         case TO_SOLVER_SPLIT: *out = cacto_to_plan{1, TO_SPLIT_THREADS, (int32_t)sizeof(ToSplitLds<NJ>), 0}; break;
-        // the kernel described is the one-wave-per-episode backward pass
-        case TO_SOLVER_HOST: *out = cacto_to_plan{0, 64, (int32_t)sizeof(ToGainsLds<NJ>), NJ > 2 ? 5 : 3}; break;
+        // the kernel described is the one-wave-per-episode backward pass; psd: one launch more, the
+        // projection of the records
+        case TO_SOLVER_HOST:
+          *out = cacto_to_plan{0, 64, (int32_t)sizeof(ToGainsLds<NJ>), (NJ > 2 ? 5 : 3) + (psd ? 1 : 0)};
+          break;
       }
     }
     return CACTO_OK;
@@ -1410,22 +1486,41 @@ struct LaunchToPlan {
 
 }  // namespace
 
-extern "C" int cacto_to_solve_plan(const cacto_sys* sys, const cacto_to_cfg* cfg_h, cacto_to_plan* out) {
+// The options are a property of the call alone: like an unknown path they are reported before the
+// other arguments are looked at.
+#define CACTO_TO_REQUIRE_OPTS(opts, who) \
+  CACTO_REQUIRE(to_opts_ok(opts), who ": bad options (hessian: CACTO_TO_HESS_EXACT or CACTO_TO_HESS_PSD; reserved words 0)")
+
+extern "C" int cacto_to_solve_plan_opts(const cacto_sys* sys, const cacto_to_cfg* cfg_h, cacto_to_plan* out,
+                                        const cacto_to_opts* opts) {
   CACTO_REQUIRE(cfg_h, "cacto_to_solve_plan: null config");
   CACTO_REQUIRE(to_path_ok(cfg_h->path),
                 "cacto_to_solve_plan: bad config (path: CACTO_TO_PATH_DEFAULT or CACTO_TO_PATH_WAVE)");
+  CACTO_TO_REQUIRE_OPTS(opts, "cacto_to_solve_plan");
   CACTO_REQUIRE(sys && out, "cacto_to_solve_plan: bad arguments (null pointer)");
-  return dispatch_nj<LaunchToPlan>(sys->host.p, sys, (int)cfg_h->path, out);
+  return dispatch_nj<LaunchToPlan>(sys->host.p, sys, (int)cfg_h->path, to_opts_psd(opts), out);
+}
+
+extern "C" int cacto_to_solve_plan(const cacto_sys* sys, const cacto_to_cfg* cfg_h, cacto_to_plan* out) {
+  return cacto_to_solve_plan_opts(sys, cfg_h, out, nullptr);
+}
+
+extern "C" int cacto_to_backward_gains_opts(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d,
+                                            int64_t ldU, const int32_t* nsteps_d, int n_ep, double mu, double* k_d,
+                                            double* K_d, double* dJ_d, int32_t* pd_d, void* stream,
+                                            const cacto_to_opts* opts) {
+  CACTO_TO_REQUIRE_OPTS(opts, "cacto_to_backward_gains");
+  CACTO_REQUIRE(sys && S_d && U_d && nsteps_d && k_d && K_d && dJ_d && pd_d && n_ep >= 0 && ldS >= 1 && ldU >= 0,
+                "cacto_to_backward_gains: bad arguments");
+  if (n_ep == 0) return CACTO_OK;
+  return dispatch_nj<LaunchToGains>(sys->host.p, sys, S_d, ldS, U_d, ldU, nsteps_d, n_ep, mu, to_opts_psd(opts), k_d, K_d,
+                                    dJ_d, pd_d, as_stream(stream));
 }
 
 extern "C" int cacto_to_backward_gains(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d,
                                        int64_t ldU, const int32_t* nsteps_d, int n_ep, double mu, double* k_d,
                                        double* K_d, double* dJ_d, int32_t* pd_d, void* stream) {
-  CACTO_REQUIRE(sys && S_d && U_d && nsteps_d && k_d && K_d && dJ_d && pd_d && n_ep >= 0 && ldS >= 1 && ldU >= 0,
-                "cacto_to_backward_gains: bad arguments");
-  if (n_ep == 0) return CACTO_OK;
-  return dispatch_nj<LaunchToGains>(sys->host.p, sys, S_d, ldS, U_d, ldU, nsteps_d, n_ep, mu, k_d, K_d, dJ_d, pd_d,
-                                    as_stream(stream));
+  return cacto_to_backward_gains_opts(sys, S_d, ldS, U_d, ldU, nsteps_d, n_ep, mu, k_d, K_d, dJ_d, pd_d, stream, nullptr);
 }
 
 extern "C" int cacto_to_forward(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d, int64_t ldU,
@@ -1439,27 +1534,33 @@ extern "C" int cacto_to_forward(const cacto_sys* sys, const double* S_d, int64_t
                                       U_new_d, cost_new_d, as_stream(stream));
 }
 
-extern "C" size_t cacto_to_workspace_bytes(const cacto_sys* sys, int n_ep, int64_t ldS) {
-  if (!sys || n_ep < 0 || ldS < 1) return 0;
+// The projection works in place on the records, so the workspace is the same in both Hessian modes
+extern "C" size_t cacto_to_workspace_bytes_opts(const cacto_sys* sys, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h,
+                                                const cacto_to_opts* opts) {
+  const int path = cfg_h ? (int)cfg_h->path : (int)CACTO_TO_PATH_DEFAULT;
+  if (!sys || n_ep < 0 || ldS < 1 || !to_path_ok(path) || !to_opts_ok(opts)) return 0;
   size_t out = 0;
-  if (dispatch_nj<LaunchToBytes>(sys->host.p, n_ep, ldS, (int)CACTO_TO_PATH_DEFAULT, &out) != CACTO_OK) return 0;
+  if (dispatch_nj<LaunchToBytes>(sys->host.p, n_ep, ldS, path, &out) != CACTO_OK) return 0;
   return out;
+}
+
+extern "C" size_t cacto_to_workspace_bytes(const cacto_sys* sys, int n_ep, int64_t ldS) {
+  return cacto_to_workspace_bytes_opts(sys, n_ep, ldS, nullptr, nullptr);
 }
 
 extern "C" size_t cacto_to_workspace_bytes_cfg(const cacto_sys* sys, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h) {
-  if (!sys || !cfg_h || n_ep < 0 || ldS < 1 || !to_path_ok(cfg_h->path)) return 0;
-  size_t out = 0;
-  if (dispatch_nj<LaunchToBytes>(sys->host.p, n_ep, ldS, (int)cfg_h->path, &out) != CACTO_OK) return 0;
-  return out;
+  if (!cfg_h) return 0;
+  return cacto_to_workspace_bytes_opts(sys, n_ep, ldS, cfg_h, nullptr);
 }
 
-extern "C" int cacto_to_solve(const cacto_sys* sys, const double* S0_d, const double* U_init_d, int64_t ldU,
-                              const int32_t* nsteps_d, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h, double* S_d,
-                              double* U_d, double* step_cost_d, int32_t* status_d, int32_t* iters_d, double* J_d,
-                              void* ws_d, size_t ws_bytes, void* stream) {
+extern "C" int cacto_to_solve_opts(const cacto_sys* sys, const double* S0_d, const double* U_init_d, int64_t ldU,
+                                   const int32_t* nsteps_d, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h, double* S_d,
+                                   double* U_d, double* step_cost_d, int32_t* status_d, int32_t* iters_d, double* J_d,
+                                   void* ws_d, size_t ws_bytes, void* stream, const cacto_to_opts* opts) {
   CACTO_REQUIRE(cfg_h, "cacto_to_solve: null config");
   // an unknown path is a property of the config alone: reported before the arguments are looked at
   CACTO_REQUIRE(to_path_ok(cfg_h->path), "cacto_to_solve: bad config (path: CACTO_TO_PATH_DEFAULT or CACTO_TO_PATH_WAVE)");
+  CACTO_TO_REQUIRE_OPTS(opts, "cacto_to_solve");
   CACTO_REQUIRE(sys && S0_d && U_init_d && nsteps_d && S_d && U_d && step_cost_d && status_d && iters_d && J_d && ws_d &&
                     n_ep >= 0 && ldS >= 1 && ldU >= 0 && ldU <= ldS,
                 "cacto_to_solve: bad arguments (null pointer, n_ep < 0, ldS < 1, ldU < 0 or ldU > ldS)");
@@ -1471,6 +1572,14 @@ extern "C" int cacto_to_solve(const cacto_sys* sys, const double* S0_d, const do
     return CACTO_EUNSUPPORTED;
   }
   if (n_ep == 0) return CACTO_OK;
-  return dispatch_nj<LaunchToSolve>(sys->host.p, sys, S0_d, U_init_d, ldU, nsteps_d, n_ep, ldS, cfg_h, S_d, U_d,
-                                    step_cost_d, status_d, iters_d, J_d, ws_d, ws_bytes, as_stream(stream));
+  return dispatch_nj<LaunchToSolve>(sys->host.p, sys, S0_d, U_init_d, ldU, nsteps_d, n_ep, ldS, cfg_h, to_opts_psd(opts),
+                                    S_d, U_d, step_cost_d, status_d, iters_d, J_d, ws_d, ws_bytes, as_stream(stream));
+}
+
+extern "C" int cacto_to_solve(const cacto_sys* sys, const double* S0_d, const double* U_init_d, int64_t ldU,
+                              const int32_t* nsteps_d, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h, double* S_d,
+                              double* U_d, double* step_cost_d, int32_t* status_d, int32_t* iters_d, double* J_d,
+                              void* ws_d, size_t ws_bytes, void* stream) {
+  return cacto_to_solve_opts(sys, S0_d, U_init_d, ldU, nsteps_d, n_ep, ldS, cfg_h, S_d, U_d, step_cost_d, status_d,
+                             iters_d, J_d, ws_d, ws_bytes, stream, nullptr);
 }

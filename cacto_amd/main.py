@@ -29,7 +29,8 @@ from .confs import SYSTEM_MAP, load_conf
 def parse_args(argv=None):
     """The reference's options (main.py:18-46) that have a meaning here, plus --nb-loops (stop after
     that many loops), --to-path (which kernels solve the TO batch, cacto_amd.to.PATHS) and
-    --accept-maxiter (keep episodes whose solve stopped at max_iter). --plots, --fig-path and
+    --accept-maxiter (keep episodes whose solve stopped at max_iter). --to-hessian (the node Hessian
+    of the TO's backward pass, cacto_amd.to.HESSIANS; exact when absent), --plots, --fig-path and
     --eval-every (the evaluation stage) are in the dict only when they are given. Returns a dict."""
     p = argparse.ArgumentParser(prog="python -m cacto_amd.main", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument("--test-n", type=int, default=0, help="Test number")
@@ -43,6 +44,9 @@ def parse_args(argv=None):
                    help="Kernels of the batched trajectory optimiser")
     p.add_argument("--accept-maxiter", action="store_true",
                    help="Keep episodes whose TO solve stopped at max_iter without converging")
+    p.add_argument("--to-hessian", type=str, default=argparse.SUPPRESS, choices=["exact", "psd"],
+                   help="Node Hessian of the trajectory optimiser's backward pass: the cost's own, or its "
+                        "projection onto the positive semidefinite cone (default: exact)")
     p.add_argument("--plots", action="store_true", default=argparse.SUPPRESS,
                    help="Run the evaluation stage: value grid, TO trajectories, return and roll-out figures")
     p.add_argument("--fig-path", type=str, default=argparse.SUPPRESS,
@@ -56,6 +60,8 @@ def train_kwargs(args):
     """parse_args' dict -> (system_id, keyword arguments of train)."""
     kw = dict(seed=args["seed"], N_try=args["test_n"], w_S=args["w_S"], to_cfg=dict(path=args["to_path"]),
               accept_maxiter=args["accept_maxiter"], n_loops=args["nb_loops"], recover=args["recover_training_flag"])
+    if "to_hessian" in args:
+        kw["to_cfg"]["hessian"] = args["to_hessian"]
     if args.get("plots"):
         kw.update(evaluate=True, eval_every=args.get("eval_every", 1))
     return args["system_id"], kw

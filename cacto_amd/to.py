@@ -4,8 +4,8 @@
 The problem is unconstrained apart from the dynamics and the fixed initial state (the control
 bounds are the penalty w_b (u/u_max)^10 inside the cost, environment_TO.py:201-206), so here it is
 solved by a batched iLQR (`cacto_to_solve`): single shooting, Gauss-Newton DDP with first-order
-dynamics and exact cost Hessians, a backtracking line search and Levenberg-Marquardt
-regularisation, all episodes of a main.py iteration in one call, float64 throughout. The cost is
+dynamics and exact cost Hessians (or, `hessian="psd"`, their projections onto the positive
+semidefinite cone), a backtracking line search and Levenberg-Marquardt regularisation, all episodes of a main.py iteration in one call, float64 throughout. The cost is
 the TO cost (-Env.reward; for UR5 plus the bound penalty that environment_TO.py has and
 UR5.reward leaves out), the dynamics Env.simulate. It is a local method like IPOPT: both stop at a
 stationary point of the same problem, not necessarily the same one.
@@ -20,6 +20,7 @@ stationary point of the same problem, not necessarily the same one.
                          trajectory — a TO solution or the policy roll-outs of RL_AC.rollout_batch
 """
 import ctypes as C
+import numbers
 
 import numpy as np
 import torch
@@ -37,12 +38,37 @@ CONVERGED, MAXITER, FAILED = L.CACTO_TO_CONVERGED, L.CACTO_TO_MAXITER, L.CACTO_T
 # and the whole loop in one kernel for those three and car_park (per-episode calls and batches of a
 # few hundred; no host round trip, poll_every is not used), the host-issued loop for the manipulator
 # and UR5. TO.solve_plan tells what a config runs.
+# hessian: the node Hessian l_xx of the backward pass. "exact" / 0: the cost's own; "psd" / 1: its
+# projection onto the positive semidefinite cone at every node (cacto_to_opts), which keeps Q_uu
+# positive definite without mu where the cost is concave. The Sobolev labels (backward_pass) are
+# exact under either.
 DEFAULT_CFG = dict(max_iter=400, max_ls=10, gtol=1e-4, armijo=1e-4, mu_min=1e-6, mu_up=10.0, mu_down=10.0,
-                   mu_max=1e10, poll_every=8, path=0)
+                   mu_max=1e10, poll_every=8, path=0, hessian="exact")
 PATHS = {"default": L.CACTO_TO_PATH_DEFAULT, "wave": L.CACTO_TO_PATH_WAVE}
+HESSIANS = {"exact": L.CACTO_TO_HESS_EXACT, "psd": L.CACTO_TO_HESS_PSD}
+
+
+def make_opts(cfg=None):
+    """The ToOpts (cacto_to_opts) of a cfg dict: its `hessian` key ("exact" / "psd" / 0 / 1, any
+    integer type), or of a bare hessian value. A ToOpts is returned as it is."""
+    if isinstance(cfg, L.ToOpts):
+        return cfg
+    h = DEFAULT_CFG["hessian"] if cfg is None else cfg
+    if isinstance(cfg, dict):
+        h = cfg.get("hessian", DEFAULT_CFG["hessian"])
+    if isinstance(h, str) and h in HESSIANS:
+        h = HESSIANS[h]
+    if isinstance(h, bool) or not isinstance(h, numbers.Integral) or int(h) not in HESSIANS.values():
+        raise ValueError("unknown TO hessian %r (one of %s, or 0 / 1)" % (h, sorted(HESSIANS)))
+    o = L.ToOpts()
+    o.hessian = int(h)
+    return o
 
 
 def make_cfg(cfg=None):
+    """The 64-byte ToCfg (cacto_to_cfg) of a cfg dict over DEFAULT_CFG. The `hessian` key is checked
+    here but is no field of that struct: it travels in the ToOpts that make_opts(cfg) gives, and a
+    caller who hands solve_batch / solve_plan a ToCfg passes that as `opts`."""
     vals = dict(DEFAULT_CFG)
     vals.update(cfg or {})
     unknown = set(vals) - set(DEFAULT_CFG)
@@ -52,10 +78,27 @@ def make_cfg(cfg=None):
         if vals["path"] not in PATHS:
             raise ValueError("unknown TO path %r (one of %s, or 0 / 1)" % (vals["path"], sorted(PATHS)))
         vals["path"] = PATHS[vals["path"]]
+    make_opts(vals)
     c = L.ToCfg()
     for k, v in vals.items():
-        setattr(c, k, v)
+        if k != "hessian":
+            setattr(c, k, v)
     return c
+
+
+def _cfg_opts(cfg, opts=None):
+    """(ToCfg, ToOpts) of a call's `cfg` and `opts`. cfg: a dict over DEFAULT_CFG (its hessian key
+    gives the options) or a ToCfg, which holds no options; opts: a ToOpts or a hessian value, which
+    overrides the dict's key; None with a ToCfg means the defaults."""
+    if isinstance(cfg, L.ToCfg):
+        return cfg, make_opts(opts)
+    return make_cfg(cfg), make_opts(cfg if opts is None else opts)
+
+
+def _opts_args(o):
+    """(suffix of the entry's name, trailing arguments): the `_opts` entry when an option differs
+    from the defaults, else the entry it extends, which is that call with NULL options."""
+    return ("_opts", (C.byref(o),)) if o.hessian != L.CACTO_TO_HESS_EXACT else ("", ())
 
 
 class TO:
@@ -66,10 +109,10 @@ class TO:
         self.sys = env.sys
 
     # ------------------------------------------------------------------ the solver
-    def solve_batch(self, S0, U_init, nsteps, cfg=None, out=None):
+    def solve_batch(self, S0, U_init, nsteps, cfg=None, out=None, opts=None):
         """cacto_to_solve. S0 [E, ns] f64, U_init [E, ldU, na] f64 (the warm start's controls),
         nsteps [E] int32 (Te; < 0 skips the episode), all on the device; cfg: a dict over
-        DEFAULT_CFG. Returns a dict of device tensors S [E, ldS, ns], U [E, ldU, na], step_cost
+        DEFAULT_CFG, or a ToCfg together with opts (a ToOpts or a hessian value; _cfg_opts). Returns a dict of device tensors S [E, ldS, ns], U [E, ldU, na], step_cost
         [E, ldS], status [E] (CONVERGED / MAXITER / FAILED), iters [E], J [E, 2] (warm start's cost,
         final cost), ldS = ldU + 1. Rows past Te, and every row of a skipped episode, keep what
         `out` (the same dict, optional) held — zeros (status -1) when it is not given."""
@@ -82,32 +125,35 @@ class TO:
                        step_cost=torch.zeros(E, ldS, **f64),
                        status=torch.full((E,), -1, dtype=torch.int32, device=DEVICE),
                        iters=torch.zeros(E, dtype=torch.int32, device=DEVICE), J=torch.zeros(E, 2, **f64))
-        c = cfg if isinstance(cfg, L.ToCfg) else make_cfg(cfg)
+        c, o = _cfg_opts(cfg, opts)
         # 0 for a path the library does not know: cacto_to_solve then reports the bad config
-        nbytes = int(L.lib().raw("cacto_to_workspace_bytes_cfg")(self.sys.handle, E, ldS, C.byref(c)))
+        sfx, extra = _opts_args(o)
+        ws_bytes = L.lib().raw("cacto_to_workspace_bytes" + (sfx or "_cfg"))
+        nbytes = int(ws_bytes(self.sys.handle, E, ldS, C.byref(c), *extra))
         ws = getattr(self, "_to_ws", None)
         if ws is None or ws.numel() < nbytes:
             ws = self._to_ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=DEVICE)
-        L.lib().call("cacto_to_solve", self.sys.handle, dptr(S0, torch.float64), dptr(U_init, torch.float64), ldU,
+        L.lib().call("cacto_to_solve" + sfx, self.sys.handle, dptr(S0, torch.float64), dptr(U_init, torch.float64), ldU,
                      dptr(nsteps, torch.int32), E, ldS, C.byref(c), dptr(out["S"], torch.float64),
                      dptr(out["U"], torch.float64), dptr(out["step_cost"], torch.float64),
                      dptr(out["status"], torch.int32), dptr(out["iters"], torch.int32), dptr(out["J"], torch.float64),
-                     dptr(ws), nbytes, stream())
+                     dptr(ws), nbytes, stream(), *extra)
         return out
 
-    def solve_plan(self, cfg=None):
-        """cacto_to_solve_plan: what solve_batch runs for this system with cfg (a dict over
-        DEFAULT_CFG), as a dict: on_device (1: the whole loop is one kernel, nothing synchronises, the
+    def solve_plan(self, cfg=None, opts=None):
+        """cacto_to_solve_plan: what solve_batch runs for this system with cfg and opts (as
+        solve_batch's), as a dict: on_device (1: the whole loop is one kernel, nothing synchronises, the
         call can be captured into a graph), block_threads and lds_bytes of the solving kernel,
         launches_per_iter (kernel launches the host issues per iteration; 0 when on_device)."""
-        c = cfg if isinstance(cfg, L.ToCfg) else make_cfg(cfg)
+        c, o = _cfg_opts(cfg, opts)
         plan = L.ToPlan()
-        L.lib().call("cacto_to_solve_plan", self.sys.handle, C.byref(c), C.byref(plan))
+        sfx, extra = _opts_args(o)
+        L.lib().call("cacto_to_solve_plan" + sfx, self.sys.handle, C.byref(c), C.byref(plan), *extra)
         return {name: int(getattr(plan, name)) for name, _ in L.ToPlan._fields_}
 
-    def backward_gains_batch(self, S_traj, U_traj, nsteps, mu=0.0):
-        """cacto_to_backward_gains along S_traj [E, ldS, ns], U_traj [E, ldU, na]: a dict k [E, ldU,
-        na], K [E, ldU, na, nx], dJ [E, 3] = (sum k^T Q_u, 1/2 sum k^T Q_uu k, max |Q_u|), pd [E]
+    def backward_gains_batch(self, S_traj, U_traj, nsteps, mu=0.0, hessian="exact"):
+        """cacto_to_backward_gains (hessian: "exact" / "psd" / 0 / 1, as the cfg key) along S_traj
+        [E, ldS, ns], U_traj [E, ldU, na]: a dict k [E, ldU, na], K [E, ldU, na, nx], dJ [E, 3] = (sum k^T Q_u, 1/2 sum k^T Q_uu k, max |Q_u|), pd [E]
         (-1: Q_uu + mu I positive definite at every step, else the step where it was not; nothing
         below that step is defined)."""
         E, ldS, ldU = S_traj.shape[0], S_traj.shape[1], U_traj.shape[1]
@@ -115,9 +161,10 @@ class TO:
         f64 = dict(dtype=torch.float64, device=DEVICE)
         out = dict(k=torch.zeros(E, ldU, na, **f64), K=torch.zeros(E, ldU, na, ns - 1, **f64),
                    dJ=torch.zeros(E, 3, **f64), pd=torch.full((E,), -1, dtype=torch.int32, device=DEVICE))
-        L.lib().call("cacto_to_backward_gains", self.sys.handle, dptr(S_traj, torch.float64), ldS,
+        sfx, extra = _opts_args(make_opts(hessian))
+        L.lib().call("cacto_to_backward_gains" + sfx, self.sys.handle, dptr(S_traj, torch.float64), ldS,
                      dptr(U_traj, torch.float64), ldU, dptr(nsteps, torch.int32), E, float(mu), dptr(out["k"]),
-                     dptr(out["K"]), dptr(out["dJ"]), dptr(out["pd"]), stream())
+                     dptr(out["K"]), dptr(out["dJ"]), dptr(out["pd"]), stream(), *extra)
         return out
 
     def forward_batch(self, S_traj, U_traj, k, K, nsteps, alpha=1.0):

@@ -493,6 +493,28 @@ enum cacto_to_path {
                               * trip, poll_every is not used. Manipulator, UR5: as 0 */
 };
 
+/* Per-call options of the trajectory optimiser, beside cacto_to_cfg (whose 64 bytes are fixed): the
+ * `_opts` entries below take the arguments of the entry they are named after plus a pointer to
+ * this struct, NULL meaning the defaults; the entries without the suffix are those calls with NULL.
+ * hessian: the node Hessian l_xx the backward pass uses.
+ *   CACTO_TO_HESS_EXACT  the exact Hessian of the cost (the default).
+ *   CACTO_TO_HESS_PSD    its projection onto the positive semidefinite cone, P(H) = V max(L, 0) V^T
+ *                        with H = V L V^T (a cyclic Jacobi iteration in float64), at every running
+ *                        and terminal node, in the cost convention. With l_uu > 0 this keeps
+ *                        Q_uu = l_uu + B^T V_xx B positive definite without mu where the cost is
+ *                        concave (near the obstacles). l_x, l_u, l_uu, the dynamics, the line search,
+ *                        the mu schedule, gtol and the statuses are untouched, so the stationary
+ *                        points are the same. cacto_ddp_backward (the Sobolev labels) always uses the
+ *                        exact Hessian.
+ * An unknown hessian or a non-zero reserved word: CACTO_EINVAL (workspace query: 0), reported before
+ * the other arguments are looked at, no device work. */
+enum cacto_to_hessian { CACTO_TO_HESS_EXACT = 0, CACTO_TO_HESS_PSD = 1 };
+
+typedef struct {
+  int32_t hessian;     /* enum cacto_to_hessian */
+  int32_t reserved[3]; /* must be 0 */
+} cacto_to_opts;
+
 /* One regularised backward pass along given trajectories (cost convention, l_xu = 0):
  *   Qbar_uu = Q_uu + mu I, k = -Qbar_uu^-1 Q_u, K = -Qbar_uu^-1 Q_ux,
  *   V_x = Q_x + K^T Q_uu k + K^T Q_u + Q_ux^T k, V_xx = Q_xx + K^T Q_uu K + K^T Q_ux + Q_ux^T K
@@ -504,6 +526,9 @@ enum cacto_to_path {
 int cacto_to_backward_gains(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d, int64_t ldU,
                             const int32_t* nsteps_d, int n_ep, double mu, double* k_d, double* K_d, double* dJ_d,
                             int32_t* pd_d, void* stream);
+int cacto_to_backward_gains_opts(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d, int64_t ldU,
+                                 const int32_t* nsteps_d, int n_ep, double mu, double* k_d, double* K_d, double* dJ_d,
+                                 int32_t* pd_d, void* stream, const cacto_to_opts* opts);
 
 /* One closed-loop roll-out: u_t = ubar_t + alpha k_t + K_t (x_t - xbar_t), x_{t+1} = Env.simulate
  * (float64). S_new_d [n_ep, ldS, ns] (time column t0 + dt t), U_new_d [n_ep, ldU, na], cost_new_d
@@ -519,6 +544,10 @@ int cacto_to_forward(const cacto_sys* sys, const double* S_d, int64_t ldS, const
  * 0 on bad arguments or an unknown path. */
 size_t cacto_to_workspace_bytes(const cacto_sys* sys, int n_ep, int64_t ldS);
 size_t cacto_to_workspace_bytes_cfg(const cacto_sys* sys, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h);
+/* ... for a config (cfg_h NULL: CACTO_TO_PATH_DEFAULT) and options. The projection of
+ * CACTO_TO_HESS_PSD works in place, so the size does not depend on the Hessian mode. */
+size_t cacto_to_workspace_bytes_opts(const cacto_sys* sys, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h,
+                                     const cacto_to_opts* opts);
 
 /* The solver. S0_d [n_ep, ns] initial states (with time), U_init_d [n_ep, ldU, na] warm start.
  * Outputs: S_d [n_ep, ldS, ns], U_d [n_ep, ldU, na], step_cost_d [n_ep, ldS], status_d [n_ep] int32
@@ -541,6 +570,13 @@ int cacto_to_solve(const cacto_sys* sys, const double* S0_d, const double* U_ini
                    const int32_t* nsteps_d, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h, double* S_d,
                    double* U_d, double* step_cost_d, int32_t* status_d, int32_t* iters_d, double* J_d, void* ws_d,
                    size_t ws_bytes, void* stream);
+/* ... with options. CACTO_TO_HESS_PSD: the persistent kernels are instantiated once more with the
+ * projection in their derivative phase (the two solvers of a system still agree bit for bit); the
+ * host-issued loop runs one more kernel per iteration, over the l_xx blocks of the records. */
+int cacto_to_solve_opts(const cacto_sys* sys, const double* S0_d, const double* U_init_d, int64_t ldU,
+                        const int32_t* nsteps_d, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h, double* S_d,
+                        double* U_d, double* step_cost_d, int32_t* status_d, int32_t* iters_d, double* J_d, void* ws_d,
+                        size_t ws_bytes, void* stream, const cacto_to_opts* opts);
 
 /* What cacto_to_solve runs for a system and a config (the role cacto_rollout_plan plays for the
  * rollout: TO.py:37-100 has one host-side IPOPT call per episode and nothing to plan), so a
@@ -556,6 +592,9 @@ typedef struct {
 
 /* CACTO_EINVAL for a null argument or an unknown cfg_h->path; no device work, nothing enqueued. */
 int cacto_to_solve_plan(const cacto_sys* sys, const cacto_to_cfg* cfg_h, cacto_to_plan* out);
+/* ... with options: CACTO_TO_HESS_PSD adds one launch to launches_per_iter of a host-issued loop. */
+int cacto_to_solve_plan_opts(const cacto_sys* sys, const cacto_to_cfg* cfg_h, cacto_to_plan* out,
+                             const cacto_to_opts* opts);
 
 /* What cacto_rollout_sched runs for B episodes under a schedule (groups, workgroups), decided by the
  * same function that launches it. "eight" = the systems whose step needs no workgroup-wide dynamics
