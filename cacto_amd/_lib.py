@@ -85,6 +85,20 @@ class UpdPlan(C.Structure):
         "xcd_tiles", "pair_xcds", "per_overlap", "devwait_actor", "cus")]
 
 
+class EnsPlan(C.Structure):
+    """cacto_ens_plan: what cacto_ensemble_update launches for R replicas (cacto_ensemble_plan)."""
+    _fields_ = [(n, C.c_int32) for n in (
+        "supported", "reason", "R", "Bp", "pair_xcds", "xcd_groups", "layers", "xcds",
+        "chain_wgs", "chain_wgs_lone", "chain_threads", "chain_lds_bytes",
+        "wgrad_wgs", "wgrad_wgs_critic", "wgrad_wgs_actor", "wgrad_threads", "wgrad_lds_bytes",
+        "launches_per_update", "cus")]
+
+
+ENSEMBLE_MAX = 64
+ENS_OK, ENS_BAD_R, ENS_NOT_PAIRED, ENS_ELU, ENS_BAD_B = 0, 1, 2, 3, 4
+CACTO_EINVAL, CACTO_EUNSUPPORTED = -1, -4
+
+
 class PerPlan(C.Structure):
     """struct cacto_per_plan: which PER kernels a batch takes on a tree (cacto_per_plan)."""
     _fields_ = [(n, C.c_int32) for n in (
@@ -132,6 +146,14 @@ _SIGS = {
     "cacto_update_n": (C.c_int, [vp, C.POINTER(Nets), C.POINTER(UpdateCfg), vp, vp, C.c_int, C.c_int, vp, sz, vp]),
     "cacto_update_n_per": (C.c_int, [vp, C.POINTER(Nets), C.POINTER(UpdateCfg), vp, vp, vp, i64, i64, C.c_double, vp,
                                      vp, C.c_double, C.c_double, C.c_double, vp, C.c_int, C.c_int, vp, sz, vp]),
+    "cacto_ensemble_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.POINTER(EnsPlan)]),
+    "cacto_ensemble_create": (C.c_int, [vp, C.c_int, C.POINTER(Nets), C.POINTER(vp), C.POINTER(vp), sz,
+                                        C.POINTER(UpdateCfg), C.c_int, C.POINTER(vp)]),
+    "cacto_ensemble_destroy": (C.c_int, [vp]),
+    "cacto_ensemble_update": (C.c_int, [vp, vp, C.c_int, vp]),
+    "cacto_ensemble_outputs": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(vp)]),
+    "cacto_workspace_yv_offset": (sz, [vp, C.c_int]),
     "cacto_dp_unique_ids": (C.c_int, [vp, C.c_int]),
     "cacto_dp_attach": (C.c_int, [vp, vp, C.c_int, C.c_int]),
     "cacto_dp_detach": (C.c_int, [vp]),

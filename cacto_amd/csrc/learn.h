@@ -146,6 +146,56 @@ int launch_wgrad_adam(const cacto_sys* sys, int mode, const AdamNet& n0, const A
 int launch_soft(const cacto_sys* sys, const cacto_nets* nets, float tau, hipStream_t st);
 int launch_pipe_probe(unsigned long long* w, int role, hipStream_t st);
 
+// ---------------------------------------------------------------- R independent learners (ensemble)
+// The paired update loop (update_pipeline_pair) for R replicas of one system as one chain launch and
+// one GEMM + Adam launch per step: k_chain_ens_q4 / k_wgrad_adam_ens run the device bodies of
+// k_chain_pair_q4 / k_wgrad_adam with a replica index taken from the block index. What a replica's
+// workgroups read lives in a device table written once, when the ensemble handle is created.
+struct EnsReplica {
+  NetView C, Tg, Ac;
+  GradBufs gbc, gba;
+  float* y;
+  float* V;
+  int32_t* step;
+  AdamNet cn, an;  // critic (with its soft target update unless MC), actor
+  const double* storage;
+};
+
+// How the R replicas' chain tiles are dealt to workgroups: the one place it is decided (ens_route).
+// Block b runs on XCD b % 8 (observed dealing: it decides only which L2 serves a tile, never a
+// result). The 8 XCDs form ng = 8 / nx groups of nx (the one-learner route's pair_xcds); replica r
+// runs on group r % ng, so the replicas spread over the XCDs instead of all landing on XCDs
+// [0, nx), and the replicas of one group are stacked in layers of `per` = ceil(nt / nx) slices.
+struct EnsDeal {
+  int R, nx, ng, per, nt;  // nt: tiles per replica in this launch (2 nct paired, nct alone)
+};
+struct EnsTile {
+  int r, j;  // replica, tile; r >= R or j >= nt: a padding workgroup
+};
+__host__ __device__ inline EnsTile ens_tile_of(const EnsDeal& d, int b) {
+  const int x = b & 7, sl = b >> 3;
+  const int g = x / d.nx, lay = sl / d.per;
+  return EnsTile{lay * d.ng + g, (sl - lay * d.per) * d.nx + (x - g * d.nx)};
+}
+inline int ens_chain_grid(const EnsDeal& d) { return 8 * d.per * ((d.R + d.ng - 1) / d.ng); }
+
+enum { ENS_OK = 0, ENS_BAD_R = 1, ENS_NOT_PAIRED = 2, ENS_ELU = 3, ENS_BAD_B = 4 };
+constexpr int ENS_MAX_R = CACTO_ENSEMBLE_MAX;
+struct EnsRoute {
+  int supported, reason;  // ENS_*
+  LearnRoute one;         // the one-learner route of the batch
+  int R, nct;             // replicas, 4-sample tiles per chain
+  EnsDeal pair, lone;     // the paired steps' deal, the lone first / last step's
+  int wa_stride[3];       // k_wgrad_adam's work-list stride per mode (critic, actor, both)
+  int lds_bytes;          // chain launch
+};
+EnsRoute ens_route(const NetTopo& critic, const NetTopo& actor, bool sobolev, int B, int R, int cus);
+// mode 0: critic chains alone, 1: actor chains alone, 2: both. idx_c / idx_a: replica 0's minibatch of
+// the step; replica r's is rstride int32 further on.
+int launch_chain_ens(const cacto_sys* sys, const EnsRoute& er, const EnsReplica* tab, const ChainScalars& cs,
+                     const int32_t* idx_c, const int32_t* idx_a, long long rstride, int B, int mode, hipStream_t st);
+int launch_wgrad_adam_ens(const cacto_sys* sys, const EnsRoute& er, const EnsReplica* tab, int mode, hipStream_t st);
+
 // elu_kernels.hip: the chain kernels of a handle whose critic is the elu network (is_elu_topo);
 // launch_critic_chain / launch_actor_chain / launch_chain_pair hand over to them
 int launch_critic_chain_elu(const cacto_sys* sys, const NetView& C, const NetView& Tg, const ChainScalars& cs,

@@ -4,9 +4,12 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <string>
+#include <vector>
 
 #include "learn.h"
 
@@ -893,6 +896,163 @@ extern "C" int cacto_update_n(const cacto_sys* sys, const cacto_nets* nets, cons
                               size_t workspace_bytes, void* stream) {
   return update_n("cacto_update_n", false, sys, nets, cfg, storage_d, idx_d, nullptr, K, B, workspace_d,
                   workspace_bytes, stream);
+}
+
+// ---------------------------------------------------------------- R independent learners
+// update_pipeline_pair for R replicas (learn.h: EnsReplica, ens_route): the same K + 1 steps, each one
+// chain launch and one GEMM + Adam launch over all replicas. The handle owns the device table of
+// descriptors, written once at creation; a call passes only the indices, K and the step's offset.
+struct cacto_ensemble {
+  const cacto_sys* sys;
+  EnsRoute route;
+  ChainScalars cs;
+  EnsReplica* tab_d = nullptr;
+  int B = 0;
+  float* y[ENS_MAX_R];
+  float* V[ENS_MAX_R];
+};
+
+namespace {
+int ens_refuse(const EnsRoute& er) {
+  switch (er.reason) {
+    case ENS_OK: return CACTO_OK;
+    case ENS_BAD_R:
+      set_error("ensemble: R must be in [1, " + std::to_string(ENS_MAX_R) + "] (CACTO_ENSEMBLE_MAX)");
+      return CACTO_EINVAL;
+    case ENS_BAD_B: set_error("ensemble: B must be positive"); return CACTO_EINVAL;
+    case ENS_ELU:
+      set_error("ensemble: the elu critic has no 4-sample chain kernels; train its seeds one by one");
+      return CACTO_EUNSUPPORTED;
+    default:
+      set_error("ensemble: the batch is not paired (2 * Bp > 1024); only the paired small-batch route is built");
+      return CACTO_EUNSUPPORTED;
+  }
+}
+}  // namespace
+
+extern "C" int cacto_ensemble_plan(int nb_state, int nb_action, int critic_type, int sobolev, int B, int R, int cus,
+                                   cacto_ens_plan* out) {
+  CACTO_REQUIRE(out && nb_state >= 2 && nb_state <= CACTO_MAX_STATE && nb_action >= 1 &&
+                    nb_action <= CACTO_MAX_ACTION && critic_type >= 0 && critic_type <= 2,
+                "cacto_ensemble_plan: bad arguments");
+  const NetTopo tc = make_topo(CACTO_NET_CRITIC, nb_state, nb_action, critic_type);
+  const NetTopo ta = make_topo(CACTO_NET_ACTOR, nb_state, nb_action);
+  if (cus <= 0) cus = cu_count();
+  const EnsRoute e = ens_route(tc, ta, sobolev != 0, B, R, cus);
+  cacto_ens_plan p{};
+  p.reason = e.reason;
+  p.R = R;
+  p.cus = cus;
+  if (e.supported) {
+    const int layers = ceil_div(R, e.pair.ng);
+    p.supported = 1;
+    p.Bp = e.one.Bp;
+    p.pair_xcds = e.pair.nx;
+    p.xcd_groups = e.pair.ng;
+    p.layers = layers;
+    p.xcds = e.pair.nx * std::min(R, e.pair.ng);
+    p.chain_wgs = ens_chain_grid(e.pair);
+    p.chain_wgs_lone = ens_chain_grid(e.lone);
+    p.chain_threads = 512;
+    p.chain_lds_bytes = e.lds_bytes;
+    p.wgrad_wgs = 8 * e.wa_stride[2] * R;
+    p.wgrad_wgs_critic = 8 * e.wa_stride[0] * R;
+    p.wgrad_wgs_actor = 8 * e.wa_stride[1] * R;
+    p.wgrad_threads = 256;
+    p.wgrad_lds_bytes = (256 + 16 * 256) * (int)sizeof(float);
+    p.launches_per_update = 2;
+  }
+  *out = p;
+  return ens_refuse(e);
+}
+
+extern "C" int cacto_ensemble_create(const cacto_sys* sys, int R, const cacto_nets* nets_h,
+                                     const double* const* storages_d, void* const* workspaces_d,
+                                     size_t workspace_bytes, const cacto_update_cfg* cfg, int B, cacto_ensemble** out) {
+  CACTO_REQUIRE(sys && nets_h && storages_d && workspaces_d && cfg && out, "cacto_ensemble_create: bad arguments");
+  const EnsRoute er = ens_route(sys->critic, sys->actor, cfg->w_S != 0.0, B, R, cu_count());
+  if (int e = ens_refuse(er)) return e;
+  CACTO_REQUIRE(!sys->dp_comm[0] && !sys->dp_comm[1],
+                "cacto_ensemble_create: the handle is data parallel (cacto_dp_attach); an ensemble runs on one rank");
+  CACTO_REQUIRE(cfg->want_target_V == 0, "cacto_ensemble_create: want_target_V is not part of the paired loop");
+  std::vector<EnsReplica> tab(R);
+  cacto_ensemble* ens = new cacto_ensemble();
+  ens->sys = sys;
+  ens->route = er;
+  ens->cs = chain_scalars(cfg, er.one, B);
+  ens->B = B;
+  const int soft = cfg->MC ? 0 : 1;
+  for (int r = 0; r < R; ++r) {
+    const cacto_nets* n = nets_h + r;
+    int err = check_nets(n);
+    if (!err && !storages_d[r]) set_error("cacto_ensemble_create: null storage"), err = CACTO_EINVAL;
+    if (!err) err = [&]() -> int {
+      CHECK_WS(workspaces_d[r], workspace_bytes, B);
+      return CACTO_OK;
+    }();
+    if (err) {
+      delete ens;
+      return err;
+    }
+    const Workspace w = plan(sys, cfg->w_S != 0.0, B, static_cast<char*>(workspaces_d[r]));
+    EnsReplica& E = tab[r];
+    E.C = cacto_make_view(sys, CACTO_NET_CRITIC, n->critic_d);
+    E.Tg = cacto_make_view(sys, CACTO_NET_CRITIC, n->target_d);
+    E.Ac = cacto_make_view(sys, CACTO_NET_ACTOR, n->actor_d);
+    E.gbc = w.crit;
+    E.gba = w.act;
+    E.y = ens->y[r] = w.scal;
+    E.V = ens->V[r] = w.scal + w.Bp;
+    E.step = n->step_d;
+    E.cn = critic_adam_net(sys, n, cfg, w, soft, nullptr, n->critic_d);
+    E.an = actor_adam_net(sys, n, cfg, w);
+    E.storage = storages_d[r];
+  }
+  hipError_t he = hipMalloc(&ens->tab_d, sizeof(EnsReplica) * R);
+  if (he == hipSuccess) he = hipMemcpy(ens->tab_d, tab.data(), sizeof(EnsReplica) * R, hipMemcpyHostToDevice);
+  if (he != hipSuccess) {
+    if (ens->tab_d) (void)hipFree(ens->tab_d);
+    delete ens;
+    return hip_fail(he, "cacto_ensemble_create: device table");
+  }
+  *out = ens;
+  return CACTO_OK;
+}
+
+extern "C" int cacto_ensemble_destroy(cacto_ensemble* ens) {
+  if (!ens) return CACTO_OK;
+  if (ens->tab_d) (void)hipFree(ens->tab_d);
+  delete ens;
+  return CACTO_OK;
+}
+
+extern "C" int cacto_ensemble_update(cacto_ensemble* ens, const int32_t* idx_d, int K, void* stream) {
+  CACTO_REQUIRE(ens && idx_d && K >= 0, "cacto_ensemble_update: bad arguments");
+  hipStream_t st = as_stream(stream);
+  const int B = ens->B;
+  const long long rstride = (long long)K * B;
+  for (int t = 0; t <= K && K > 0; ++t) {
+    const int mode = t == 0 ? 0 : t < K ? 2 : 1;
+    const int32_t* idx_c = idx_d + (size_t)std::min(t, K - 1) * B;  // (unused at t == K)
+    const int32_t* idx_a = idx_d + (size_t)std::max(t - 1, 0) * B;  // (unused at t == 0)
+    if (int e = launch_chain_ens(ens->sys, ens->route, ens->tab_d, ens->cs, idx_c, idx_a, rstride, B, mode, st))
+      return e;
+    if (int e = launch_wgrad_adam_ens(ens->sys, ens->route, ens->tab_d, mode, st)) return e;
+  }
+  return CACTO_OK;
+}
+
+extern "C" int cacto_ensemble_outputs(const cacto_ensemble* ens, int r, float** y_d, float** V_d) {
+  CACTO_REQUIRE(ens && r >= 0 && r < ens->route.R && y_d && V_d, "cacto_ensemble_outputs: bad arguments");
+  *y_d = ens->y[r];
+  *V_d = ens->V[r];
+  return CACTO_OK;
+}
+
+extern "C" size_t cacto_workspace_yv_offset(const cacto_sys* sys, int B) {
+  if (!sys || B <= 0) return 0;
+  const Workspace w = plan(sys, true, B, reinterpret_cast<char*>(256));
+  return reinterpret_cast<char*>(w.scal) - reinterpret_cast<char*>(256);
 }
 
 extern "C" int cacto_update_n_dp(const cacto_sys* sys, const cacto_nets* nets, const cacto_update_cfg* cfg,

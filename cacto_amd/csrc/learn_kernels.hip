@@ -988,6 +988,48 @@ __global__ void __launch_bounds__(256) k_wgrad_adam(AdamNet n0, AdamNet n1, cons
 #endif
 }
 
+// ---------------------------------------------------------------- R independent learners (learn.h)
+// k_chain_pair_q4's two chains for R replicas in one grid: workgroup -> (replica, tile) by
+// ens_tile_of, the replica's descriptor from the device table (wave-uniform, read-only during the
+// call: scalar loads). mode 0: every tile a critic tile (the loop's first step), 1: every tile an
+// actor tile (its last), 2: critic tiles [0, nct) then actor tiles. Each tile runs q4_critic_chain /
+// q4_actor_chain on exactly the arguments the one-learner kernels give it.
+template <int NJ>
+__global__ void __launch_bounds__(Q4_THREADS)
+    k_chain_ens_q4(const SysDevice* __restrict__ sdp, const EnsReplica* __restrict__ tab, ChainScalars cs,
+                   const int32_t* __restrict__ idx_c, const int32_t* __restrict__ idx_a, long long rstride, int B,
+                   int nct, int mode, EnsDeal d) {
+  constexpr size_t bytes = sizeof(Q4CriticLds) > sizeof(Q4ActorLds) ? sizeof(Q4CriticLds) : sizeof(Q4ActorLds);
+  __shared__ __attribute__((aligned(16))) unsigned char smem[bytes];
+  const EnsTile w = ens_tile_of(d, blockIdx.x);
+  if (w.r >= d.R || w.j >= d.nt) return;
+  const EnsReplica& E = tab[w.r];
+  if (mode == 0 || (mode == 2 && w.j < nct)) {
+    q4_critic_chain(*reinterpret_cast<Q4CriticLds*>(smem), w.j, sdp, E.C, E.Tg, cs, E.storage,
+                    idx_c + (size_t)w.r * rstride, nullptr, B, E.gbc, E.y, E.V, nullptr, E.step);
+  } else {
+    q4_actor_chain<NJ>(*reinterpret_cast<Q4ActorLds*>(smem), mode == 2 ? w.j - nct : w.j, sdp, E.Ac, E.C, cs,
+                       E.storage, idx_a + (size_t)w.r * rstride, B, E.gba, E.step);
+  }
+}
+
+// k_wgrad_adam for R replicas: block b runs on XCD b % 8 and takes slot (b / 8) % stride of that
+// XCD's bin for replica (b / 8) / stride — the one-learner work list, once per replica.
+__global__ void __launch_bounds__(256) k_wgrad_adam_ens(const EnsReplica* __restrict__ tab,
+                                                        const int32_t* __restrict__ items, int stride, int mode) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int sl = blockIdx.x >> 3, r = __builtin_amdgcn_readfirstlane(sl / stride);
+  const int code = __builtin_amdgcn_readfirstlane(items[(blockIdx.x & 7) * stride + (sl - r * stride)]);
+  __shared__ float tr[256];
+  __shared__ float part[WA_MAXCH * 256];
+  if (code < 0) return;
+  const EnsReplica& E = tab[r];
+  const int l = (code >> 16) & 0xf;
+  // the work list's network bit: n1 of the paired launch is the actor; alone, n0 is the mode's network
+  if (mode == 1 || ((code >> 15) & 1)) wgrad_adam_item(E.an, code & 0x7fff, l, E.step, wave, lane, tr, part);
+  else wgrad_adam_item(E.cn, code & 0x7fff, l, E.step, wave, lane, tr, part);
+}
+
 }  // namespace cacto
 
 #ifdef CACTO_STAMPS
@@ -1330,6 +1372,111 @@ int launch_wgrad_adam(const cacto_sys* sys, int mode, const AdamNet& n0, const A
   return CACTO_OK;
 }
 
+// One mode's work list of k_wgrad_adam (cacto_build_wgrad_adam_items, below): the 8 XCD bins padded
+// to a common stride, which is returned; flat (optional): the [8][stride] item codes.
+static int wa_bins(const NetTopo& critic, const NetTopo& actor, int mode, std::vector<int32_t>* flat) {
+  std::vector<int32_t> bins[8];
+  const NetTopo* nets[2] = {&critic, &actor};
+  for (int n = 0; n < 2; ++n) {
+    if ((mode == 0 && n == 1) || (mode == 1 && n == 0)) continue;
+    const int tag = (mode == 2 && n == 1) ? 1 : 0;  // n1 in the paired launch
+    const NetTopo& t = *nets[n];
+    int base = 0;
+    for (int l = 0; l < t.L; ++l) {
+      const int IT = t.KT[l], OT = t.OT[l];
+      // bi x bo = 8 with the blocks (IT/bi) x (OT/bo) closest to square; both within the grid
+      int bi = 1;
+      double best = 1e30;
+      for (int c = 1; c <= 8; c *= 2) {
+        if (c > IT || 8 / c > OT) continue;
+        const double d = std::abs((double)IT / c - (double)OT / (8 / c));
+        if (d < best) best = d, bi = c;
+      }
+      if (best == 1e30) bi = std::max(1, std::min(IT, 8));  // grid smaller than 8 blocks
+      const int bo = std::max(1, 8 / bi);
+      for (int it = 0; it < IT; ++it)
+        for (int ot = 0; ot < OT; ++ot) {
+          const int bin = ((it * bi) / IT) * bo + std::min(bo - 1, (ot * bo) / OT);
+          bins[bin % 8].push_back((l << 16) | (tag << 15) | (base + it * OT + ot));
+        }
+      for (int ot = 0; ot < OT; ++ot) {
+        const int bin = std::min(bo - 1, (ot * bo) / OT);
+        bins[bin % 8].push_back((l << 16) | (tag << 15) | (base + IT * OT + ot));
+      }
+      base += IT * OT + OT;
+    }
+  }
+  size_t S = 4;
+  for (auto& b : bins) S = std::max(S, (b.size() + 3) / 4 * 4);
+  if (flat) {
+    flat->assign(8 * S, -1);
+    for (int x = 0; x < 8; ++x)
+      for (size_t k = 0; k < bins[x].size(); ++k) (*flat)[x * S + k] = bins[x][k];
+  }
+  return (int)S;
+}
+static int wa_stride_of(const NetTopo& critic, const NetTopo& actor, int mode) {
+  return wa_bins(critic, actor, mode, nullptr);
+}
+// The ensemble's route (learn.h): the one-learner route of the batch, which must be the paired one
+// on 4-sample tiles, and the replicas' deal over the XCDs. With R = 1 the paired steps' deal and
+// grid are k_chain_pair_q4's (tile sl * nx + b % 8 on block b, 8 * ceil(2 nct / nx) workgroups) and
+// the GEMM + Adam launches have k_wgrad_adam's grids. The lone first and last step differ from the
+// one-learner kernels' plain grid of nct workgroups: they take the same XCD deal, 8 * ceil(nct / nx)
+// workgroups (B = 64: 32 against 16), the surplus exiting at once.
+EnsRoute ens_route(const NetTopo& critic, const NetTopo& actor, bool sobolev, int B, int R, int cus) {
+  EnsRoute e{};
+  e.R = R;
+  if (B <= 0) {
+    e.reason = ENS_BAD_B;
+    return e;
+  }
+  e.one = learn_route(critic, actor, sobolev, B, cus);
+  e.reason = R < 1 || R > ENS_MAX_R ? ENS_BAD_R
+             : e.one.elu            ? ENS_ELU
+             : !e.one.paired || e.one.tile != Q4_TILE ? ENS_NOT_PAIRED
+                                                      : ENS_OK;
+  if (e.reason != ENS_OK) return e;
+  e.supported = 1;
+  e.nct = e.one.Bp / Q4_TILE;
+  const int nx = e.one.pair_xcds;
+  e.pair = EnsDeal{R, nx, 8 / nx, ceil_div(2 * e.nct, nx), 2 * e.nct};
+  e.lone = EnsDeal{R, nx, 8 / nx, ceil_div(e.nct, nx), e.nct};
+  for (int m = 0; m < 3; ++m) e.wa_stride[m] = wa_stride_of(critic, actor, m);
+  e.lds_bytes = (int)std::max(sizeof(Q4CriticLds), sizeof(Q4ActorLds));
+  return e;
+}
+
+template <int NJ>
+struct LaunchChainEns {
+  static int run(const cacto_sys* sys, const EnsRoute& er, const EnsReplica* tab, const ChainScalars& cs,
+                 const int32_t* idx_c, const int32_t* idx_a, long long rstride, int B, int mode, hipStream_t st) {
+    const EnsDeal& d = mode == 2 ? er.pair : er.lone;
+    hipLaunchKernelGGL(k_chain_ens_q4<NJ>, dim3(ens_chain_grid(d)), dim3(Q4_THREADS), 0, st, sys->dev, tab, cs, idx_c,
+                       idx_a, rstride, B, er.nct, mode, d);
+    CACTO_CHECK_HIP(hipGetLastError());
+    return CACTO_OK;
+  }
+};
+
+int launch_chain_ens(const cacto_sys* sys, const EnsRoute& er, const EnsReplica* tab, const ChainScalars& cs,
+                     const int32_t* idx_c, const int32_t* idx_a, long long rstride, int B, int mode, hipStream_t st) {
+  return dispatch_nj<LaunchChainEns>(sys->host.p, sys, er, tab, cs, idx_c, idx_a, rstride, B, mode, st);
+}
+
+int launch_wgrad_adam_ens(const cacto_sys* sys, const EnsRoute& er, const EnsReplica* tab, int mode, hipStream_t st) {
+  const int stride = sys->wa_stride[mode];
+  // as launch_wgrad_adam: one item per workgroup, its row chunks parked in part[WA_MAXCH]
+  if ((mode != 1 && er.one.critic.nch > WA_MAXCH) || (mode != 0 && er.one.actor.nch > WA_MAXCH)) {
+    set_error("k_wgrad_adam_ens: more than WA_MAXCH row chunks");
+    return CACTO_EINVAL;
+  }
+  hipLaunchKernelGGL(k_wgrad_adam_ens, dim3(8 * stride * er.R), dim3(256), 0, st, tab, sys->wa_items[mode], stride,
+                     mode);
+  CACTO_CHECK_HIP(hipGetLastError());
+  return CACTO_OK;
+}
+
 int launch_soft(const cacto_sys* sys, const cacto_nets* nets, float tau, hipStream_t st) {
   const NetTopo& t = sys->critic;
   hipLaunchKernelGGL(k_soft, dim3(std::min((t.params + 255) / 256, 1024)), dim3(256), 0, st, t, nets->critic_d,
@@ -1355,47 +1502,11 @@ using namespace cacto;
 // Code: bits 0-14 the item, bit 15 the network (n1 of the paired launch), bits 16-19 the layer
 // (so the kernel does not search AdamNet::ioff with dependent scalar loads); -1 = no item.
 int cacto_build_wgrad_adam_items(cacto_sys* sys) {
-  std::vector<int32_t> bins[3][8];
-  const NetTopo* nets[2] = {&sys->critic, &sys->actor};
   for (int mode = 0; mode < 3; ++mode) {
-    for (int n = 0; n < 2; ++n) {
-      if ((mode == 0 && n == 1) || (mode == 1 && n == 0)) continue;
-      const int tag = (mode == 2 && n == 1) ? 1 : 0;  // n1 in the paired launch
-      const NetTopo& t = *nets[n];
-      int base = 0;
-      for (int l = 0; l < t.L; ++l) {
-        const int IT = t.KT[l], OT = t.OT[l];
-        // bi x bo = 8 with the blocks (IT/bi) x (OT/bo) closest to square; both within the grid
-        int bi = 1;
-        double best = 1e30;
-        for (int c = 1; c <= 8; c *= 2) {
-          if (c > IT || 8 / c > OT) continue;
-          const double d = std::abs((double)IT / c - (double)OT / (8 / c));
-          if (d < best) best = d, bi = c;
-        }
-        if (best == 1e30) bi = std::max(1, std::min(IT, 8));  // grid smaller than 8 blocks
-        const int bo = std::max(1, 8 / bi);
-        for (int it = 0; it < IT; ++it)
-          for (int ot = 0; ot < OT; ++ot) {
-            const int bin = ((it * bi) / IT) * bo + std::min(bo - 1, (ot * bo) / OT);
-            bins[mode][bin % 8].push_back((l << 16) | (tag << 15) | (base + it * OT + ot));
-          }
-        for (int ot = 0; ot < OT; ++ot) {
-          const int bin = std::min(bo - 1, (ot * bo) / OT);
-          bins[mode][bin % 8].push_back((l << 16) | (tag << 15) | (base + IT * OT + ot));
-        }
-        base += IT * OT + OT;
-      }
-    }
-    size_t S = 4;
-    for (auto& b : bins[mode]) S = std::max(S, (b.size() + 3) / 4 * 4);
-    std::vector<int32_t> flat(8 * S, -1);
-    for (int x = 0; x < 8; ++x)
-      for (size_t k = 0; k < bins[mode][x].size(); ++k) flat[x * S + k] = bins[mode][x][k];
+    std::vector<int32_t> flat;
+    sys->wa_stride[mode] = wa_bins(sys->critic, sys->actor, mode, &flat);
     CACTO_CHECK_HIP(hipMalloc(&sys->wa_items[mode], flat.size() * sizeof(int32_t)));
     CACTO_CHECK_HIP(hipMemcpy(sys->wa_items[mode], flat.data(), flat.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    sys->wa_stride[mode] = (int)S;
   }
   return CACTO_OK;
 }
-

@@ -2,6 +2,7 @@
 evaluation stage (main.py:168, :249-252, :273, :279) as an option.
 
     python -m cacto_amd.main --system-id double_integrator --w-S 1e-2 [--plots]
+    python -m cacto_amd.main --system-id double_integrator --w-S 1e-2 --seeds 0,1,2   # train_ensemble
 
 Per loop: EP_UPDATE initial states from Env.reset (the host's `random`, as the reference), one
 RL_AC.compute_samples (roll-outs -> batched TO -> filter -> labels -> RL_Solve + ring write, all on
@@ -31,10 +32,29 @@ def parse_args(argv=None):
     that many loops), --to-path (which kernels solve the TO batch, cacto_amd.to.PATHS) and
     --accept-maxiter (keep episodes whose solve stopped at max_iter). --to-hessian (the node Hessian
     of the TO's backward pass, cacto_amd.to.HESSIANS; exact when absent), --plots, --fig-path and
-    --eval-every (the evaluation stage) are in the dict only when they are given. Returns a dict."""
+    --eval-every (the evaluation stage) and --seeds (several seeds at once, train_ensemble; not with
+    --seed or --plots) are in the dict only when they are given. Returns a dict."""
     p = argparse.ArgumentParser(prog="python -m cacto_amd.main", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument("--test-n", type=int, default=0, help="Test number")
-    p.add_argument("--seed", type=int, default=0, help="random and numpy.random seed")
+    seed_given = []
+
+    class _Seed(argparse.Action):
+        def __call__(self, parser, namespace, values, option_string=None):
+            setattr(namespace, self.dest, values)
+            seed_given.append(option_string)
+
+    def _seed_list(text):
+        try:
+            out = [int(s) for s in text.split(",")]
+        except ValueError:
+            raise argparse.ArgumentTypeError("a comma-separated list of integers, e.g. 0,1,2")
+        if len(set(out)) != len(out):
+            raise argparse.ArgumentTypeError("the seeds must differ")
+        return out
+    p.add_argument("--seed", type=int, default=0, action=_Seed, help="random and numpy.random seed")
+    p.add_argument("--seeds", type=_seed_list, default=argparse.SUPPRESS,
+                   help="Train these seeds at once on one GPU (train_ensemble), e.g. 0,1,2: seed k runs as N_try "
+                        "test-n + k's position; not with --seed or --plots")
     p.add_argument("--system-id", type=str, default="single_integrator", choices=sorted(SYSTEM_MAP),
                    help="System-id")
     p.add_argument("--recover-training-flag", action="store_true", help="Flag to recover training")
@@ -53,7 +73,13 @@ def parse_args(argv=None):
                    help="Where --plots writes (default: 'Results <system-id>/Figures')")
     p.add_argument("--eval-every", type=int, default=argparse.SUPPRESS,
                    help="With --plots: evaluate in every K-th loop only (default: 1)")
-    return vars(p.parse_args(argv))
+    args = vars(p.parse_args(argv))
+    if "seeds" in args:
+        if seed_given:
+            p.error("--seed and --seeds exclude each other")
+        if args.get("plots"):
+            p.error("--plots is not available with --seeds: the evaluation stage draws host random numbers")
+    return args
 
 
 def train_kwargs(args):
@@ -171,12 +197,144 @@ def train(conf, seed=0, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=False, n_l
                 evaluation_seconds=dict(plot_fun.seconds) if evaluate else None)
 
 
+class HostRng:
+    """One replica's copy of the two process-global generators train draws from — `random`
+    (Env.reset) and `numpy.random` (ReplayBuffer.sample_indices) — seeded as train seeds them. Used
+    as a context manager around that replica's host draws: the replica's states are swapped into the
+    globals on entry and saved back on exit (the globals get their own state back), so the replica
+    sees exactly the draws of its solo run whatever the other replicas draw in between."""
+
+    def __init__(self, seed):
+        keep = random.getstate(), np.random.get_state()
+        random.seed(seed)
+        np.random.seed(seed)
+        self.state = random.getstate(), np.random.get_state()
+        random.setstate(keep[0])
+        np.random.set_state(keep[1])
+
+    def __enter__(self):
+        self._keep = random.getstate(), np.random.get_state()
+        random.setstate(self.state[0])
+        np.random.set_state(self.state[1])
+        return self
+
+    def __exit__(self, *exc):
+        self.state = random.getstate(), np.random.get_state()
+        random.setstate(self._keep[0])
+        np.random.set_state(self._keep[1])
+        return False
+
+
+def train_ensemble(conf, seeds, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=False, n_loops=None, weights=None,
+                   recover_training=None, log=print):
+    """train for every seed of `seeds` at once (the reference's ten-seed sets,
+    generate_tests_set_script.py) in one process on one GPU: one Env, one TO, per seed an NN, an
+    RL_AC (replica r runs as N_try + r) and a replay buffer; per loop one Ensemble.compute_samples
+    (every replica's roll-outs, ONE TO solve over all their episodes) and one
+    Ensemble.learn_and_update (one chain launch and one GEMM + Adam launch per step for all
+    replicas). Each seed's networks, Adam state, replay buffer, counts and returns equal those of
+    train(conf, seed=seed, N_try=N_try + r, ...), bit for bit: every replica has its own copy of the
+    host generators (HostRng), swapped in around its draws in train's order.
+
+    train's arguments without the evaluation stage (which draws host random numbers of its own).
+    `weights`: one setup_model dict for all replicas, or a list of one per seed. `recover_training`:
+    (path, N_try, step) as train's, read as the checkpoints of an earlier ensemble run: replica r
+    starts from <path>/N_try_<N_try + r>/*_<step>.h5 — what train(seed, N_try=N_try + r,
+    recover_training=(path, N_try + r, step)) loads — so N_try must be an integer; the update counter
+    starts at step. Uniform replay, the
+    paired small-batch route, one rank (Ensemble's ValueErrors otherwise). A loop in which some
+    replica keeps no episode raises RuntimeError naming the seed. Returns one train-shaped dict per
+    seed (evaluation fields empty), in the order of `seeds`."""
+    from .environment import make_env
+    from .neural_network import NN
+    from .replay_buffer import ReplayBuffer
+    from .rl import RL_AC, Ensemble
+    from .to import TO
+    seeds = [int(s) for s in seeds]
+    if not seeds:
+        raise ValueError("train_ensemble: no seeds")
+    if conf.prioritized_replay_alpha != 0:
+        raise ValueError("train_ensemble: PER replay buffers are not supported (uniform replay only); train those "
+                         "seeds with train")
+    R = len(seeds)
+    rngs = [HostRng(s) for s in seeds]
+    env = make_env(conf)
+    TrOp = TO(env, conf, w_S)
+    learners, buffers = [], []
+    update_step_counter = int(recover_training[2]) if recover_training is not None else 0
+    if recover_training is not None:
+        try:
+            n_try_rec = int(recover_training[1])
+        except (TypeError, ValueError):
+            raise ValueError("train_ensemble: recover_training = (path, N_try, step) needs an integer N_try: replica r "
+                             "recovers from N_try + r, got %r" % (recover_training[1],))
+    for r, seed in enumerate(seeds):
+        with rngs[r]:
+            rl = RL_AC(env, NN(env, conf, w_S, seed=seed), conf, N_try + r)
+            buffers.append(ReplayBuffer(conf))
+            if getattr(conf, "NNs_path", None):
+                os.makedirs(os.path.join(conf.NNs_path, "N_try_%s" % (N_try + r)), exist_ok=True)
+            rec = None if recover_training is None else (recover_training[0], n_try_rec + r, recover_training[2])
+            rl.setup_model(recover_training=rec, weights=weights[r] if isinstance(weights, (list, tuple)) else weights)
+            if getattr(conf, "NNs_path", None):
+                rl.RL_save_weights(update_step_counter)
+            learners.append(rl)
+    ens = Ensemble(learners, host_rng=lambda r: rngs[r])
+    ens.plan(conf.BATCH_SIZE)       # refuse an unsupported batch / critic before any work
+    n_sched = len(conf.UPDATE_LOOPS)
+    loops = n_sched if n_loops is None else min(int(n_loops), n_sched)
+    ep_arr_idx = [0] * R
+    ep_reward_arr = [np.zeros(int(conf.EP_UPDATE) * n_sched) * np.nan for _ in range(R)]
+    counts_per_loop = [[] for _ in range(R)]
+    for ep in range(loops):
+        ics = []
+        for r in range(R):
+            with rngs[r]:
+                ics.append([env.reset() for _ in range(conf.EP_UPDATE)])
+        res = ens.compute_samples(ep, ics, TrOp, buffers, cfg=to_cfg, accept_maxiter=accept_maxiter)
+        for r in range(R):
+            counts_per_loop[r].append({k: res[r][k] for k in ("rows", "n_kept", "zero_length", "nan_rollouts",
+                                                              "converged", "maxiter", "failed")})
+        for r in range(R):
+            if res[r]["n_kept"] == 0:
+                raise RuntimeError("seed %d (N_try %d), loop %d: no episode of %d was kept (%s)"
+                                   % (seeds[r], N_try + r, ep, conf.EP_UPDATE, counts_per_loop[r][-1]))
+        update_step_counter = ens.learn_and_update(update_step_counter, buffers, ep)
+        for r in range(R):
+            n, ep_return = res[r]["n_kept"], res[r]["ep_return"]
+            ep_reward_arr[r][ep_arr_idx[r]:ep_arr_idx[r] + n] = ep_return
+            ep_arr_idx[r] += n
+            for i in range(n):
+                log("N_try {} Episode  {}  --->   Return = {}".format(N_try + r, ep * n + i, ep_return[i]))
+        if hasattr(conf, "NUPDATES") and update_step_counter > conf.NUPDATES:
+            break
+    if getattr(conf, "NNs_path", None):
+        for rl in learners:
+            rl.RL_save_weights()
+    ens.close()
+    return [dict(update_step_counter=update_step_counter, ep_reward_arr=ep_reward_arr[r],
+                 counts_per_loop=counts_per_loop[r], RLAC=learners[r], buffer=buffers[r], evaluation=[], returns=None,
+                 evaluation_seconds=None, seed=seeds[r], N_try=N_try + r) for r in range(R)]
+
+
 def main(argv=None):
     args = parse_args(argv)
     system_id, kw = train_kwargs(args)
     conf = load_conf(system_id)
     if not getattr(conf, "NNs_path", None):
         conf.NNs_path = os.path.join(os.getcwd(), "Results " + system_id, "NNs")
+    if args.get("seeds") is not None:
+        kw.pop("seed")
+        recover = None
+        if kw.pop("recover"):
+            recover = (conf.NNs_path_rec, conf.N_try_rec, conf.update_step_counter_rec)
+        print("System: {} - N_try = {} .. {} (seeds {})".format(conf.system_id, kw["N_try"],
+                                                                 kw["N_try"] + len(args["seeds"]) - 1, args["seeds"]))
+        outs = train_ensemble(conf, args["seeds"], recover_training=recover, log=print, **kw)
+        for o in outs:
+            print("seed {} (N_try {}): updates {}  kept per loop: {}".format(
+                o["seed"], o["N_try"], o["update_step_counter"], [c["n_kept"] for c in o["counts_per_loop"]]))
+        return outs
     if kw.get("evaluate") and (args.get("fig_path") or not getattr(conf, "Fig_path", None)):
         conf.Fig_path = args.get("fig_path") or os.path.join(os.getcwd(), "Results " + system_id, "Figures")
     recover = None

@@ -661,6 +661,17 @@ class RL_AC:
         of COUNTERS (rows, kept as n_kept, ...), ep_return (host float64, kept episodes in order) and
         dev, the device tensors S, U, step_cost, status, iters, dVdx (None with w_S == 0), EE_TO, and
         with env_RL S_RL, R_RL, EE_RL."""
+        res, pre = self.samples_rollout(ep, ICS_list)
+        if pre is None:
+            return res
+        sol = TrOp.solve_batch(pre["S0"], pre["warm"], pre["live"], cfg=cfg)
+        return self.samples_collect(res, pre, sol, TrOp, buffer, accept_maxiter)
+
+    def samples_rollout(self, ep, ICS_list):
+        """compute_samples up to its TrOp.solve_batch: the result dict with its counters at zero, and
+        the solve's inputs — dict(E, T, S0 [E, ns], n [E] int32, roll_status [E], warm [E, T, na] f64,
+        live [E] int32 (NSTEPS_SH, or -1 for an episode the roll-out dropped)), all on the device —
+        or None when no episode has a step to take (nothing was launched)."""
         ICS = np.asarray(ICS_list, dtype=np.float64).reshape(len(ICS_list), -1)
         E = ICS.shape[0]
         ns_ = np.array([self.nsteps_sh(s) for s in ICS], dtype=np.int32)
@@ -669,14 +680,21 @@ class RL_AC:
         res["zero_length"] = int((ns_ <= 0).sum())
         T = int(ns_.max()) if E else 0
         if T <= 0:
-            return res
+            return res, None
         na = self.conf.nb_action
         inputs = self.rollout_inputs(ICS, ns_)
         S0_d, n_d = inputs[0], inputs[1]
         roll = self.rollout_batch(ICS, ns_, T, ep=ep, want=("S", "A"), inputs=inputs)
         warm = roll["A"].double() if ep != 0 else torch.zeros(E, T, na, dtype=torch.float64, device=DEVICE)
         live = torch.where((roll["status"] == 0) & (n_d > 0), n_d, torch.full_like(n_d, -1))
-        sol = TrOp.solve_batch(S0_d, warm, live, cfg=cfg)
+        return res, dict(E=E, T=T, S0=S0_d, n=n_d, roll_status=roll["status"], warm=warm, live=live)
+
+    def samples_collect(self, res, pre, sol, TrOp, buffer, accept_maxiter=False):
+        """compute_samples from its TrOp.solve_batch on: `sol` is the solve of samples_rollout's
+        inputs `pre` (S [E, T + 1, ns], U [E, T, na], step_cost [E, T + 1], status, iters). Fills and
+        returns `res`."""
+        E, T, S0_d, n_d = pre["E"], pre["T"], pre["S0"], pre["n"]
+        roll = dict(status=pre["roll_status"])
         kept_d = torch.empty(E, dtype=torch.int32, device=DEVICE)
         off_d = torch.empty(E + 1, dtype=torch.int64, device=DEVICE)
         counts_d = torch.empty(8, dtype=torch.int64, device=DEVICE)
@@ -828,3 +846,195 @@ class RL_AC:
                 res.append((ICS[k].copy(), S[k, :n + 1].copy(), A[k, :n].copy() if ep != 0 else np.zeros((n, na)),
                             n, 1))
         return res
+
+
+class Ensemble:
+    """R independent RL_AC learners of one system trained together on one GPU — the reference's
+    ten-seed sets (generate_tests_set_script.py: ten `main.py --seed=...` runs per system) as one
+    process. Every learner is built on the same Env (one system handle) with its own NN(env, conf,
+    w_S, seed=...) and its own replay buffer; one TO serves them all. The K updates of a loop run
+    as `cacto_ensemble_update` (one chain launch and one GEMM + Adam launch per step for all
+    replicas), the TO batch of a loop as one solve_batch over every replica's episodes. Each
+    replica's results equal those of the same learner trained alone, bit for bit.
+
+    Built for the paired small-batch route only (RL_AC.update_plan's `paired` with 4-sample tiles:
+    a sine or sine-elu critic and 2 * Bp <= 1024), uniform replay, one rank; anything else raises
+    ValueError.
+
+    rngs: per replica, the generator ReplayBuffer.sample_indices draws from (None: the global numpy
+    RNG for all). host_rng: optional callable r -> context manager entered around replica r's host
+    random draws (cacto_amd.main.train_ensemble swaps the process-global generators' states in)."""
+
+    def __init__(self, learners, rngs=None, host_rng=None):
+        self.learners = list(learners)
+        if not self.learners:
+            raise ValueError("Ensemble: no learners")
+        first = self.learners[0]
+        self.conf, self.sys, self.env = first.conf, first.sys, first.env
+        for rl in self.learners[1:]:
+            if rl.sys is not self.sys or rl.conf is not self.conf:
+                raise ValueError("Ensemble: every learner must be built on the same Env / system handle")
+            if float(rl.w_S) != float(first.w_S):
+                raise ValueError("Ensemble: the learners' w_S differ")
+        if len(self.learners) > L.ENSEMBLE_MAX:
+            raise ValueError("Ensemble: at most %d learners (CACTO_ENSEMBLE_MAX)" % L.ENSEMBLE_MAX)
+        self.rngs = list(rngs) if rngs is not None else None
+        self.host_rng = host_rng
+        self._handle = None
+        self._key = None
+        self._keep = None
+
+    def __len__(self):
+        return len(self.learners)
+
+    def _ctx(self, r):
+        import contextlib
+        return self.host_rng(r) if self.host_rng is not None else contextlib.nullcontext()
+
+    # ---- the plan and the refusals ----
+    def plan(self, B=None, R=None):
+        """cacto_ensemble_plan for a batch of B (default conf.BATCH_SIZE) and R replicas (default
+        len(self)) as a dict (cacto_ens_plan in the header). Raises ValueError for what is refused."""
+        B = int(self.conf.BATCH_SIZE if B is None else B)
+        R = len(self.learners) if R is None else int(R)
+        ctype = {"sine": 0, "sine-elu": 1, "elu": 2}[getattr(self.sys, "critic_type", "sine")]
+        plan = L.EnsPlan()
+        rc = L.lib().raw("cacto_ensemble_plan")(self.conf.nb_state, self.conf.nb_action, ctype,
+                                                int(float(self.learners[0].w_S) != 0.0), B, R, 0, C.byref(plan))
+        if rc != 0:
+            raise ValueError("Ensemble: %s" % L.lib().dll.cacto_last_error().decode(errors="replace"))
+        return {name: getattr(plan, name) for name, _ in L.EnsPlan._fields_}
+
+    def _check(self, buffers, B):
+        if len(buffers) != len(self.learners):
+            raise ValueError("Ensemble: %d buffers for %d learners" % (len(buffers), len(self.learners)))
+        for b in buffers:
+            if getattr(b, "prioritized", False):
+                kind = "ReLO" if getattr(b, "RB_type", "PER") == "ReLO" else "PER"
+                raise ValueError("Ensemble: %s replay buffers are not supported (uniform replay only); train "
+                                 "those seeds with cacto_amd.main.train" % kind)
+        if any(rl._dp for rl in self.learners):
+            raise ValueError("Ensemble: data-parallel learners are not supported (one rank)")
+        self.plan(B)
+
+    # ---- cacto_ensemble_update ----
+    def _ensure(self, storages, B):
+        ws = [rl.workspace(B) for rl in self.learners]
+        # every address the device table holds: a buffer that moved (setup_model again, a grown
+        # workspace, another storage) makes a new handle
+        key = (B, tuple(s.data_ptr() for s in storages), tuple(w.data_ptr() for w in ws),
+               tuple(getattr(rl.nets, name) for rl in self.learners for name, _ in L.Nets._fields_))
+        if self._handle is not None and key == self._key:
+            return
+        self.close()
+        R = len(self.learners)
+        nets = (L.Nets * R)(*[rl.nets for rl in self.learners])
+        st = (C.c_void_p * R)(*[dptr(s, torch.float64).value for s in storages])
+        wp = (C.c_void_p * R)(*[w.data_ptr() for w in ws])
+        cfg = self.learners[0]._cfg_for(B)
+        h = C.c_void_p()
+        L.lib().call("cacto_ensemble_create", self.sys.handle, R, nets, st, wp, min(w.numel() for w in ws) * 4,
+                     C.byref(cfg), B, C.byref(h))
+        self._handle, self._key, self._keep = h, key, (list(storages), ws)
+
+    def close(self):
+        """Destroys the ensemble handle (after the device has finished its last update)."""
+        if self._handle is not None:
+            torch.cuda.synchronize()
+            L.lib().raw("cacto_ensemble_destroy")(self._handle)
+            self._handle = self._key = self._keep = None
+
+    def __del__(self):
+        try:
+            if not torch.cuda.is_current_stream_capturing():
+                self.close()
+        except Exception:
+            pass
+
+    def update_rows_n(self, storages, idx_steps):
+        """K consecutive RL.py:101-118 updates of every replica in one call (cacto_ensemble_update):
+        storages — each replica's replay rows; idx_steps [R, K, B] int32 on the device, replica r's
+        minibatch of update t at idx_steps[r, t], indexing storages[r]. Replica r ends bit-identical
+        to self.learners[r].update_rows_n(storages[r], idx_steps[r]) run alone. Asynchronous on the
+        current stream; capturable into a graph once the handle exists (the first call creates it,
+        also one with K = 0, which launches nothing)."""
+        R, K, B = (int(v) for v in idx_steps.shape)
+        if R != len(self.learners) or len(storages) != R:
+            raise ValueError("Ensemble.update_rows_n: idx_steps [R, K, B] and storages need R = %d" % len(self.learners))
+        if any(rl._dp for rl in self.learners):
+            raise ValueError("Ensemble: data-parallel learners are not supported (one rank)")
+        self.plan(B)
+        self._ensure(storages, B)
+        if K == 0:
+            return
+        L.lib().call("cacto_ensemble_update", self._handle, dptr(idx_steps.contiguous(), torch.int32), K, stream())
+
+    def outputs(self, r, B):
+        """Replica r's y and V ([B] float32 copies) of its last critic step."""
+        y, V = C.c_void_p(), C.c_void_p()
+        L.lib().call("cacto_ensemble_outputs", self._handle, int(r), C.byref(y), C.byref(V))
+        ws = self._keep[1][r]
+        oy, oV = (y.value - ws.data_ptr()) // 4, (V.value - ws.data_ptr()) // 4
+        return ws[oy:oy + B].clone(), ws[oV:oV + B].clone()
+
+    # ---- RL.py:120-143 per replica ----
+    def learn_and_update(self, update_step_counter, buffers, ep):
+        """RL_AC.learn_and_update for every replica: each replica's UPDATE_LOOPS[ep] minibatches drawn
+        up front from its own generator, the updates between two checkpoint saves as one ensemble
+        call, and _after_step per replica, so every replica writes the reference's checkpoints under
+        its own N_try. Returns the update counter (the same for every replica)."""
+        n = int(self.conf.UPDATE_LOOPS[ep])
+        B = int(self.conf.BATCH_SIZE)
+        self._check(buffers, B)
+        idx = []
+        for r, b in enumerate(buffers):
+            with self._ctx(r):
+                idx.append(b.sample_indices(n, self.rngs[r] if self.rngs is not None else None))
+        idx_all = torch.stack(idx)                               # [R, n, B]
+        storages = [b.storage for b in buffers]
+        i = 0
+        while i < n:
+            k = min(n - i, self.conf.save_interval - update_step_counter % self.conf.save_interval)
+            self.update_rows_n(storages, idx_all[:, i:i + k].contiguous())
+            for _ in range(k):
+                for rl in self.learners:
+                    nxt = rl._after_step(update_step_counter)
+                update_step_counter = nxt
+            i += k
+        return update_step_counter
+
+    # ---- main.py:174-195 for every replica, one TO solve ----
+    def compute_samples(self, ep, ICS_lists, TrOp, buffers, cfg=None, accept_maxiter=False):
+        """RL_AC.compute_samples for every replica with ONE TrOp.solve_batch: per replica the roll-out
+        with its own actor (samples_rollout), then one solve over all replicas' episodes (start
+        states, warm starts and live lengths concatenated, the warm starts padded to the largest
+        horizon), then per replica, on its slice of the solution, samples_collect. The solver
+        treats every episode on its own, so a replica's slice equals its solo solve. Returns one
+        compute_samples dict per replica."""
+        if len(ICS_lists) != len(self.learners) or len(buffers) != len(self.learners):
+            raise ValueError("Ensemble.compute_samples: one ICS list and one buffer per learner")
+        pres = [rl.samples_rollout(ep, ics) for rl, ics in zip(self.learners, ICS_lists)]
+        live = [(r, pre) for r, (_, pre) in enumerate(pres) if pre is not None]
+        out = [res for res, _ in pres]
+        if not live:
+            return out
+        na = self.conf.nb_action
+        Tmax = max(pre["T"] for _, pre in live)
+        Etot = sum(pre["E"] for _, pre in live)
+        warm = torch.zeros(Etot, Tmax, na, dtype=torch.float64, device=DEVICE)
+        a = 0
+        for _, pre in live:
+            warm[a:a + pre["E"], :pre["T"]] = pre["warm"]
+            a += pre["E"]
+        sol = TrOp.solve_batch(torch.cat([pre["S0"] for _, pre in live]).contiguous(), warm,
+                               torch.cat([pre["live"] for _, pre in live]).contiguous(), cfg=cfg)
+        a = 0
+        for r, pre in live:
+            E, T = pre["E"], pre["T"]
+            part = dict(S=sol["S"][a:a + E, :T + 1].contiguous(), U=sol["U"][a:a + E, :T].contiguous(),
+                        step_cost=sol["step_cost"][a:a + E, :T + 1].contiguous(),
+                        status=sol["status"][a:a + E].contiguous(), iters=sol["iters"][a:a + E].contiguous(),
+                        J=sol["J"][a:a + E].contiguous())
+            a += E
+            out[r] = self.learners[r].samples_collect(out[r], pre, part, TrOp, buffers[r], accept_maxiter)
+        return out

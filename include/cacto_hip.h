@@ -31,6 +31,8 @@
  *   cacto_update           RL_AC.update + update_target (one learn_and_update iteration, RL.py:122-137)
  *   cacto_update_n[_per]   the learn_and_update loop RL.py:120-143 for K updates (with PER:
  *                          sample -> update -> priority update), pipelined on two streams
+ *   cacto_ensemble_*       the same loop (RL.py:120-143) for R independent learners of one system —
+ *                          the ten-seed sets of generate_tests_set_script.py — in one call
  *   cacto_buffer_gather    ReplayBuffer.sample row gather replay_buffer.py:47-61
  *   cacto_buffer_add       ReplayBuffer.add ring write replay_buffer.py:25-36
  *   cacto_rl_solve_add     RL_AC.RL_Solve n-step targets RL.py:145-189 fused with the
@@ -341,6 +343,84 @@ int cacto_update_n_per(const cacto_sys* sys, const cacto_nets* nets, const cacto
                        int64_t max_idx, double beta, const double* uniforms_d, double* exp_counter_d,
                        double fresh_factor, double eps, double alpha, double* max_priority_d, int K, int B,
                        void* workspace_d, size_t workspace_bytes, void* stream);
+
+/* ---- R independent learners of one system (the ten-seed sets: generate_tests_set_script.py writes
+ * ten `main.py --seed=...` runs per system, n_runs = 10; each runs the loop of RL.py:120-143) ----
+ * cacto_update_n's paired small-batch loop for R replicas — each with its own networks, Adam state,
+ * counters and replay storage, all of one system handle — as ONE chain launch and ONE weight-gradient
+ * + Adam launch per step, whatever R is (K + 1 steps per call, 2 launches each). Replica r's networks,
+ * moments, counters, y and V equal those of cacto_update_n run alone on replica r's inputs, bit for
+ * bit: every tile runs the same device code on the same inputs, and only the dealing of tiles to
+ * workgroups (cacto_ens_plan) differs. Only the paired route on 4-sample tiles is built: a sine (or,
+ * in the sine-elu build, sine-elu) critic, 2 * Bp <= 1024, uniform replay, one rank. */
+#define CACTO_ENSEMBLE_MAX 64 /* replicas per ensemble handle */
+typedef struct cacto_ensemble cacto_ensemble;
+
+/* reason codes of cacto_ens_plan.reason */
+#define CACTO_ENS_OK 0
+#define CACTO_ENS_BAD_R 1      /* R < 1 or R > CACTO_ENSEMBLE_MAX            (CACTO_EINVAL) */
+#define CACTO_ENS_NOT_PAIRED 2 /* 2 * Bp > 1024: the batch is not paired     (CACTO_EUNSUPPORTED) */
+#define CACTO_ENS_ELU 3        /* the elu critic (critic_type 2)             (CACTO_EUNSUPPORTED) */
+#define CACTO_ENS_BAD_B 4      /* B <= 0                                     (CACTO_EINVAL) */
+
+/* What cacto_ensemble_update launches. The 8 XCDs form xcd_groups = 8 / pair_xcds groups (pair_xcds:
+ * the one-learner route's); replica r runs on group r % xcd_groups, stacked in `layers`. With R = 1
+ * the workgroup counts are the one-learner route's. */
+typedef struct {
+  int32_t supported;
+  int32_t reason;          /* CACTO_ENS_* */
+  int32_t R;
+  int32_t Bp;
+  int32_t pair_xcds;       /* XCDs one replica's chain tiles run on */
+  int32_t xcd_groups;
+  int32_t layers;          /* ceil(R / xcd_groups) */
+  int32_t xcds;            /* XCDs the chain launch uses */
+  int32_t chain_wgs;       /* workgroups of a paired step's chain launch (steps 1 .. K - 1) */
+  int32_t chain_wgs_lone;  /* ... of the first (critic alone) and last (actor alone) step's */
+  int32_t chain_threads;
+  int32_t chain_lds_bytes;
+  int32_t wgrad_wgs;       /* workgroups of a paired step's GEMM + Adam launch */
+  int32_t wgrad_wgs_critic; /* ... of the first step's */
+  int32_t wgrad_wgs_actor;  /* ... of the last step's */
+  int32_t wgrad_threads;
+  int32_t wgrad_lds_bytes;
+  int32_t launches_per_update; /* 2 (K + 1 steps of 2 launches per call of K updates) */
+  int32_t cus;
+} cacto_ens_plan;
+
+/* The plan for a system of nb_state / nb_action with critic_type (0 sine, 1 sine-elu, 2 elu), sobolev
+ * (w_S != 0), batch B, R replicas and `cus` compute units (<= 0: this device's, 256 without one). Needs
+ * no handle and no GPU. Always fills *out; returns CACTO_OK when supported, else the code beside the
+ * reason above with a message in cacto_last_error. */
+int cacto_ensemble_plan(int nb_state, int nb_action, int critic_type, int sobolev, int B, int R, int cus,
+                        cacto_ens_plan* out);
+
+/* Creates the handle that owns the device table of the R replicas' descriptors (written once, here).
+ * nets_h [R], storages_d [R] (each replica's replay rows), workspaces_d [R] (each workspace_bytes >=
+ * cacto_workspace_bytes(sys, B), 256-byte aligned, distinct) are host arrays; what they point to, and
+ * `sys`, must outlive the handle and stay where they are. cfg is copied (want_target_V must be 0).
+ * Refused with CACTO_EINVAL: null arguments, R out of range, a workspace that is too small, a handle
+ * with data-parallel communicators attached (cacto_dp_attach); with CACTO_EUNSUPPORTED: a batch that
+ * is not paired, the elu critic. Allocates and copies (synchronous); not for use inside a capture. */
+int cacto_ensemble_create(const cacto_sys* sys, int R, const cacto_nets* nets_h, const double* const* storages_d,
+                          void* const* workspaces_d, size_t workspace_bytes, const cacto_update_cfg* cfg, int B,
+                          cacto_ensemble** out);
+/* Frees the table. The caller orders it after the handle's last update (e.g. a stream synchronise). */
+int cacto_ensemble_destroy(cacto_ensemble* ens);
+/* K consecutive updates of every replica. idx_d: int32 [R][K][B], replica-major — replica r's
+ * minibatch of update t at idx_d + (r * K + t) * B — indexing that replica's storage. Asynchronous on
+ * `stream`: kernel launches only, no host synchronisation, no allocation, nothing read from the
+ * environment, so a call can be captured into a hipGraph. K == 0 is a no-op. */
+int cacto_ensemble_update(cacto_ensemble* ens, const int32_t* idx_d, int K, void* stream);
+/* Diagnostics (no reference counterpart; the training loop needs neither): where the paired loops
+ * leave the reward-to-go y and the critic value V of their last critic step, so that a test can
+ * compare them between the ensemble and the one-learner call.
+ * The device addresses of replica r's y [Bp] and V [Bp] (inside its workspace). */
+int cacto_ensemble_outputs(const cacto_ensemble* ens, int r, float** y_d, float** V_d);
+/* Diagnostics: byte offset, in a workspace of cacto_workspace_bytes(sys, B), of the y [Bp] that
+ * cacto_update_n's paired route leaves of its last critic step; V [Bp] follows it. 0 for bad
+ * arguments. */
+size_t cacto_workspace_yv_offset(const cacto_sys* sys, int B);
 
 /* Data-parallel K-update loop (RL.py:101-118 per update, replaces the two blocking all-reduces of
  * learn_and_update's DP form with one per update). The host runs K + 1 steps; step t computes the
