@@ -64,6 +64,12 @@ class ToOpts(C.Structure):
     _fields_ = [("hessian", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class ToBox(C.Structure):
+    """cacto_to_box: hard control limits of the trajectory optimiser (the `_box` entries)."""
+    _fields_ = [("mode", C.c_int32), ("reserved", C.c_int32), ("lo", C.c_double * MAX_ACTION),
+                ("hi", C.c_double * MAX_ACTION)]
+
+
 class ToPlan(C.Structure):
     """cacto_to_plan: what cacto_to_solve runs for a system and a config (cacto_to_solve_plan)."""
     _fields_ = [("on_device", C.c_int32), ("block_threads", C.c_int32), ("lds_bytes", C.c_int32),
@@ -111,6 +117,7 @@ WG_FUSED, WG_SPLIT, WG_BIG = 0, 1, 2
 CACTO_TO_CONVERGED, CACTO_TO_MAXITER, CACTO_TO_FAILED = 0, 1, 2
 CACTO_TO_PATH_DEFAULT, CACTO_TO_PATH_WAVE = 0, 1
 CACTO_TO_HESS_EXACT, CACTO_TO_HESS_PSD = 0, 1
+CACTO_TO_BOUNDS_NONE, CACTO_TO_BOUNDS_BOX = 0, 1
 PER_UPDATE_SET, PER_UPDATE_SUB, PER_UPDATE_CHAIN = 0, 1, 2
 PER_RUN_SUB, PER_RUN_EMPTY = 256, 0x7f7f7f7f
 
@@ -187,6 +194,15 @@ _SIGS = {
     "cacto_to_solve_opts": (C.c_int, [vp, vp, vp, i64, vp, C.c_int, i64, C.POINTER(ToCfg), vp, vp, vp, vp, vp, vp, vp,
                                       sz, vp, C.POINTER(ToOpts)]),
     "cacto_to_solve_plan_opts": (C.c_int, [vp, C.POINTER(ToCfg), C.POINTER(ToPlan), C.POINTER(ToOpts)]),
+    "cacto_to_backward_gains_box": (C.c_int, [vp, vp, i64, vp, i64, vp, C.c_int, C.c_double, vp, vp, vp, vp, vp,
+                                              C.POINTER(ToOpts), C.POINTER(ToBox)]),
+    "cacto_to_forward_box": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp, C.c_int, C.c_double, vp, vp, vp, vp,
+                                       C.POINTER(ToBox)]),
+    "cacto_to_workspace_bytes_box": (sz, [vp, C.c_int, i64, C.POINTER(ToCfg), C.POINTER(ToOpts), C.POINTER(ToBox)]),
+    "cacto_to_solve_box": (C.c_int, [vp, vp, vp, i64, vp, C.c_int, i64, C.POINTER(ToCfg), vp, vp, vp, vp, vp, vp, vp,
+                                     sz, vp, C.POINTER(ToOpts), C.POINTER(ToBox)]),
+    "cacto_to_solve_plan_box": (C.c_int, [vp, C.POINTER(ToCfg), C.POINTER(ToPlan), C.POINTER(ToOpts),
+                                          C.POINTER(ToBox)]),
     "cacto_buffer_add": (C.c_int, [vp, vp, i64, i64, vp, i64, vp]),
     "cacto_rl_solve_add": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp, C.c_int, C.c_int, i64, C.c_int, C.c_int, vp,
                                      i64, i64, vp, vp]),

@@ -22,6 +22,14 @@
 // onto the positive semidefinite cone (psd_project.h): a bool template parameter of the solving
 // kernels, and for the records of the label pass's derivative kernels one more kernel
 // (k_to_psd_records); nothing else of the algorithm changes.
+// With a cacto_to_box of mode CACTO_TO_BOUNDS_BOX the problem gains hard limits lo <= u <= hi and the
+// method becomes control-limited DDP (Tassa, Mansard, Todorov, ICRA 2014): after the same Cholesky
+// verdict on Qbar_uu, k is the solution of the node's box QP (box_qp.h) over lo - ubar <= x <= hi - ubar,
+// K = -Qbar_ff^-1 Q_ux,f on the rows the QP leaves free and exactly 0 on the clamped ones, dJ[2] skips
+// the components held at a bound, and every roll-out (the warm start's too) clamps its controls. The
+// bounds are a class template parameter of every kernel (ToNoBox / ToBoxDev): without them each kernel
+// is what it was. cacto_ddp_backward, the label pass, knows no bounds: along a bounded trajectory the
+// Sobolev labels are the reference's unconstrained dV/dx (TO.py:119-202).
 //
 //
 // The file, in order:
@@ -48,6 +56,7 @@
 //   The library is built with -ffp-contract=off and the solvers share these functions, so the two
 //   solvers of a system give the same numbers bit for bit.
 #include "ddp_device.h"
+#include "box_qp.h"
 #include "psd_project.h"
 
 namespace cacto {
@@ -65,6 +74,45 @@ struct Traj {
 struct Gains {
   View k, K;  // K: element (i, j) of step t at index i * N + j
 };
+
+// The control bounds of a call (cacto_to_box), a template parameter of every kernel below and its
+// last argument. ToNoBox: the unbounded problem; every function is then what it is without the
+// parameter. ToBoxDev: lo <= u <= hi holds for every control a roll-out applies (the warm start's
+// included), and every node of the backward pass solves a box QP (box_qp.h) in place of the linear
+// system: control-limited DDP (Tassa, Mansard, Todorov, ICRA 2014).
+struct ToNoBox {
+  static constexpr bool on = false;
+  __device__ __forceinline__ double clamp(int, double v) const { return v; }
+};
+struct ToBoxDev {
+  static constexpr bool on = true;
+  double lo[CACTO_MAX_ACTION], hi[CACTO_MAX_ACTION];
+  __device__ __forceinline__ double clamp(int j, double v) const { return fmin(fmax(v, lo[j]), hi[j]); }
+  // control j sits on a bound and the gradient component qu points out of the box: it takes no part
+  // in the stopping rule
+  __device__ __forceinline__ bool held(int j, double u, double qu) const {
+    return (u == lo[j] && qu > 0.0) || (u == hi[j] && qu < 0.0);
+  }
+};
+
+// The gains of a node under bounds, on one thread: k = argmin 1/2 x^T Qbar x + Q_u^T x over
+// lo - ubar <= x <= hi - ubar (the offsets by box_offset_lo / box_offset_hi, so that a clamped control's
+// full step reaches its bound exactly; Qbar = Q_uu + mu I, whose own Cholesky verdict the caller has
+// taken already); Lf the factor of its free block (box_chol_free). false: the QP gave no solution, which the
+// caller treats as a Qbar that is not positive definite.
+template <int M>
+__device__ __forceinline__ bool to_box_gain(const ToBoxDev& bx, const double* Quu, double mu, const double* Qu, const double* ub,
+                                            double* k, unsigned* free_mask, double* Lf) {
+  double Hb[M * M], bl[M], bh[M];
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+#pragma unroll
+    for (int c = 0; c < M; ++c) Hb[j * M + c] = Quu[j * M + c] + (j == c ? mu : 0.0);
+    bl[j] = box_offset_lo(ub[j], bx.lo[j]);
+    bh[j] = box_offset_hi(ub[j], bx.hi[j]);
+  }
+  return to_box_qp<M>(Hb, Qu, bl, bh, k, free_mask, Lf);
+}
 
 // l_u, l_uu (diagonal) of the cost at control u_j: w6 scale (u^2 + w_b (u/u_max)^10)' — the
 // expressions of k_ddp_backward with the sign of the cost
@@ -133,11 +181,14 @@ __device__ inline void to_chol_solve(const double* L, double* x, int sx) {
 
 // One step of the backward recursion on one thread (cost convention). In: A, B, l_x, l_xx, l_u,
 // diagonal l_uu, V_x / V_xx of step t+1. Out: k [M], K [M*N], V_x / V_xx of step t, dJ
-// accumulated. false: Qbar_uu is not positive definite (nothing is updated).
-template <int N, int M>
+// accumulated. false: Qbar_uu is not positive definite (nothing is updated). Under bounds (ub: the
+// node's nominal control) Qbar_uu is factored for that verdict all the same; then k is the box QP's
+// solution, K = -Qbar_ff^-1 Q_ux,f on its free rows and exactly 0 on the clamped ones, and dJ[2]
+// leaves out the components held at a bound; V_x, V_xx, dJ[0], dJ[1] are the same formulas.
+template <int N, int M, class BX>
 __device__ inline bool to_riccati_step(const double* A, const double* B, const double* lx, const double* lxx,
-                                       const double* lu, const double* luu, double mu, double* Vx, double* Vxx,
-                                       double* k, double* K, double* dJ) {
+                                       const double* lu, const double* luu, double mu, const BX& bx, const double* ub,
+                                       double* Vx, double* Vxx, double* k, double* K, double* dJ) {
   double Qx[N], Qu[M], Qxx[N * N], Qux[M * N], Quu[M * M], VA[N * N], VB[N * M];
 #pragma unroll
   for (int r = 0; r < N; ++r) {
@@ -202,13 +253,29 @@ __device__ inline bool to_riccati_step(const double* A, const double* B, const d
 #pragma unroll
     for (int c = 0; c < M; ++c) L[j * M + c] = Quu[j * M + c] + (j == c ? mu : 0.0);
   if (!to_chol<M>(L)) return false;
+  if constexpr (BX::on) {
+    unsigned fm;
+    if (!to_box_gain<M>(bx, Quu, mu, Qu, ub, k, &fm, L)) return false;
 #pragma unroll
-  for (int j = 0; j < M; ++j) k[j] = -Qu[j];
-  to_chol_solve<M>(L, k, 1);
+    for (int j = 0; j < M; ++j)
 #pragma unroll
-  for (int q = 0; q < M * N; ++q) K[q] = -Qux[q];
+      for (int c = 0; c < N; ++c) K[j * N + c] = ((fm >> j) & 1u) ? -Qux[j * N + c] : 0.0;
 #pragma unroll
-  for (int c = 0; c < N; ++c) to_chol_solve<M>(L, K + c, N);
+    for (int c = 0; c < N; ++c) to_chol_solve<M>(L, K + c, N);
+#pragma unroll
+    for (int j = 0; j < M; ++j)
+      if (!((fm >> j) & 1u))
+#pragma unroll
+        for (int c = 0; c < N; ++c) K[j * N + c] = 0.0;
+  } else {
+#pragma unroll
+    for (int j = 0; j < M; ++j) k[j] = -Qu[j];
+    to_chol_solve<M>(L, k, 1);
+#pragma unroll
+    for (int q = 0; q < M * N; ++q) K[q] = -Qux[q];
+#pragma unroll
+    for (int c = 0; c < N; ++c) to_chol_solve<M>(L, K + c, N);
+  }
   double Tk[M], T[M * N], d0 = 0.0, d1 = 0.0, d2 = dJ[2];
 #pragma unroll
   for (int j = 0; j < M; ++j) {
@@ -228,7 +295,11 @@ __device__ inline bool to_riccati_step(const double* A, const double* B, const d
   for (int j = 0; j < M; ++j) {
     d0 += k[j] * Qu[j];
     d1 += k[j] * Tk[j];
-    d2 = fmax(d2, fabs(Qu[j]));
+    if constexpr (BX::on) {
+      if (!bx.held(j, ub[j], Qu[j])) d2 = fmax(d2, fabs(Qu[j]));
+    } else {
+      d2 = fmax(d2, fabs(Qu[j]));
+    }
   }
   dJ[0] += d0;
   dJ[1] += 0.5 * d1;
@@ -330,9 +401,10 @@ __device__ inline void to_node_record(const SysDevice& sd, const double* Minv, c
 // The backward pass of one closed-form episode on one thread. node(t, terminal, buf) is node t's
 // record: evaluated into buf [ToRec::R] on the spot (k_to_solve_thread, k_to_gains_thread) or read from
 // where the lanes of k_to_solve_wave left it. Returns -1, or the step at which Qbar_uu was not
-// positive definite. dJ [3] is reset here.
-template <int NJ, class Node>
-__device__ inline int to_backward_thread(Node node, int Te, double mu, const Gains& g, double* dJ) {
+// positive definite. dJ [3] is reset here. U: the episode's nominal controls (read under bounds only).
+template <int NJ, class BX, class Node>
+__device__ inline int to_backward_thread(Node node, int Te, double mu, const BX& bx, const View& U, const Gains& g,
+                                         double* dJ) {
   using TR = ToRec<NJ>;
   using RC = DdpRec<NJ>;
   constexpr int N = TR::N, M = TR::M;
@@ -347,9 +419,12 @@ __device__ inline int to_backward_thread(Node node, int Te, double mu, const Gai
   dJ[0] = dJ[1] = dJ[2] = 0.0;
   for (int i = Te - 1; i >= 0; --i) {
     const double* r = node(i, false, buf);
-    double kk[M], KK[M * N];
-    if (!to_riccati_step<N, M>(r + RC::A, r + RC::B, r + RC::LX, r + RC::LXX, r + TR::LU, r + TR::LUU, mu, Vx, Vxx, kk,
-                               KK, dJ))
+    double kk[M], KK[M * N], ub[M];
+    if constexpr (BX::on)
+#pragma unroll
+      for (int j = 0; j < M; ++j) ub[j] = U.at(i, j);
+    if (!to_riccati_step<N, M>(r + RC::A, r + RC::B, r + RC::LX, r + RC::LXX, r + TR::LU, r + TR::LUU, mu, bx, ub, Vx, Vxx,
+                               kk, KK, dJ))
       return i;
 #pragma unroll
     for (int j = 0; j < M; ++j) g.k.at(i, j) = kk[j];
@@ -359,24 +434,25 @@ __device__ inline int to_backward_thread(Node node, int Te, double mu, const Gai
   return -1;
 }
 // ... with every node evaluated on this thread
-template <int NJ, bool PSD>
+template <int NJ, bool PSD, class BX>
 __device__ inline int to_backward_eval(const SysDevice& sd, const double* Minv, const Traj& cur, int Te, double mu,
-                                       const Gains& g, double* dJ) {
-  return to_backward_thread<NJ>(
+                                       const BX& bx, const Gains& g, double* dJ) {
+  return to_backward_thread<NJ, BX>(
       [&](int t, bool terminal, double* buf) -> const double* {
         to_node_record<NJ, PSD>(sd, Minv, cur, t, terminal, buf);
         return buf;
       },
-      Te, mu, g, dJ);
+      Te, mu, bx, cur.U, g, dJ);
 }
 
 // One roll-out of one episode on one thread: closed loop around (cur, g) with step size alpha, or
 // open loop (g.k.p == nullptr). STORE: the new trajectory goes to nw and the node costs to cost
 // (element t at cost.at(t, 0)); nw may be cur itself, since node t+1 of cur is read before node
-// t+1 of nw is written. Returns the total cost.
-template <int NJ, bool STORE>
+// t+1 of nw is written. Returns the total cost. Under bounds every control is clamped to them before
+// it is applied, the open-loop ones (a warm start's) included.
+template <int NJ, bool STORE, class BX>
 __device__ inline double to_forward_thread(const SysDevice& sd, const Traj& cur, const Gains& g, int Te, double alpha,
-                                           const Traj& nw, const View& cost) {
+                                           const BX& bx, const Traj& nw, const View& cost) {
   constexpr int N = DdpDims<NJ>::N, M = DdpDims<NJ>::M, ns = N + 1;
   const cacto_sys_params& p = sd.p;
   double w_run[7], w_term[7];
@@ -404,7 +480,7 @@ __device__ inline double to_forward_thread(const SysDevice& sd, const Traj& cur,
 #pragma unroll
         for (int c = 0; c < N; ++c) v += g.K.at(t, j * N + c) * (x[c] - xb[c]);
       }
-      u[j] = v;
+      u[j] = bx.clamp(j, v);
     }
     const double c = to_cost<NJ>(sd, w_run, x, u);
     J += c;
@@ -444,12 +520,12 @@ __device__ __forceinline__ Gains api_gains(double* k, double* K, int64_t ldU, in
 }
 
 // cacto_to_backward_gains, closed-form family: one thread per episode.
-template <int NJ, bool PSD>
+template <int NJ, bool PSD, class BX>
 __global__ void __launch_bounds__(64) k_to_gains_thread(const SysDevice* __restrict__ sdp, const double* S, int64_t ldS,
                                                          const double* U, int64_t ldU,
                                                          const int32_t* __restrict__ nsteps, int n_ep, double mu,
                                                          double* k_out, double* K_out, double* __restrict__ dJ_out,
-                                                         int32_t* __restrict__ pd_out) {
+                                                         int32_t* __restrict__ pd_out, BX bx) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n_ep) return;
   const int Te = nsteps[e];
@@ -458,18 +534,18 @@ __global__ void __launch_bounds__(64) k_to_gains_thread(const SysDevice* __restr
   const Traj cur = api_traj<NJ>(const_cast<double*>(S), ldS, const_cast<double*>(U), ldU, e);
   const ToMinv<NJ> Minv(sd, cur);
   double dJ[3];
-  const int pd = to_backward_eval<NJ, PSD>(sd, Minv.a, cur, Te, mu, api_gains<NJ>(k_out, K_out, ldU, e), dJ);
+  const int pd = to_backward_eval<NJ, PSD>(sd, Minv.a, cur, Te, mu, bx, api_gains<NJ>(k_out, K_out, ldU, e), dJ);
   pd_out[e] = pd;
 #pragma unroll
   for (int k = 0; k < 3; ++k) dJ_out[(size_t)e * 3 + k] = dJ[k];
 }
 
 // cacto_to_forward, every system: one thread per episode.
-template <int NJ>
+template <int NJ, class BX>
 __global__ void __launch_bounds__(64) k_to_forward(const SysDevice* __restrict__ sdp, const double* S, int64_t ldS,
                                                     const double* U, int64_t ldU, const double* k_in,
                                                     const double* K_in, const int32_t* __restrict__ nsteps, int n_ep,
-                                                    double alpha, double* S_new, double* U_new, double* cost_new) {
+                                                    double alpha, double* S_new, double* U_new, double* cost_new, BX bx) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n_ep) return;
   const int Te = nsteps[e];
@@ -477,7 +553,7 @@ __global__ void __launch_bounds__(64) k_to_forward(const SysDevice* __restrict__
   const Traj cur = api_traj<NJ>(const_cast<double*>(S), ldS, const_cast<double*>(U), ldU, e);
   const Traj nw = api_traj<NJ>(S_new, ldS, U_new, ldU, e);
   const Gains g = api_gains<NJ>(const_cast<double*>(k_in), const_cast<double*>(K_in), ldU, e);
-  to_forward_thread<NJ, true>(*sdp, cur, g, Te, alpha, nw, View{cost_new + (size_t)e * ldS, 1, 1});
+  to_forward_thread<NJ, true>(*sdp, cur, g, Te, alpha, bx, nw, View{cost_new + (size_t)e * ldS, 1, 1});
 }
 
 struct ToCfgDev {
@@ -585,7 +661,8 @@ __device__ __forceinline__ void to_state_store(const ToIter& s, int Te, const To
 
 // The warm start of one episode, in place in cur: the copy of s0 and of the controls of nodes
 // first, first + stride, ... of U_init, then (on one thread, after the copy) the roll-out, which
-// leaves the node costs in cost and returns their sum.
+// leaves the node costs in cost and returns their sum. Under bounds the roll-out clamps the controls
+// it stores: the warm start the loop begins from, and whose cost is J[0], is the clamped one.
 template <int NJ>
 __device__ __forceinline__ void to_warm_copy(const double* S0, const double* U_init, int64_t ldU, int e, int Te,
                                              const Traj& cur, int first, int stride) {
@@ -597,25 +674,25 @@ __device__ __forceinline__ void to_warm_copy(const double* S0, const double* U_i
 #pragma unroll
     for (int j = 0; j < na; ++j) cur.U.at(t, j) = U_init[((size_t)e * ldU + t) * na + j];
 }
-template <int NJ>
-__device__ __forceinline__ double to_warm_rollout(const SysDevice& sd, int Te, const Traj& cur, const View& cost) {
+template <int NJ, class BX>
+__device__ __forceinline__ double to_warm_rollout(const SysDevice& sd, int Te, const BX& bx, const Traj& cur, const View& cost) {
   const Gains none{View{nullptr, 0, 0}, View{nullptr, 0, 0}};
-  return to_forward_thread<NJ, true>(sd, cur, none, Te, 0.0, cur, cost);
+  return to_forward_thread<NJ, true>(sd, cur, none, Te, 0.0, bx, cur, cost);
 }
-template <int NJ>
+template <int NJ, class BX>
 __device__ __forceinline__ double to_warm_start_thread(const SysDevice& sd, const double* S0, const double* U_init, int64_t ldU,
-                                                       int e, int Te, const Traj& cur, const View& cost) {
+                                                       int e, int Te, const BX& bx, const Traj& cur, const View& cost) {
   to_warm_copy<NJ>(S0, U_init, ldU, e, Te, cur, 0, 1);
-  return to_warm_rollout<NJ>(sd, Te, cur, cost);
+  return to_warm_rollout<NJ>(sd, Te, bx, cur, cost);
 }
 
 // One candidate of the line search on one thread: the cost of alpha = 2^-j rolled out without
 // storing it, or NaN when the step is not admissible.
-template <int NJ>
+template <int NJ, class BX>
 __device__ __forceinline__ double to_ls_candidate(const SysDevice& sd, const ToCfgDev& cfg, const Traj& cur, const Gains& g, int Te,
-                                                  int j, double J, const double* dJ, const View& cost) {
+                                                  int j, double J, const double* dJ, const BX& bx, const View& cost) {
   const double alpha = ldexp(1.0, -j);
-  const double Jc = to_forward_thread<NJ, false>(sd, cur, g, Te, alpha, cur, cost);
+  const double Jc = to_forward_thread<NJ, false>(sd, cur, g, Te, alpha, bx, cur, cost);
   return to_admissible(cfg, J, Jc, alpha, dJ) ? Jc : __builtin_nan("");
 }
 // The smallest admissible j among to_ls_candidate's values cand [0..max_ls] — by definition what
@@ -791,7 +868,7 @@ __global__ void __launch_bounds__(256) k_to_order(const int32_t* __restrict__ ns
 // end. Its own phases: the backward pass with every node evaluated on the spot, and sequential
 // backtracking that stops at the first admissible step — a candidate's cost is evaluated without
 // storing it, and the accepted one is rolled out again in place.
-template <int NJ, bool PSD>
+template <int NJ, bool PSD, class BX>
 __global__ void __launch_bounds__(64) k_to_solve_thread(const SysDevice* __restrict__ sdp, const double* __restrict__ S0,
                                                          const double* __restrict__ U_init, int64_t ldU,
                                                          const int32_t* __restrict__ nsteps, int n_ep, int64_t ldS,
@@ -799,7 +876,7 @@ __global__ void __launch_bounds__(64) k_to_solve_thread(const SysDevice* __restr
                                                          double* __restrict__ lanes, double* __restrict__ S_out,
                                                          double* __restrict__ U_out, double* __restrict__ cost_out,
                                                          int32_t* __restrict__ status_out, int32_t* __restrict__ iters_out,
-                                                         double* __restrict__ J_out) {
+                                                         double* __restrict__ J_out, BX bx) {
   constexpr int N = DdpDims<NJ>::N, M = DdpDims<NJ>::M, ns = N + 1;
   const int slot = blockIdx.x * blockDim.x + threadIdx.x;
   if (slot >= n_ep) return;
@@ -812,16 +889,16 @@ __global__ void __launch_bounds__(64) k_to_solve_thread(const SysDevice* __restr
   View cost;
   Gains g;
   ToWs<NJ>::lanes_views(lanes, (size_t)n_ep, (size_t)ldS, e, &cur, &cost, &g);
-  ToIter s = to_iter_begin(Te, to_warm_start_thread<NJ>(sd, S0, U_init, ldU, e, Te, cur, cost));
+  ToIter s = to_iter_begin(Te, to_warm_start_thread<NJ>(sd, S0, U_init, ldU, e, Te, bx, cur, cost));
   if (s.running()) {
     const ToMinv<NJ> Minv(sd, cur);
     double dJ[3];
     for (int it = 0; it < cfg.max_iter && s.running(); ++it) {
-      const ToVerdict v = to_verdict(cfg, to_backward_eval<NJ, PSD>(sd, Minv.a, cur, Te, s.mu, g, dJ), dJ);
+      const ToVerdict v = to_verdict(cfg, to_backward_eval<NJ, PSD>(sd, Minv.a, cur, Te, s.mu, bx, g, dJ), dJ);
       int sel = -1;
       for (int j = 0; v == TO_SEARCH && j <= cfg.max_ls && sel < 0; ++j)
-        if (!isnan(to_ls_candidate<NJ>(sd, cfg, cur, g, Te, j, s.J, dJ, cost))) sel = j;
-      to_decide(cfg, s, v, sel, sel >= 0 ? to_forward_thread<NJ, true>(sd, cur, g, Te, ldexp(1.0, -sel), cur, cost) : s.J);
+        if (!isnan(to_ls_candidate<NJ>(sd, cfg, cur, g, Te, j, s.J, dJ, bx, cost))) sel = j;
+      to_decide(cfg, s, v, sel, sel >= 0 ? to_forward_thread<NJ, true>(sd, cur, g, Te, ldexp(1.0, -sel), bx, cur, cost) : s.J);
     }
   }
   for (int t = 0; t <= Te; ++t) {
@@ -849,13 +926,13 @@ struct ToWaveLds {
 // stride over the nodes for the records and lane 0 runs the recursion from them; lane
 // j <= max_ls evaluates the cost of alpha = 2^-j without storing it, and the lane of the
 // smallest admissible j rolls that step out in place.
-template <int NJ, bool PSD>
+template <int NJ, bool PSD, class BX>
 __global__ void __launch_bounds__(64) k_to_solve_wave(const SysDevice* __restrict__ sdp, const double* __restrict__ S0,
                                                        const double* U_init, int64_t ldU,
                                                        const int32_t* __restrict__ nsteps, int n_ep, int64_t ldS,
                                                        ToCfgDev cfg, ToWs<NJ> lay, double* S_out, double* U_out,
                                                        double* cost_out, int32_t* __restrict__ status_out,
-                                                       int32_t* __restrict__ iters_out, double* __restrict__ J_out) {
+                                                       int32_t* __restrict__ iters_out, double* __restrict__ J_out, BX bx) {
   using TR = ToRec<NJ>;
   __shared__ ToWaveLds lds;
   const int lane = threadIdx.x;
@@ -870,7 +947,7 @@ __global__ void __launch_bounds__(64) k_to_solve_wave(const SysDevice* __restric
   double* rec = lay.episode_rec(e, TR::R);
   to_warm_copy<NJ>(S0, U_init, ldU, e, Te, cur, lane, 64);
   __syncthreads();
-  if (lane == 0) lds.pass[3] = to_warm_rollout<NJ>(sd, Te, cur, cost);
+  if (lane == 0) lds.pass[3] = to_warm_rollout<NJ>(sd, Te, bx, cur, cost);
   __syncthreads();
   ToIter s = to_iter_begin(Te, lds.pass[3]);
   if (s.running()) {
@@ -880,8 +957,8 @@ __global__ void __launch_bounds__(64) k_to_solve_wave(const SysDevice* __restric
       __syncthreads();
       if (lane == 0) {
         double d[3];
-        lds.pd = to_backward_thread<NJ>([rec](int t, bool, double*) { return (const double*)(rec + (size_t)t * TR::R); }, Te,
-                                        s.mu, g, d);
+        lds.pd = to_backward_thread<NJ, BX>([rec](int t, bool, double*) { return (const double*)(rec + (size_t)t * TR::R); },
+                                            Te, s.mu, bx, cur.U, g, d);
 #pragma unroll
         for (int k = 0; k < 3; ++k) lds.pass[k] = d[k];
       }
@@ -890,9 +967,9 @@ __global__ void __launch_bounds__(64) k_to_solve_wave(const SysDevice* __restric
       const ToVerdict v = to_verdict(cfg, lds.pd, dJ);
       int sel = -1;
       if (v == TO_SEARCH) {
-        const bool ok = lane <= cfg.max_ls && !isnan(to_ls_candidate<NJ>(sd, cfg, cur, g, Te, lane, s.J, dJ, cost));
+        const bool ok = lane <= cfg.max_ls && !isnan(to_ls_candidate<NJ>(sd, cfg, cur, g, Te, lane, s.J, dJ, bx, cost));
         sel = __ffsll(__ballot(ok)) - 1;
-        if (lane == sel) lds.pass[3] = to_forward_thread<NJ, true>(sd, cur, g, Te, ldexp(1.0, -sel), cur, cost);
+        if (lane == sel) lds.pass[3] = to_forward_thread<NJ, true>(sd, cur, g, Te, ldexp(1.0, -sel), bx, cur, cost);
         __syncthreads();
       }
       to_decide(cfg, s, v, sel, lds.pass[3]);
@@ -953,9 +1030,10 @@ struct ToPass {
   int pd;
   double dJ[3];
 };
-template <int NJ, int BT>
+template <int NJ, int BT, class BX>
 __device__ __forceinline__ ToPass to_gains_episode(ToGainsLds<NJ>& L, const cacto_sys_params& p, const double* Ue, int Te, double mu,
-                                        const double* rec_e, size_t ts, size_t es, double* ke, double* Ke, int lane) {
+                                        const BX& bx, const double* rec_e, size_t ts, size_t es, double* ke, double* Ke,
+                                        int lane) {
   using RC = DdpRec<NJ>;
   constexpr int N = RC::N, M = RC::M, na = Dims<NJ>::NA;
   const double w6 = p.w_running[6];
@@ -1033,21 +1111,38 @@ __device__ __forceinline__ ToPass to_gains_episode(ToGainsLds<NJ>& L, const cact
       double Lm[M * M], kk[M];
 #pragma unroll
       for (int q = 0; q < M * M; ++q) Lm[q] = L.sQuu[q] + (q % (M + 1) == 0 ? mu : 0.0);
-      if (!to_chol<M>(Lm)) {
+      // under bounds, after the same verdict on the full Qbar_uu: k from the box QP, Lm the factor of
+      // its free block, K's clamped rows exactly 0 (to_riccati_step's rule)
+      unsigned fm = ~0u;
+      bool ok = to_chol<M>(Lm);
+      if constexpr (BX::on) {
+        if (ok) {
+          double qu[M], ub[M];
+#pragma unroll
+          for (int j = 0; j < M; ++j) {
+            qu[j] = L.sQu[j];
+            ub[j] = L.sU[j];
+          }
+          ok = to_box_gain<M>(bx, L.sQuu, mu, qu, ub, kk, &fm, Lm);
+        }
+      }
+      if (!ok) {
         L.sFail = 1;
         pd = i;
       } else {
+        if constexpr (!BX::on) {
 #pragma unroll
-        for (int j = 0; j < M; ++j) kk[j] = -L.sQu[j];
-        to_chol_solve<M>(Lm, kk, 1);
+          for (int j = 0; j < M; ++j) kk[j] = -L.sQu[j];
+          to_chol_solve<M>(Lm, kk, 1);
+        }
 #pragma unroll 1
         for (int c = 0; c < N; ++c) {
           double col[M];
 #pragma unroll
-          for (int j = 0; j < M; ++j) col[j] = -L.sQux[j * N + c];
+          for (int j = 0; j < M; ++j) col[j] = ((fm >> j) & 1u) ? -L.sQux[j * N + c] : 0.0;
           to_chol_solve<M>(Lm, col, 1);
 #pragma unroll
-          for (int j = 0; j < M; ++j) L.sK[j * N + c] = col[j];
+          for (int j = 0; j < M; ++j) L.sK[j * N + c] = ((fm >> j) & 1u) ? col[j] : 0.0;
         }
 #pragma unroll
         for (int j = 0; j < M; ++j) {
@@ -1058,7 +1153,11 @@ __device__ __forceinline__ ToPass to_gains_episode(ToGainsLds<NJ>& L, const cact
           L.sk[j] = kk[j];
           d0 += kk[j] * L.sQu[j];
           d1 += kk[j] * s;
-          d2 = fmax(d2, fabs(L.sQu[j]));
+          if constexpr (BX::on) {
+            if (!bx.held(j, L.sU[j], L.sQu[j])) d2 = fmax(d2, fabs(L.sQu[j]));
+          } else {
+            d2 = fmax(d2, fabs(L.sQu[j]));
+          }
         }
       }
     }
@@ -1105,13 +1204,13 @@ __device__ __forceinline__ ToPass to_gains_episode(ToGainsLds<NJ>& L, const cact
 // cacto_to_backward_gains and the host-issued solver of the split family: one wavefront per
 // episode. rec_ws: the derivative records of k_ddp_derivs / k_ddp_prim + k_ddp_tan + k_ddp_lx,
 // [t][k][e]. mu_ep: per-episode mu (the solver) or nullptr (mu).
-template <int NJ>
+template <int NJ, class BX>
 __global__ void __launch_bounds__(64) k_to_gains_wave(const SysDevice* __restrict__ sdp, const double* __restrict__ U,
                                                       int64_t ldU, const int32_t* __restrict__ nsteps, int n_ep,
                                                       int64_t ldS, double mu, const double* __restrict__ mu_ep,
                                                       const double* __restrict__ rec_ws, double* __restrict__ k_out,
                                                       double* __restrict__ K_out, double* __restrict__ dJ_out,
-                                                      int32_t* __restrict__ pd_out) {
+                                                      int32_t* __restrict__ pd_out, BX bx) {
   using RC = DdpRec<NJ>;
   constexpr int N = RC::N, na = Dims<NJ>::NA;
   __shared__ ToGainsLds<NJ> lds;
@@ -1119,7 +1218,7 @@ __global__ void __launch_bounds__(64) k_to_gains_wave(const SysDevice* __restric
   const int Te = nsteps[e];
   if (!to_valid_len(Te, ldS, ldU)) return;  // uniform over the workgroup
   if (mu_ep) mu = mu_ep[e];
-  const ToPass bp = to_gains_episode<NJ, 64>(lds, sdp->p, U + (size_t)e * ldU * na, Te, mu, rec_ws + e,
+  const ToPass bp = to_gains_episode<NJ, 64>(lds, sdp->p, U + (size_t)e * ldU * na, Te, mu, bx, rec_ws + e,
                                              (size_t)RC::R * n_ep, (size_t)n_ep, k_out + (size_t)e * ldU * na,
                                              K_out + (size_t)e * ldU * na * N, lane);
   if (lane == 0) {
@@ -1134,13 +1233,13 @@ __global__ void __launch_bounds__(64) k_to_gains_wave(const SysDevice* __restric
 // k_to_init, then per pass the derivative kernels of the label pass (fed ToState::live as nsteps),
 // k_to_gains_wave and k_to_linesearch, the state in ToState in between. k_to_init: the warm
 // start, rolled out into the caller's S / U / step_cost, one thread per episode.
-template <int NJ>
+template <int NJ, class BX>
 __global__ void __launch_bounds__(64) k_to_init(const SysDevice* __restrict__ sdp, const double* __restrict__ S0,
                                                 const double* __restrict__ U_init, int64_t ldU,
                                                 const int32_t* __restrict__ nsteps, int n_ep, int64_t ldS, ToState st,
                                                 double* S_out, double* U_out, double* cost_out,
                                                 int32_t* __restrict__ status_out, int32_t* __restrict__ iters_out,
-                                                double* __restrict__ J_out) {
+                                                double* __restrict__ J_out, BX bx) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n_ep) return;
   const int Te = nsteps[e];
@@ -1150,7 +1249,7 @@ __global__ void __launch_bounds__(64) k_to_init(const SysDevice* __restrict__ sd
     atomicAdd(st.done, 1);
     return;
   }
-  const ToIter s = to_iter_begin(Te, to_warm_start_thread<NJ>(*sdp, S0, U_init, ldU, e, Te, api_traj<NJ>(S_out, ldS, U_out, ldU, e),
+  const ToIter s = to_iter_begin(Te, to_warm_start_thread<NJ>(*sdp, S0, U_init, ldU, e, Te, bx, api_traj<NJ>(S_out, ldS, U_out, ldU, e),
                                                               View{cost_out + (size_t)e * ldS, 1, 1}));
   to_state_store(s, Te, st, out, e);
 }
@@ -1159,13 +1258,13 @@ __global__ void __launch_bounds__(64) k_to_init(const SysDevice* __restrict__ sd
 // 64 / LSP episodes (LSP: the power of two >= max_ls + 1), thread (episode, j) evaluates the cost
 // of alpha = 2^-j without storing the trajectory, the episode's first thread picks the smallest
 // admissible j and stores the episode's state, and thread j rolls the accepted step out in place.
-template <int NJ>
+template <int NJ, class BX>
 __global__ void __launch_bounds__(64) k_to_linesearch(const SysDevice* __restrict__ sdp, double* S, int64_t ldS, double* U,
                                                        int64_t ldU, double* k_in, double* K_in,
                                                        const double* __restrict__ dJ_in, const int32_t* __restrict__ pd_in,
                                                        int n_ep, ToCfgDev cfg, int LSP, ToState st, double* cost_out,
                                                        int32_t* __restrict__ status_out, int32_t* __restrict__ iters_out,
-                                                       double* __restrict__ J_out) {
+                                                       double* __restrict__ J_out, BX bx) {
   __shared__ double sJ[64];
   __shared__ int sSel[64];
   const int G = 64 / LSP, tid = threadIdx.x;
@@ -1189,7 +1288,7 @@ __global__ void __launch_bounds__(64) k_to_linesearch(const SysDevice* __restric
     cost = View{cost_out + (size_t)e * ldS, 1, 1};
   }
   const bool search = live && v == TO_SEARCH;
-  sJ[tid] = search && j <= cfg.max_ls ? to_ls_candidate<NJ>(*sdp, cfg, cur, g, Te, j, J, dJ, cost) : __builtin_nan("");
+  sJ[tid] = search && j <= cfg.max_ls ? to_ls_candidate<NJ>(*sdp, cfg, cur, g, Te, j, J, dJ, bx, cost) : __builtin_nan("");
   __syncthreads();
   if (j == 0) {
     const int sel = to_pick(cfg, sJ + grp * LSP);
@@ -1201,7 +1300,7 @@ __global__ void __launch_bounds__(64) k_to_linesearch(const SysDevice* __restric
     sSel[grp] = sel;
   }
   __syncthreads();
-  if (search && j == sSel[grp]) to_forward_thread<NJ, true>(*sdp, cur, g, Te, ldexp(1.0, -j), cur, cost);
+  if (search && j == sSel[grp]) to_forward_thread<NJ, true>(*sdp, cur, g, Te, ldexp(1.0, -j), bx, cur, cost);
 }
 
 // LDS of k_to_solve_split: the backward pass's operands, and the scalars the phases hand to every
@@ -1230,13 +1329,13 @@ struct ToSplitLds {
 // The revolute chains are not instantiated: their derivative phase needs the tangent pass's LDS
 // slabs and the bodies of k_ddp_prim / k_ddp_tan / k_ddp_lx, and a build of this kernel with them
 // faulted on the GPU for a reason that has not been found.
-template <int NJ, int BT, bool PSD>
+template <int NJ, int BT, bool PSD, class BX>
 __global__ void __launch_bounds__(BT) k_to_solve_split(const SysDevice* __restrict__ sdp, const double* __restrict__ S0,
                                                         const double* U_init, int64_t ldU,
                                                         const int32_t* __restrict__ nsteps, int n_ep, int64_t ldS,
                                                         ToCfgDev cfg, ToWs<NJ> lay, double* S_out, double* U_out,
                                                         double* cost_out, int32_t* __restrict__ status_out,
-                                                        int32_t* __restrict__ iters_out, double* __restrict__ J_out) {
+                                                        int32_t* __restrict__ iters_out, double* __restrict__ J_out, BX bx) {
   static_assert(NJ == -2, "k_to_solve_split: car_park only");
   using RC = DdpRec<NJ>;
   __shared__ ToSplitLds<NJ> lds;
@@ -1249,7 +1348,7 @@ __global__ void __launch_bounds__(BT) k_to_solve_split(const SysDevice* __restri
   const View cost{cost_out + (size_t)e * ldS, 1, 1};
   const Gains g = lay.episode_gains(e);
   double* rec = lay.episode_rec(e, RC::R);
-  if (tid == 0) lds.pass[3] = to_warm_start_thread<NJ>(sd, S0, U_init, ldU, e, Te, cur, cost);
+  if (tid == 0) lds.pass[3] = to_warm_start_thread<NJ>(sd, S0, U_init, ldU, e, Te, bx, cur, cost);
   __syncthreads();
   ToIter s = to_iter_begin(Te, lds.pass[3]);
   for (int it = 0; it < cfg.max_iter && s.running(); ++it) {
@@ -1258,7 +1357,7 @@ __global__ void __launch_bounds__(BT) k_to_solve_split(const SysDevice* __restri
       if constexpr (PSD) to_psd_record<NJ>(rec + (size_t)t * RC::R, 1);
     }
     __syncthreads();
-    const ToPass bp = to_gains_episode<NJ, BT>(lds.gains, sd.p, cur.U.p, Te, s.mu, rec, (size_t)RC::R, 1, g.k.p, g.K.p, tid);
+    const ToPass bp = to_gains_episode<NJ, BT>(lds.gains, sd.p, cur.U.p, Te, s.mu, bx, rec, (size_t)RC::R, 1, g.k.p, g.K.p, tid);
     if (tid == 0) {
       lds.pd = bp.pd;
 #pragma unroll
@@ -1268,12 +1367,12 @@ __global__ void __launch_bounds__(BT) k_to_solve_split(const SysDevice* __restri
     const double dJ[3] = {lds.pass[0], lds.pass[1], lds.pass[2]};
     const ToVerdict v = to_verdict(cfg, lds.pd, dJ);
     if (tid < 64)
-      lds.cand[tid] = v == TO_SEARCH && tid <= cfg.max_ls ? to_ls_candidate<NJ>(sd, cfg, cur, g, Te, tid, s.J, dJ, cost)
+      lds.cand[tid] = v == TO_SEARCH && tid <= cfg.max_ls ? to_ls_candidate<NJ>(sd, cfg, cur, g, Te, tid, s.J, dJ, bx, cost)
                                                           : __builtin_nan("");
     __syncthreads();
     const int sel = to_pick(cfg, lds.cand);
     to_decide(cfg, s, v, sel, lds.cand[max(sel, 0)]);
-    if (tid == sel) to_forward_thread<NJ, true>(sd, cur, g, Te, ldexp(1.0, -sel), cur, cost);
+    if (tid == sel) to_forward_thread<NJ, true>(sd, cur, g, Te, ldexp(1.0, -sel), bx, cur, cost);
     __syncthreads();
   }
   if (tid == 0) to_iter_store(s, out, e);
@@ -1293,6 +1392,34 @@ inline bool to_opts_ok(const cacto_to_opts* o) {
                 o->reserved[1] == 0 && o->reserved[2] == 0);
 }
 inline bool to_opts_psd(const cacto_to_opts* o) { return o && o->hessian == CACTO_TO_HESS_PSD; }
+
+// cacto_to_box: NULL and mode NONE mean no bounds (lo, hi are then not looked at). A box needs
+// lo[j] < hi[j], neither a NaN, for j < na; an infinite entry leaves that side open.
+inline bool to_box_on(const cacto_to_box* b) { return b && b->mode == CACTO_TO_BOUNDS_BOX; }
+inline bool to_box_ok(const cacto_to_box* b, int na) {
+  if (!b) return true;
+  if ((b->mode != CACTO_TO_BOUNDS_NONE && b->mode != CACTO_TO_BOUNDS_BOX) || b->reserved != 0) return false;
+  if (b->mode == CACTO_TO_BOUNDS_BOX)
+    for (int j = 0; j < na && j < CACTO_MAX_ACTION; ++j)
+      if (!(b->lo[j] < b->hi[j])) return false;  // also a NaN
+  return true;
+}
+// A null system leaves nb_action unknown: the first entry, which every system has, is checked
+inline int to_box_na(const cacto_sys* sys) { return sys ? sys->host.p.nb_action : 1; }
+inline ToBoxDev to_box_dev(const cacto_to_box* b) {
+  ToBoxDev d;
+  for (int j = 0; j < CACTO_MAX_ACTION; ++j) {
+    d.lo[j] = b->lo[j];
+    d.hi[j] = b->hi[j];
+  }
+  return d;
+}
+// f(bounds of the call as the kernels take them)
+template <class F>
+int to_with_box(const cacto_to_box* box, F f) {
+  if (to_box_on(box)) return f(to_box_dev(box));
+  return f(ToNoBox{});
+}
 
 // the (dynamics, reward) combinations of the six systems, as cacto_ddp_backward
 template <int NJ>
@@ -1337,8 +1464,14 @@ int to_launch_derivs(const cacto_sys* sys, const double* S, int64_t ldS, const d
 template <int NJ>
 struct LaunchToGains {
   static int run(const cacto_sys* sys, const double* S, int64_t ldS, const double* U, int64_t ldU, const int32_t* n,
-                 int n_ep, double mu, bool psd, double* k, double* K, double* dJ, int32_t* pd, hipStream_t st) {
+                 int n_ep, double mu, bool psd, const cacto_to_box* box, double* k, double* K, double* dJ, int32_t* pd,
+                 hipStream_t st) {
     if (!to_supported<NJ>(sys, "cacto_to_backward_gains")) return CACTO_EUNSUPPORTED;
+    return to_with_box(box, [&](auto bx) { return go(sys, S, ldS, U, ldU, n, n_ep, mu, psd, bx, k, K, dJ, pd, st); });
+  }
+  template <class BX>
+  static int go(const cacto_sys* sys, const double* S, int64_t ldS, const double* U, int64_t ldU, const int32_t* n,
+                int n_ep, double mu, bool psd, BX bx, double* k, double* K, double* dJ, int32_t* pd, hipStream_t st) {
     if constexpr (DdpDims<NJ>::ok) {
       if constexpr (to_split<NJ>()) {
         double* rec = nullptr;
@@ -1346,15 +1479,15 @@ struct LaunchToGains {
         if (rc != CACTO_OK) return rc;
         const int rc2 = to_launch_derivs<NJ>(sys, S, ldS, U, ldU, n, n_ep, rec, psd, st);
         if (rc2 != CACTO_OK) return rc2;
-        hipLaunchKernelGGL(k_to_gains_wave<NJ>, dim3(n_ep), dim3(64), 0, st, sys->dev, U, ldU, n, n_ep, ldS, mu,
-                           (const double*)nullptr, rec, k, K, dJ, pd);
+        hipLaunchKernelGGL((k_to_gains_wave<NJ, BX>), dim3(n_ep), dim3(64), 0, st, sys->dev, U, ldU, n, n_ep, ldS, mu,
+                           (const double*)nullptr, rec, k, K, dJ, pd, bx);
       } else {
         if (psd)
-          hipLaunchKernelGGL((k_to_gains_thread<NJ, true>), dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S, ldS, U,
-                             ldU, n, n_ep, mu, k, K, dJ, pd);
+          hipLaunchKernelGGL((k_to_gains_thread<NJ, true, BX>), dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S, ldS,
+                             U, ldU, n, n_ep, mu, k, K, dJ, pd, bx);
         else
-          hipLaunchKernelGGL((k_to_gains_thread<NJ, false>), dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S, ldS, U,
-                             ldU, n, n_ep, mu, k, K, dJ, pd);
+          hipLaunchKernelGGL((k_to_gains_thread<NJ, false, BX>), dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S, ldS,
+                             U, ldU, n, n_ep, mu, k, K, dJ, pd, bx);
       }
       CACTO_CHECK_HIP(hipGetLastError());
     }
@@ -1365,15 +1498,17 @@ struct LaunchToGains {
 template <int NJ>
 struct LaunchToForward {
   static int run(const cacto_sys* sys, const double* S, int64_t ldS, const double* U, int64_t ldU, const double* k,
-                 const double* K, const int32_t* n, int n_ep, double alpha, double* Sn, double* Un, double* cost,
-                 hipStream_t st) {
+                 const double* K, const int32_t* n, int n_ep, double alpha, const cacto_to_box* box, double* Sn, double* Un,
+                 double* cost, hipStream_t st) {
     if (!to_supported<NJ>(sys, "cacto_to_forward")) return CACTO_EUNSUPPORTED;
-    if constexpr (DdpDims<NJ>::ok) {
-      hipLaunchKernelGGL(k_to_forward<NJ>, dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S, ldS, U, ldU, k, K, n,
-                         n_ep, alpha, Sn, Un, cost);
-      CACTO_CHECK_HIP(hipGetLastError());
-    }
-    return CACTO_OK;
+    return to_with_box(box, [&](auto bx) -> int {
+      if constexpr (DdpDims<NJ>::ok) {
+        hipLaunchKernelGGL((k_to_forward<NJ, decltype(bx)>), dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S, ldS, U,
+                           ldU, k, K, n, n_ep, alpha, Sn, Un, cost, bx);
+        CACTO_CHECK_HIP(hipGetLastError());
+      }
+      return CACTO_OK;
+    });
   }
 };
 
@@ -1386,25 +1521,33 @@ struct LaunchToBytes {
 };
 
 // The solvers' launches. A solver is instantiated for the systems to_route can give it, once per
-// Hessian mode: the mode is a template parameter of the solving kernels, so the exact-mode kernels
-// carry no trace of the projection.
+// Hessian mode and once per bounds mode: both are template parameters of the solving kernels, so the
+// exact-mode kernels carry no trace of the projection and the unbounded ones none of the box QP.
 template <int NJ>
 struct LaunchToSolve {
-  template <bool PSD>
+  template <bool PSD, class BX>
   static void launch_closed_form(ToSolver solver, const cacto_sys* sys, const double* S0, const double* U_init, int64_t ldU,
                                  const int32_t* n, int n_ep, int64_t ldS, const ToCfgDev& c, const ToWs<NJ>& lay, double* S,
-                                 double* U, double* cost, int32_t* status, int32_t* iters, double* J, hipStream_t st) {
+                                 double* U, double* cost, int32_t* status, int32_t* iters, double* J, BX bx, hipStream_t st) {
     if (solver == TO_SOLVER_WAVE)
-      hipLaunchKernelGGL((k_to_solve_wave<NJ, PSD>), dim3(n_ep), dim3(64), 0, st, sys->dev, S0, U_init, ldU, n, n_ep, ldS, c,
-                         lay, S, U, cost, status, iters, J);
+      hipLaunchKernelGGL((k_to_solve_wave<NJ, PSD, BX>), dim3(n_ep), dim3(64), 0, st, sys->dev, S0, U_init, ldU, n, n_ep, ldS,
+                         c, lay, S, U, cost, status, iters, J, bx);
     else
-      hipLaunchKernelGGL((k_to_solve_thread<NJ, PSD>), dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S0, U_init, ldU,
-                         n, n_ep, ldS, c, (const int32_t*)lay.order, lay.lanes, S, U, cost, status, iters, J);
+      hipLaunchKernelGGL((k_to_solve_thread<NJ, PSD, BX>), dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S0, U_init,
+                         ldU, n, n_ep, ldS, c, (const int32_t*)lay.order, lay.lanes, S, U, cost, status, iters, J, bx);
   }
   static int run(const cacto_sys* sys, const double* S0, const double* U_init, int64_t ldU, const int32_t* n, int n_ep,
-                 int64_t ldS, const cacto_to_cfg* cfg, bool psd, double* S, double* U, double* cost, int32_t* status,
-                 int32_t* iters, double* J, void* ws, size_t ws_bytes, hipStream_t st) {
+                 int64_t ldS, const cacto_to_cfg* cfg, bool psd, const cacto_to_box* box, double* S, double* U, double* cost,
+                 int32_t* status, int32_t* iters, double* J, void* ws, size_t ws_bytes, hipStream_t st) {
     if (!to_supported<NJ>(sys, "cacto_to_solve")) return CACTO_EUNSUPPORTED;
+    return to_with_box(box, [&](auto bx) {
+      return go(sys, S0, U_init, ldU, n, n_ep, ldS, cfg, psd, bx, S, U, cost, status, iters, J, ws, ws_bytes, st);
+    });
+  }
+  template <class BX>
+  static int go(const cacto_sys* sys, const double* S0, const double* U_init, int64_t ldU, const int32_t* n, int n_ep,
+                int64_t ldS, const cacto_to_cfg* cfg, bool psd, BX bx, double* S, double* U, double* cost, int32_t* status,
+                int32_t* iters, double* J, void* ws, size_t ws_bytes, hipStream_t st) {
     if constexpr (DdpDims<NJ>::ok) {
       const ToSolver solver = to_route<NJ>(cfg->path);
       const ToWs<NJ> lay(ws, n_ep, ldS, solver);
@@ -1416,27 +1559,27 @@ struct LaunchToSolve {
         hipLaunchKernelGGL(k_to_order, dim3(1), dim3(256), 0, st, n, n_ep, ldS, lay.order, lay.hist);
         CACTO_CHECK_HIP(hipGetLastError());
         if (psd)
-          launch_closed_form<true>(solver, sys, S0, U_init, ldU, n, n_ep, ldS, c, lay, S, U, cost, status, iters, J, st);
+          launch_closed_form<true>(solver, sys, S0, U_init, ldU, n, n_ep, ldS, c, lay, S, U, cost, status, iters, J, bx, st);
         else
-          launch_closed_form<false>(solver, sys, S0, U_init, ldU, n, n_ep, ldS, c, lay, S, U, cost, status, iters, J, st);
+          launch_closed_form<false>(solver, sys, S0, U_init, ldU, n, n_ep, ldS, c, lay, S, U, cost, status, iters, J, bx, st);
         CACTO_CHECK_HIP(hipGetLastError());
       } else if (solver == TO_SOLVER_SPLIT) {
         if constexpr (to_persistent<NJ>()) {
           constexpr int BT = TO_SPLIT_THREADS;
           if (psd)
-            hipLaunchKernelGGL((k_to_solve_split<NJ, BT, true>), dim3(n_ep), dim3(BT), 0, st, sys->dev, S0, U_init, ldU, n,
-                               n_ep, ldS, c, lay, S, U, cost, status, iters, J);
+            hipLaunchKernelGGL((k_to_solve_split<NJ, BT, true, BX>), dim3(n_ep), dim3(BT), 0, st, sys->dev, S0, U_init, ldU,
+                               n, n_ep, ldS, c, lay, S, U, cost, status, iters, J, bx);
           else
-            hipLaunchKernelGGL((k_to_solve_split<NJ, BT, false>), dim3(n_ep), dim3(BT), 0, st, sys->dev, S0, U_init, ldU, n,
-                               n_ep, ldS, c, lay, S, U, cost, status, iters, J);
+            hipLaunchKernelGGL((k_to_solve_split<NJ, BT, false, BX>), dim3(n_ep), dim3(BT), 0, st, sys->dev, S0, U_init, ldU,
+                               n, n_ep, ldS, c, lay, S, U, cost, status, iters, J, bx);
           CACTO_CHECK_HIP(hipGetLastError());
         }
       } else {
         // the gains kernel indexes the gains with ldU; the workspace holds ldS rows of them
         CACTO_REQUIRE(ldU <= ldS, "cacto_to_solve: ldU > ldS");
         CACTO_CHECK_HIP(hipMemsetAsync(lay.st.done, 0, sizeof(int32_t), st));
-        hipLaunchKernelGGL(k_to_init<NJ>, dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S0, U_init, ldU, n, n_ep,
-                           ldS, lay.st, S, U, cost, status, iters, J);
+        hipLaunchKernelGGL((k_to_init<NJ, BX>), dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S0, U_init, ldU, n, n_ep,
+                           ldS, lay.st, S, U, cost, status, iters, J, bx);
         CACTO_CHECK_HIP(hipGetLastError());
         int LSP = 1;
         while (LSP < c.max_ls + 1) LSP *= 2;
@@ -1450,11 +1593,11 @@ struct LaunchToSolve {
           }
           const int rc = to_launch_derivs<NJ>(sys, S, ldS, U, ldU, lay.st.live, n_ep, lay.rec, psd, st);
           if (rc != CACTO_OK) return rc;
-          hipLaunchKernelGGL(k_to_gains_wave<NJ>, dim3(n_ep), dim3(64), 0, st, sys->dev, U, ldU, lay.st.live, n_ep, ldS,
-                             0.0, (const double*)lay.st.mu, lay.rec, lay.k, lay.K, lay.dJ, lay.pd);
+          hipLaunchKernelGGL((k_to_gains_wave<NJ, BX>), dim3(n_ep), dim3(64), 0, st, sys->dev, U, ldU, lay.st.live, n_ep, ldS,
+                             0.0, (const double*)lay.st.mu, lay.rec, lay.k, lay.K, lay.dJ, lay.pd, bx);
           CACTO_CHECK_HIP(hipGetLastError());
-          hipLaunchKernelGGL(k_to_linesearch<NJ>, dim3(ceil_div(n_ep, G)), dim3(64), 0, st, sys->dev, S, ldS, U, ldU, lay.k,
-                             lay.K, lay.dJ, lay.pd, n_ep, c, LSP, lay.st, cost, status, iters, J);
+          hipLaunchKernelGGL((k_to_linesearch<NJ, BX>), dim3(ceil_div(n_ep, G)), dim3(64), 0, st, sys->dev, S, ldS, U, ldU,
+                             lay.k, lay.K, lay.dJ, lay.pd, n_ep, c, LSP, lay.st, cost, status, iters, J, bx);
           CACTO_CHECK_HIP(hipGetLastError());
         }
       }
@@ -1490,31 +1633,53 @@ struct LaunchToPlan {
 // other arguments are looked at.
 #define CACTO_TO_REQUIRE_OPTS(opts, who) \
   CACTO_REQUIRE(to_opts_ok(opts), who ": bad options (hessian: CACTO_TO_HESS_EXACT or CACTO_TO_HESS_PSD; reserved words 0)")
+// ... and so are the bounds, right after them: before the system is looked at, so with a null one
+// (nb_action unknown) the first entry is what is checked
+#define CACTO_TO_REQUIRE_BOX(box, sys, who)             \
+  CACTO_REQUIRE(to_box_ok(box, to_box_na(sys)),         \
+                who ": bad bounds (mode: CACTO_TO_BOUNDS_NONE or CACTO_TO_BOUNDS_BOX; reserved 0; lo[j] < hi[j], no NaN)")
 
-extern "C" int cacto_to_solve_plan_opts(const cacto_sys* sys, const cacto_to_cfg* cfg_h, cacto_to_plan* out,
-                                        const cacto_to_opts* opts) {
+// The kernels a plan describes are the same with and without bounds (the box QP needs no LDS and no
+// launch of its own)
+extern "C" int cacto_to_solve_plan_box(const cacto_sys* sys, const cacto_to_cfg* cfg_h, cacto_to_plan* out,
+                                       const cacto_to_opts* opts, const cacto_to_box* box) {
   CACTO_REQUIRE(cfg_h, "cacto_to_solve_plan: null config");
   CACTO_REQUIRE(to_path_ok(cfg_h->path),
                 "cacto_to_solve_plan: bad config (path: CACTO_TO_PATH_DEFAULT or CACTO_TO_PATH_WAVE)");
   CACTO_TO_REQUIRE_OPTS(opts, "cacto_to_solve_plan");
+  CACTO_TO_REQUIRE_BOX(box, sys, "cacto_to_solve_plan");
   CACTO_REQUIRE(sys && out, "cacto_to_solve_plan: bad arguments (null pointer)");
   return dispatch_nj<LaunchToPlan>(sys->host.p, sys, (int)cfg_h->path, to_opts_psd(opts), out);
+}
+
+extern "C" int cacto_to_solve_plan_opts(const cacto_sys* sys, const cacto_to_cfg* cfg_h, cacto_to_plan* out,
+                                        const cacto_to_opts* opts) {
+  return cacto_to_solve_plan_box(sys, cfg_h, out, opts, nullptr);
 }
 
 extern "C" int cacto_to_solve_plan(const cacto_sys* sys, const cacto_to_cfg* cfg_h, cacto_to_plan* out) {
   return cacto_to_solve_plan_opts(sys, cfg_h, out, nullptr);
 }
 
+extern "C" int cacto_to_backward_gains_box(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d,
+                                           int64_t ldU, const int32_t* nsteps_d, int n_ep, double mu, double* k_d,
+                                           double* K_d, double* dJ_d, int32_t* pd_d, void* stream,
+                                           const cacto_to_opts* opts, const cacto_to_box* box) {
+  CACTO_TO_REQUIRE_OPTS(opts, "cacto_to_backward_gains");
+  CACTO_TO_REQUIRE_BOX(box, sys, "cacto_to_backward_gains");
+  CACTO_REQUIRE(sys && S_d && U_d && nsteps_d && k_d && K_d && dJ_d && pd_d && n_ep >= 0 && ldS >= 1 && ldU >= 0,
+                "cacto_to_backward_gains: bad arguments");
+  if (n_ep == 0) return CACTO_OK;
+  return dispatch_nj<LaunchToGains>(sys->host.p, sys, S_d, ldS, U_d, ldU, nsteps_d, n_ep, mu, to_opts_psd(opts), box, k_d,
+                                    K_d, dJ_d, pd_d, as_stream(stream));
+}
+
 extern "C" int cacto_to_backward_gains_opts(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d,
                                             int64_t ldU, const int32_t* nsteps_d, int n_ep, double mu, double* k_d,
                                             double* K_d, double* dJ_d, int32_t* pd_d, void* stream,
                                             const cacto_to_opts* opts) {
-  CACTO_TO_REQUIRE_OPTS(opts, "cacto_to_backward_gains");
-  CACTO_REQUIRE(sys && S_d && U_d && nsteps_d && k_d && K_d && dJ_d && pd_d && n_ep >= 0 && ldS >= 1 && ldU >= 0,
-                "cacto_to_backward_gains: bad arguments");
-  if (n_ep == 0) return CACTO_OK;
-  return dispatch_nj<LaunchToGains>(sys->host.p, sys, S_d, ldS, U_d, ldU, nsteps_d, n_ep, mu, to_opts_psd(opts), k_d, K_d,
-                                    dJ_d, pd_d, as_stream(stream));
+  return cacto_to_backward_gains_box(sys, S_d, ldS, U_d, ldU, nsteps_d, n_ep, mu, k_d, K_d, dJ_d, pd_d, stream, opts,
+                                     nullptr);
 }
 
 extern "C" int cacto_to_backward_gains(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d,
@@ -1523,25 +1688,41 @@ extern "C" int cacto_to_backward_gains(const cacto_sys* sys, const double* S_d, 
   return cacto_to_backward_gains_opts(sys, S_d, ldS, U_d, ldU, nsteps_d, n_ep, mu, k_d, K_d, dJ_d, pd_d, stream, nullptr);
 }
 
-extern "C" int cacto_to_forward(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d, int64_t ldU,
-                                const double* k_d, const double* K_d, const int32_t* nsteps_d, int n_ep, double alpha,
-                                double* S_new_d, double* U_new_d, double* cost_new_d, void* stream) {
+extern "C" int cacto_to_forward_box(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d, int64_t ldU,
+                                    const double* k_d, const double* K_d, const int32_t* nsteps_d, int n_ep, double alpha,
+                                    double* S_new_d, double* U_new_d, double* cost_new_d, void* stream,
+                                    const cacto_to_box* box) {
+  CACTO_TO_REQUIRE_BOX(box, sys, "cacto_to_forward");
   CACTO_REQUIRE(sys && S_d && U_d && nsteps_d && S_new_d && U_new_d && cost_new_d && n_ep >= 0 && ldS >= 1 && ldU >= 0 &&
                     (k_d == nullptr) == (K_d == nullptr),
                 "cacto_to_forward: bad arguments");
   if (n_ep == 0) return CACTO_OK;
-  return dispatch_nj<LaunchToForward>(sys->host.p, sys, S_d, ldS, U_d, ldU, k_d, K_d, nsteps_d, n_ep, alpha, S_new_d,
+  return dispatch_nj<LaunchToForward>(sys->host.p, sys, S_d, ldS, U_d, ldU, k_d, K_d, nsteps_d, n_ep, alpha, box, S_new_d,
                                       U_new_d, cost_new_d, as_stream(stream));
 }
 
-// The projection works in place on the records, so the workspace is the same in both Hessian modes
-extern "C" size_t cacto_to_workspace_bytes_opts(const cacto_sys* sys, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h,
-                                                const cacto_to_opts* opts) {
+extern "C" int cacto_to_forward(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d, int64_t ldU,
+                                const double* k_d, const double* K_d, const int32_t* nsteps_d, int n_ep, double alpha,
+                                double* S_new_d, double* U_new_d, double* cost_new_d, void* stream) {
+  return cacto_to_forward_box(sys, S_d, ldS, U_d, ldU, k_d, K_d, nsteps_d, n_ep, alpha, S_new_d, U_new_d, cost_new_d, stream,
+                              nullptr);
+}
+
+// The projection works in place on the records, so the workspace is the same in both Hessian modes;
+// the box QP lives in registers, so it is the same with and without bounds
+extern "C" size_t cacto_to_workspace_bytes_box(const cacto_sys* sys, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h,
+                                               const cacto_to_opts* opts, const cacto_to_box* box) {
   const int path = cfg_h ? (int)cfg_h->path : (int)CACTO_TO_PATH_DEFAULT;
+  if (!to_box_ok(box, to_box_na(sys))) return 0;
   if (!sys || n_ep < 0 || ldS < 1 || !to_path_ok(path) || !to_opts_ok(opts)) return 0;
   size_t out = 0;
   if (dispatch_nj<LaunchToBytes>(sys->host.p, n_ep, ldS, path, &out) != CACTO_OK) return 0;
   return out;
+}
+
+extern "C" size_t cacto_to_workspace_bytes_opts(const cacto_sys* sys, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h,
+                                                const cacto_to_opts* opts) {
+  return cacto_to_workspace_bytes_box(sys, n_ep, ldS, cfg_h, opts, nullptr);
 }
 
 extern "C" size_t cacto_to_workspace_bytes(const cacto_sys* sys, int n_ep, int64_t ldS) {
@@ -1553,14 +1734,16 @@ extern "C" size_t cacto_to_workspace_bytes_cfg(const cacto_sys* sys, int n_ep, i
   return cacto_to_workspace_bytes_opts(sys, n_ep, ldS, cfg_h, nullptr);
 }
 
-extern "C" int cacto_to_solve_opts(const cacto_sys* sys, const double* S0_d, const double* U_init_d, int64_t ldU,
-                                   const int32_t* nsteps_d, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h, double* S_d,
-                                   double* U_d, double* step_cost_d, int32_t* status_d, int32_t* iters_d, double* J_d,
-                                   void* ws_d, size_t ws_bytes, void* stream, const cacto_to_opts* opts) {
+extern "C" int cacto_to_solve_box(const cacto_sys* sys, const double* S0_d, const double* U_init_d, int64_t ldU,
+                                  const int32_t* nsteps_d, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h, double* S_d,
+                                  double* U_d, double* step_cost_d, int32_t* status_d, int32_t* iters_d, double* J_d,
+                                  void* ws_d, size_t ws_bytes, void* stream, const cacto_to_opts* opts,
+                                  const cacto_to_box* box) {
   CACTO_REQUIRE(cfg_h, "cacto_to_solve: null config");
   // an unknown path is a property of the config alone: reported before the arguments are looked at
   CACTO_REQUIRE(to_path_ok(cfg_h->path), "cacto_to_solve: bad config (path: CACTO_TO_PATH_DEFAULT or CACTO_TO_PATH_WAVE)");
   CACTO_TO_REQUIRE_OPTS(opts, "cacto_to_solve");
+  CACTO_TO_REQUIRE_BOX(box, sys, "cacto_to_solve");
   CACTO_REQUIRE(sys && S0_d && U_init_d && nsteps_d && S_d && U_d && step_cost_d && status_d && iters_d && J_d && ws_d &&
                     n_ep >= 0 && ldS >= 1 && ldU >= 0 && ldU <= ldS,
                 "cacto_to_solve: bad arguments (null pointer, n_ep < 0, ldS < 1, ldU < 0 or ldU > ldS)");
@@ -1573,7 +1756,15 @@ extern "C" int cacto_to_solve_opts(const cacto_sys* sys, const double* S0_d, con
   }
   if (n_ep == 0) return CACTO_OK;
   return dispatch_nj<LaunchToSolve>(sys->host.p, sys, S0_d, U_init_d, ldU, nsteps_d, n_ep, ldS, cfg_h, to_opts_psd(opts),
-                                    S_d, U_d, step_cost_d, status_d, iters_d, J_d, ws_d, ws_bytes, as_stream(stream));
+                                    box, S_d, U_d, step_cost_d, status_d, iters_d, J_d, ws_d, ws_bytes, as_stream(stream));
+}
+
+extern "C" int cacto_to_solve_opts(const cacto_sys* sys, const double* S0_d, const double* U_init_d, int64_t ldU,
+                                   const int32_t* nsteps_d, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h, double* S_d,
+                                   double* U_d, double* step_cost_d, int32_t* status_d, int32_t* iters_d, double* J_d,
+                                   void* ws_d, size_t ws_bytes, void* stream, const cacto_to_opts* opts) {
+  return cacto_to_solve_box(sys, S0_d, U_init_d, ldU, nsteps_d, n_ep, ldS, cfg_h, S_d, U_d, step_cost_d, status_d, iters_d,
+                            J_d, ws_d, ws_bytes, stream, opts, nullptr);
 }
 
 extern "C" int cacto_to_solve(const cacto_sys* sys, const double* S0_d, const double* U_init_d, int64_t ldU,

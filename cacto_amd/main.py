@@ -31,7 +31,8 @@ def parse_args(argv=None):
     """The reference's options (main.py:18-46) that have a meaning here, plus --nb-loops (stop after
     that many loops), --to-path (which kernels solve the TO batch, cacto_amd.to.PATHS) and
     --accept-maxiter (keep episodes whose solve stopped at max_iter). --to-hessian (the node Hessian
-    of the TO's backward pass, cacto_amd.to.HESSIANS; exact when absent), --plots, --fig-path and
+    of the TO's backward pass, cacto_amd.to.HESSIANS; exact when absent), --to-bounds (hard control
+    limits of the TO, the conf's u_min / u_max; none when absent), --plots, --fig-path and
     --eval-every (the evaluation stage) and --seeds (several seeds at once, train_ensemble; not with
     --seed or --plots) are in the dict only when they are given. Returns a dict."""
     p = argparse.ArgumentParser(prog="python -m cacto_amd.main", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -67,6 +68,9 @@ def parse_args(argv=None):
     p.add_argument("--to-hessian", type=str, default=argparse.SUPPRESS, choices=["exact", "psd"],
                    help="Node Hessian of the trajectory optimiser's backward pass: the cost's own, or its "
                         "projection onto the positive semidefinite cone (default: exact)")
+    p.add_argument("--to-bounds", type=str, default=argparse.SUPPRESS, choices=["none", "conf"],
+                   help="Hard control limits of the trajectory optimiser: none (the reference's penalty alone), or "
+                        "the conf's u_min / u_max enforced by control-limited DDP (default: none)")
     p.add_argument("--plots", action="store_true", default=argparse.SUPPRESS,
                    help="Run the evaluation stage: value grid, TO trajectories, return and roll-out figures")
     p.add_argument("--fig-path", type=str, default=argparse.SUPPRESS,
@@ -88,6 +92,8 @@ def train_kwargs(args):
               accept_maxiter=args["accept_maxiter"], n_loops=args["nb_loops"], recover=args["recover_training_flag"])
     if "to_hessian" in args:
         kw["to_cfg"]["hessian"] = args["to_hessian"]
+    if "to_bounds" in args:
+        kw["to_cfg"]["bounds"] = args["to_bounds"]
     if args.get("plots"):
         kw.update(evaluate=True, eval_every=args.get("eval_every", 1))
     return args["system_id"], kw

@@ -2,7 +2,8 @@
 
 `TO_System_Solve` (TO.py:37-100) states one NLP per episode with CasADi and solves it with IPOPT.
 The problem is unconstrained apart from the dynamics and the fixed initial state (the control
-bounds are the penalty w_b (u/u_max)^10 inside the cost, environment_TO.py:201-206), so here it is
+bounds are the penalty w_b (u/u_max)^10 inside the cost, environment_TO.py:201-206; `bounds="conf"`
+enforces them as hard limits besides, by control-limited DDP), so here it is
 solved by a batched iLQR (`cacto_to_solve`): single shooting, Gauss-Newton DDP with first-order
 dynamics and exact cost Hessians (or, `hessian="psd"`, their projections onto the positive
 semidefinite cone), a backtracking line search and Levenberg-Marquardt regularisation, all episodes of a main.py iteration in one call, float64 throughout. The cost is
@@ -42,10 +43,17 @@ CONVERGED, MAXITER, FAILED = L.CACTO_TO_CONVERGED, L.CACTO_TO_MAXITER, L.CACTO_T
 # projection onto the positive semidefinite cone at every node (cacto_to_opts), which keeps Q_uu
 # positive definite without mu where the cost is concave. The Sobolev labels (backward_pass) are
 # exact under either.
+# bounds: hard limits lo <= u <= hi on the controls (cacto_to_box; control-limited DDP: a box QP per
+# node of the backward pass, feedback on the unclamped controls only, every roll-out and the warm start
+# clamped, gtol on the projected gradient). "none" / None: the reference's problem, where the penalty
+# alone holds the controls; "conf": conf.u_min, conf.u_max; a pair (lo, hi) of nb_action values each
+# (+-inf: that side open). Every returned control then lies in [lo, hi] exactly. The Sobolev labels
+# (backward_pass) stay the reference's unconstrained dV/dx along the bounded trajectory.
 DEFAULT_CFG = dict(max_iter=400, max_ls=10, gtol=1e-4, armijo=1e-4, mu_min=1e-6, mu_up=10.0, mu_down=10.0,
-                   mu_max=1e10, poll_every=8, path=0, hessian="exact")
+                   mu_max=1e10, poll_every=8, path=0, hessian="exact", bounds="none")
 PATHS = {"default": L.CACTO_TO_PATH_DEFAULT, "wave": L.CACTO_TO_PATH_WAVE}
 HESSIANS = {"exact": L.CACTO_TO_HESS_EXACT, "psd": L.CACTO_TO_HESS_PSD}
+NOT_FIELDS = ("hessian", "bounds")      # cfg keys that travel beside the ToCfg (make_opts, make_box)
 
 
 def make_opts(cfg=None):
@@ -65,10 +73,49 @@ def make_opts(cfg=None):
     return o
 
 
+def make_box(cfg=None, conf=None):
+    """The ToBox (cacto_to_box) of a cfg dict's `bounds` key, or of a bare bounds value: None for
+    "none" / None (no bounds: the entries without them are called); "conf": conf.u_min, conf.u_max; a
+    pair (lo, hi) of array-likes of conf.nb_action values, lo < hi, no NaN. A ToBox is returned as it
+    is. Anything else: ValueError. Without a conf only the form is checked (make_cfg) and the result
+    is None."""
+    b = cfg.get("bounds", DEFAULT_CFG["bounds"]) if isinstance(cfg, dict) else cfg
+    if isinstance(b, L.ToBox):
+        return b
+    if b is None or (isinstance(b, str) and b == "none"):
+        return None
+    bad = ValueError("unknown TO bounds %r (\"none\", \"conf\", or a pair (lo, hi) of nb_action values, lo < hi)" % (b,))
+    if isinstance(b, str):
+        if b != "conf":
+            raise bad
+        if conf is None:
+            return None
+        lo, hi = conf.u_min, conf.u_max
+    else:
+        try:
+            lo, hi = b
+            lo, hi = np.array(lo, dtype=np.float64), np.array(hi, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise bad from None
+        if lo.ndim != 1 or lo.shape != hi.shape or not 1 <= len(lo) <= L.MAX_ACTION:
+            raise bad
+        if conf is None:
+            return None
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    if lo.shape != (conf.nb_action,) or hi.shape != (conf.nb_action,) or not (lo < hi).all():
+        raise bad
+    box = L.ToBox()
+    box.mode = L.CACTO_TO_BOUNDS_BOX
+    for j in range(conf.nb_action):
+        box.lo[j], box.hi[j] = float(lo[j]), float(hi[j])
+    return box
+
+
 def make_cfg(cfg=None):
-    """The 64-byte ToCfg (cacto_to_cfg) of a cfg dict over DEFAULT_CFG. The `hessian` key is checked
-    here but is no field of that struct: it travels in the ToOpts that make_opts(cfg) gives, and a
-    caller who hands solve_batch / solve_plan a ToCfg passes that as `opts`."""
+    """The 64-byte ToCfg (cacto_to_cfg) of a cfg dict over DEFAULT_CFG. The `hessian` and `bounds` keys
+    are checked here but are no fields of that struct: they travel in the ToOpts that make_opts(cfg)
+    and the ToBox that make_box(cfg, conf) give, and a caller who hands solve_batch / solve_plan a
+    ToCfg passes those as `opts` and `bounds`."""
     vals = dict(DEFAULT_CFG)
     vals.update(cfg or {})
     unknown = set(vals) - set(DEFAULT_CFG)
@@ -79,9 +126,10 @@ def make_cfg(cfg=None):
             raise ValueError("unknown TO path %r (one of %s, or 0 / 1)" % (vals["path"], sorted(PATHS)))
         vals["path"] = PATHS[vals["path"]]
     make_opts(vals)
+    make_box(vals)
     c = L.ToCfg()
     for k, v in vals.items():
-        if k != "hessian":
+        if k not in NOT_FIELDS:
             setattr(c, k, v)
     return c
 
@@ -95,9 +143,20 @@ def _cfg_opts(cfg, opts=None):
     return make_cfg(cfg), make_opts(cfg if opts is None else opts)
 
 
-def _opts_args(o):
-    """(suffix of the entry's name, trailing arguments): the `_opts` entry when an option differs
-    from the defaults, else the entry it extends, which is that call with NULL options."""
+def _cfg_box(cfg, conf, bounds=None):
+    """The ToBox (or None) of a call's `cfg` and `bounds`: the dict's key, or `bounds` over it; a ToCfg
+    holds none."""
+    if bounds is not None:
+        return make_box(bounds, conf)
+    return make_box(cfg, conf) if isinstance(cfg, dict) else None
+
+
+def _opts_args(o, box=None):
+    """(suffix of the entry's name, trailing arguments): the `_box` entry (options, bounds) when there
+    are bounds, the `_opts` entry when only an option differs from the defaults, else the entry both
+    extend, which is that call with NULL options and NULL bounds."""
+    if box is not None:
+        return "_box", (C.byref(o), C.byref(box))
     return ("_opts", (C.byref(o),)) if o.hessian != L.CACTO_TO_HESS_EXACT else ("", ())
 
 
@@ -109,10 +168,11 @@ class TO:
         self.sys = env.sys
 
     # ------------------------------------------------------------------ the solver
-    def solve_batch(self, S0, U_init, nsteps, cfg=None, out=None, opts=None):
+    def solve_batch(self, S0, U_init, nsteps, cfg=None, out=None, opts=None, bounds=None):
         """cacto_to_solve. S0 [E, ns] f64, U_init [E, ldU, na] f64 (the warm start's controls),
         nsteps [E] int32 (Te; < 0 skips the episode), all on the device; cfg: a dict over
-        DEFAULT_CFG, or a ToCfg together with opts (a ToOpts or a hessian value; _cfg_opts). Returns a dict of device tensors S [E, ldS, ns], U [E, ldU, na], step_cost
+        DEFAULT_CFG, or a ToCfg together with opts (a ToOpts or a hessian value; _cfg_opts) and bounds
+        (as the cfg key; over the dict's when given). Returns a dict of device tensors S [E, ldS, ns], U [E, ldU, na], step_cost
         [E, ldS], status [E] (CONVERGED / MAXITER / FAILED), iters [E], J [E, 2] (warm start's cost,
         final cost), ldS = ldU + 1. Rows past Te, and every row of a skipped episode, keep what
         `out` (the same dict, optional) held — zeros (status -1) when it is not given."""
@@ -127,7 +187,7 @@ class TO:
                        iters=torch.zeros(E, dtype=torch.int32, device=DEVICE), J=torch.zeros(E, 2, **f64))
         c, o = _cfg_opts(cfg, opts)
         # 0 for a path the library does not know: cacto_to_solve then reports the bad config
-        sfx, extra = _opts_args(o)
+        sfx, extra = _opts_args(o, _cfg_box(cfg, self.conf, bounds))
         ws_bytes = L.lib().raw("cacto_to_workspace_bytes" + (sfx or "_cfg"))
         nbytes = int(ws_bytes(self.sys.handle, E, ldS, C.byref(c), *extra))
         ws = getattr(self, "_to_ws", None)
@@ -140,19 +200,21 @@ class TO:
                      dptr(ws), nbytes, stream(), *extra)
         return out
 
-    def solve_plan(self, cfg=None, opts=None):
+    def solve_plan(self, cfg=None, opts=None, bounds=None):
         """cacto_to_solve_plan: what solve_batch runs for this system with cfg and opts (as
         solve_batch's), as a dict: on_device (1: the whole loop is one kernel, nothing synchronises, the
         call can be captured into a graph), block_threads and lds_bytes of the solving kernel,
         launches_per_iter (kernel launches the host issues per iteration; 0 when on_device)."""
         c, o = _cfg_opts(cfg, opts)
         plan = L.ToPlan()
-        sfx, extra = _opts_args(o)
+        sfx, extra = _opts_args(o, _cfg_box(cfg, self.conf, bounds))
         L.lib().call("cacto_to_solve_plan" + sfx, self.sys.handle, C.byref(c), C.byref(plan), *extra)
         return {name: int(getattr(plan, name)) for name, _ in L.ToPlan._fields_}
 
-    def backward_gains_batch(self, S_traj, U_traj, nsteps, mu=0.0, hessian="exact"):
-        """cacto_to_backward_gains (hessian: "exact" / "psd" / 0 / 1, as the cfg key) along S_traj
+    def backward_gains_batch(self, S_traj, U_traj, nsteps, mu=0.0, hessian="exact", bounds=None):
+        """cacto_to_backward_gains (hessian: "exact" / "psd" / 0 / 1, bounds: as the cfg keys; under
+        bounds k is the box QP's solution around U_traj, K's clamped rows are 0 and dJ[2] is the
+        projected gradient) along S_traj
         [E, ldS, ns], U_traj [E, ldU, na]: a dict k [E, ldU, na], K [E, ldU, na, nx], dJ [E, 3] = (sum k^T Q_u, 1/2 sum k^T Q_uu k, max |Q_u|), pd [E]
         (-1: Q_uu + mu I positive definite at every step, else the step where it was not; nothing
         below that step is defined)."""
@@ -161,21 +223,24 @@ class TO:
         f64 = dict(dtype=torch.float64, device=DEVICE)
         out = dict(k=torch.zeros(E, ldU, na, **f64), K=torch.zeros(E, ldU, na, ns - 1, **f64),
                    dJ=torch.zeros(E, 3, **f64), pd=torch.full((E,), -1, dtype=torch.int32, device=DEVICE))
-        sfx, extra = _opts_args(make_opts(hessian))
+        sfx, extra = _opts_args(make_opts(hessian), make_box(bounds, self.conf))
         L.lib().call("cacto_to_backward_gains" + sfx, self.sys.handle, dptr(S_traj, torch.float64), ldS,
                      dptr(U_traj, torch.float64), ldU, dptr(nsteps, torch.int32), E, float(mu), dptr(out["k"]),
                      dptr(out["K"]), dptr(out["dJ"]), dptr(out["pd"]), stream(), *extra)
         return out
 
-    def forward_batch(self, S_traj, U_traj, k, K, nsteps, alpha=1.0):
-        """cacto_to_forward: u_t = ubar_t + alpha k_t + K_t (x_t - xbar_t) rolled out from S_traj[:, 0].
+    def forward_batch(self, S_traj, U_traj, k, K, nsteps, alpha=1.0, bounds=None):
+        """cacto_to_forward: u_t = ubar_t + alpha k_t + K_t (x_t - xbar_t) rolled out from S_traj[:, 0],
+        every u_t clamped to `bounds` (as the cfg key) when given.
         Returns (S_new, U_new, cost_new [E, ldS]); k = K = None gives the open-loop roll-out."""
         E, ldS, ldU = S_traj.shape[0], S_traj.shape[1], U_traj.shape[1]
         S_new, U_new = torch.zeros_like(S_traj), torch.zeros_like(U_traj)
         cost = torch.zeros(E, ldS, dtype=torch.float64, device=DEVICE)
-        L.lib().call("cacto_to_forward", self.sys.handle, dptr(S_traj, torch.float64), ldS,
+        box = make_box(bounds, self.conf)
+        sfx, extra = ("_box", (C.byref(box),)) if box is not None else ("", ())
+        L.lib().call("cacto_to_forward" + sfx, self.sys.handle, dptr(S_traj, torch.float64), ldS,
                      dptr(U_traj, torch.float64), ldU, dptr(k, torch.float64), dptr(K, torch.float64),
-                     dptr(nsteps, torch.int32), E, float(alpha), dptr(S_new), dptr(U_new), dptr(cost), stream())
+                     dptr(nsteps, torch.int32), E, float(alpha), dptr(S_new), dptr(U_new), dptr(cost), stream(), *extra)
         return S_new, U_new, cost
 
     # ------------------------------------------------------------------ the reference's signatures

@@ -595,6 +595,39 @@ typedef struct {
   int32_t reserved[3]; /* must be 0 */
 } cacto_to_opts;
 
+/* Hard control limits, beside cacto_to_cfg and cacto_to_opts (both fixed): the `_box` entries below
+ * take the arguments of the entry they extend plus a pointer to this struct last. NULL, or mode
+ * CACTO_TO_BOUNDS_NONE (lo, hi are then not read): the call is the entry it extends — the same
+ * kernels, the same numbers, the controls held only by the penalty inside the cost.
+ *   CACTO_TO_BOUNDS_BOX  control-limited DDP (Tassa, Mansard, Todorov, ICRA 2014) on lo <= u <= hi:
+ *     backward  Qbar_uu = Q_uu + mu I is factored first as without bounds (the same verdict, the same
+ *               mu schedule); then k = argmin 1/2 x^T Qbar_uu x + Q_u^T x over lo - ubar <= x <= hi - ubar
+ *               (a projected-Newton iteration in float64; one that does not finish counts as a Qbar_uu
+ *               that is not positive definite; the two offsets are moved outward by one unit in the
+ *               last place where ubar + offset would stop short of the bound in float64, so that the
+ *               clamped full step of a clamped control is the bound itself), K = -Qbar_ff^-1 Q_ux,f on the rows of the controls the
+ *               solution leaves free and exactly 0 on the clamped rows; V_x, V_xx, dJ[0], dJ[1] by the
+ *               formulas above. dJ[2], the quantity gtol stops on, becomes the projected gradient: the
+ *               maximum of |Q_u,j| over the nodes and the j that are not held at a bound (ubar_j == lo_j
+ *               with Q_u,j > 0, or ubar_j == hi_j with Q_u,j < 0).
+ *     forward   u = min(max(ubar + alpha k + K dx, lo), hi) in every roll-out, the line search's
+ *               candidates and cacto_to_forward_box's open-loop roll-out included. The warm start is
+ *               clamped the same way before it is rolled out, and J[0] is the clamped warm start's cost.
+ *     Every control the solver returns lies in [lo, hi] exactly. The two solvers of a system agree
+ *     bit for bit. cacto_ddp_backward (the Sobolev labels) knows no bounds: along a bounded trajectory
+ *     it gives the reference's unconstrained dV/dx (TO.py:119-202).
+ * An unknown mode, a non-zero reserved word, or with CACTO_TO_BOUNDS_BOX a NaN or lo[j] >= hi[j] for
+ * some j < nb_action: CACTO_EINVAL "bad bounds" (workspace query: 0), no device work, reported right
+ * after the options and before the other arguments; with a null system, where nb_action is not known
+ * yet, entry 0 is the one checked. */
+enum cacto_to_bounds { CACTO_TO_BOUNDS_NONE = 0, CACTO_TO_BOUNDS_BOX = 1 };
+
+typedef struct {
+  int32_t mode;     /* enum cacto_to_bounds */
+  int32_t reserved; /* must be 0 */
+  double lo[CACTO_MAX_ACTION], hi[CACTO_MAX_ACTION]; /* first nb_action entries; -inf / +inf: that side open */
+} cacto_to_box;     /* 136 bytes */
+
 /* One regularised backward pass along given trajectories (cost convention, l_xu = 0):
  *   Qbar_uu = Q_uu + mu I, k = -Qbar_uu^-1 Q_u, K = -Qbar_uu^-1 Q_ux,
  *   V_x = Q_x + K^T Q_uu k + K^T Q_u + Q_ux^T k, V_xx = Q_xx + K^T Q_uu K + K^T Q_ux + Q_ux^T K
@@ -609,6 +642,11 @@ int cacto_to_backward_gains(const cacto_sys* sys, const double* S_d, int64_t ldS
 int cacto_to_backward_gains_opts(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d, int64_t ldU,
                                  const int32_t* nsteps_d, int n_ep, double mu, double* k_d, double* K_d, double* dJ_d,
                                  int32_t* pd_d, void* stream, const cacto_to_opts* opts);
+/* ... under bounds (cacto_to_box): U_d is the nominal control the box is taken around; dJ_d[2] is
+ * the projected gradient. */
+int cacto_to_backward_gains_box(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d, int64_t ldU,
+                                const int32_t* nsteps_d, int n_ep, double mu, double* k_d, double* K_d, double* dJ_d,
+                                int32_t* pd_d, void* stream, const cacto_to_opts* opts, const cacto_to_box* box);
 
 /* One closed-loop roll-out: u_t = ubar_t + alpha k_t + K_t (x_t - xbar_t), x_{t+1} = Env.simulate
  * (float64). S_new_d [n_ep, ldS, ns] (time column t0 + dt t), U_new_d [n_ep, ldU, na], cost_new_d
@@ -617,6 +655,10 @@ int cacto_to_backward_gains_opts(const cacto_sys* sys, const double* S_d, int64_
 int cacto_to_forward(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d, int64_t ldU,
                      const double* k_d, const double* K_d, const int32_t* nsteps_d, int n_ep, double alpha,
                      double* S_new_d, double* U_new_d, double* cost_new_d, void* stream);
+/* ... with every control clamped to the bounds before it is applied (cacto_to_box). */
+int cacto_to_forward_box(const cacto_sys* sys, const double* S_d, int64_t ldS, const double* U_d, int64_t ldU,
+                         const double* k_d, const double* K_d, const int32_t* nsteps_d, int n_ep, double alpha,
+                         double* S_new_d, double* U_new_d, double* cost_new_d, void* stream, const cacto_to_box* box);
 
 /* Workspace of cacto_to_solve: for cfg.path = CACTO_TO_PATH_DEFAULT, and for the path of a given
  * config (CACTO_TO_PATH_WAVE adds the per-node derivative records of the closed-form family; for
@@ -628,6 +670,9 @@ size_t cacto_to_workspace_bytes_cfg(const cacto_sys* sys, int n_ep, int64_t ldS,
  * CACTO_TO_HESS_PSD works in place, so the size does not depend on the Hessian mode. */
 size_t cacto_to_workspace_bytes_opts(const cacto_sys* sys, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h,
                                      const cacto_to_opts* opts);
+/* ... and bounds: the box QP needs no memory, so the size does not depend on them (0 on bad bounds). */
+size_t cacto_to_workspace_bytes_box(const cacto_sys* sys, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h,
+                                    const cacto_to_opts* opts, const cacto_to_box* box);
 
 /* The solver. S0_d [n_ep, ns] initial states (with time), U_init_d [n_ep, ldU, na] warm start.
  * Outputs: S_d [n_ep, ldS, ns], U_d [n_ep, ldU, na], step_cost_d [n_ep, ldS], status_d [n_ep] int32
@@ -657,6 +702,12 @@ int cacto_to_solve_opts(const cacto_sys* sys, const double* S0_d, const double* 
                         const int32_t* nsteps_d, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h, double* S_d,
                         double* U_d, double* step_cost_d, int32_t* status_d, int32_t* iters_d, double* J_d, void* ws_d,
                         size_t ws_bytes, void* stream, const cacto_to_opts* opts);
+/* ... under bounds (cacto_to_box): every solving kernel is instantiated once more per bounds mode,
+ * so the unbounded kernels carry no trace of the box QP; the launches and the workspace are the same. */
+int cacto_to_solve_box(const cacto_sys* sys, const double* S0_d, const double* U_init_d, int64_t ldU,
+                       const int32_t* nsteps_d, int n_ep, int64_t ldS, const cacto_to_cfg* cfg_h, double* S_d,
+                       double* U_d, double* step_cost_d, int32_t* status_d, int32_t* iters_d, double* J_d, void* ws_d,
+                       size_t ws_bytes, void* stream, const cacto_to_opts* opts, const cacto_to_box* box);
 
 /* What cacto_to_solve runs for a system and a config (the role cacto_rollout_plan plays for the
  * rollout: TO.py:37-100 has one host-side IPOPT call per episode and nothing to plan), so a
@@ -675,6 +726,9 @@ int cacto_to_solve_plan(const cacto_sys* sys, const cacto_to_cfg* cfg_h, cacto_t
 /* ... with options: CACTO_TO_HESS_PSD adds one launch to launches_per_iter of a host-issued loop. */
 int cacto_to_solve_plan_opts(const cacto_sys* sys, const cacto_to_cfg* cfg_h, cacto_to_plan* out,
                              const cacto_to_opts* opts);
+/* ... and bounds, which change nothing of the plan. */
+int cacto_to_solve_plan_box(const cacto_sys* sys, const cacto_to_cfg* cfg_h, cacto_to_plan* out,
+                            const cacto_to_opts* opts, const cacto_to_box* box);
 
 /* What cacto_rollout_sched runs for B episodes under a schedule (groups, workgroups), decided by the
  * same function that launches it. "eight" = the systems whose step needs no workgroup-wide dynamics

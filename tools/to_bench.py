@@ -4,7 +4,7 @@ full-solve settings of the tests (gtol 1e-4, max_iter 400, max_ls 10, armijo 1e-
 from 1e-6). Prints one JSON line: episodes/s, mean and max backward passes, the share per status.
 
     python tools/to_bench.py [--system double_integrator] [--episodes 4096] [--path default|wave] [--repeat 3]
-                             [--hessian exact|psd] [--helper 8]
+                             [--hessian exact|psd] [--bounds none|conf] [--helper 8]
 
 --path wave runs the one-workgroup-per-episode persistent kernel (cacto_to_cfg.path; not the
 manipulator and UR5, which have none):
@@ -14,6 +14,9 @@ launches_per_iter) beside the figures.
 
 --hessian psd solves with every node's l_xx projected onto the positive semidefinite cone
 (cacto_to_opts.hessian); the result line carries the mode.
+
+--bounds conf solves under the conf's u_min / u_max as hard limits (cacto_to_box, control-limited
+DDP); the result line carries the mode and the share of the returned controls that sit on a bound.
 
 --helper N also times tests/ilqr_ref.py (numpy, one core) on the first N of those episodes and
 reports its seconds per episode. Reported, not gated: there is no earlier figure to compare with,
@@ -41,6 +44,7 @@ def main():
     ap.add_argument("--poll-every", type=int, default=8)
     ap.add_argument("--path", default="default", choices=["default", "wave"])
     ap.add_argument("--hessian", default="exact", choices=["exact", "psd"])
+    ap.add_argument("--bounds", default="none", choices=["none", "conf"])
     ap.add_argument("--helper-only", action="store_true", help="time the helper alone (needs no GPU)")
     args = ap.parse_args()
 
@@ -61,6 +65,8 @@ def main():
     from cacto_amd.to import TO
     to = TO(make_env(conf), conf)
     cfg = dict(R.SOLVE_CFG, poll_every=args.poll_every, path=args.path, hessian=args.hessian)
+    if args.bounds != "none":       # the key only when asked for: a library of an older revision has no such entry
+        cfg["bounds"] = args.bounds
     from cacto_amd import _lib
     # a library of an older revision (CACTO_HIP_LIB with CACTO_LIB_PARTIAL=1, cacto_amd/_lib.py: A/B runs)
     # has no plan entry
@@ -78,8 +84,14 @@ def main():
     best = min(times[1:])
     status, iters = out["status"].cpu().numpy(), out["iters"].cpu().numpy()
     J = out["J"].cpu().numpy()
+    U = out["U"].cpu().numpy()
+    mask = np.arange(U.shape[1])[None, :, None] < Te[:, None, None]
+    at_bound = ((U == conf.u_min) | (U == conf.u_max)) & mask
+    outside = ((U < conf.u_min) | (U > conf.u_max)) & mask
+    n_ctrl = max(int(mask.sum()) * conf.nb_action, 1)
     res = dict(metric="to_solve_episodes_per_s", system=args.system, path=args.path, hessian=args.hessian,
-               episodes=args.episodes,
+               bounds=args.bounds, controls_at_bound=float(at_bound.sum() / n_ctrl),
+               controls_outside=float(outside.sum() / n_ctrl), episodes=args.episodes,
                mean_steps=float(Te.mean()), seconds=best, seconds_all=times[1:], episodes_per_s=args.episodes / best,
                iters_mean=float(iters.mean()), iters_max=int(iters.max()),
                status_share=dict(converged=float((status == R.CONVERGED).mean()),
