@@ -181,6 +181,7 @@ _SIGS = {
     "cacto_rollout_plan": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(RoPlan)]),
     "cacto_rollout_rewards": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
     "cacto_ddp_backward": (C.c_int, [vp, vp, i64, vp, i64, vp, C.c_int, C.c_double, vp, vp]),
+    "cacto_ddp_backward_box": (C.c_int, [vp, vp, i64, vp, i64, vp, C.c_int, C.c_double, vp, vp, C.POINTER(ToBox)]),
     "cacto_to_backward_gains": (C.c_int, [vp, vp, i64, vp, i64, vp, C.c_int, C.c_double, vp, vp, vp, vp, vp]),
     "cacto_to_forward": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp, C.c_int, C.c_double, vp, vp, vp, vp]),
     "cacto_to_workspace_bytes": (sz, [vp, C.c_int, i64]),

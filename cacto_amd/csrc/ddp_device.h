@@ -619,4 +619,93 @@ __global__ void __launch_bounds__(64) k_ddp_lx(const SysDevice* __restrict__ sdp
   for (int k = 0; k < N * N; ++k) rec[(size_t)(RC::LXX + k) * n_ep] = lxx[k];
 }
 
+// The control bounds of a call (cacto_to_box), a template parameter of the trajectory optimiser's
+// kernels (to_kernels.hip) and of the label pass's recursions (ddp_kernels.hip), and their last
+// argument. ToNoBox: the unbounded problem; every function is then what it is without the
+// parameter. ToBoxDev, in the optimiser: lo <= u <= hi holds for every control a roll-out applies (the
+// warm start's included), and every node of the backward pass solves a box QP (box_qp.h) in place of
+// the linear system: control-limited DDP (Tassa, Mansard, Todorov, ICRA 2014). In the label pass: the
+// controls a bound holds leave the node's recursion (ddp_label_mask).
+struct ToNoBox {
+  static constexpr bool on = false;
+  __device__ __forceinline__ double clamp(int, double v) const { return v; }
+};
+struct ToBoxDev {
+  static constexpr bool on = true;
+  double lo[CACTO_MAX_ACTION], hi[CACTO_MAX_ACTION];
+  __device__ __forceinline__ double clamp(int j, double v) const { return fmin(fmax(v, lo[j]), hi[j]); }
+  // control j sits on a bound and the gradient component qu points out of the box: it takes no part
+  // in the stopping rule
+  __device__ __forceinline__ bool held(int j, double u, double qu) const {
+    return (u == lo[j] && qu > 0.0) || (u == hi[j] && qu < 0.0);
+  }
+  // the same rule for the label pass, which differentiates the reward (qu = -Q_u of the cost) along
+  // any recorded trajectory: a control on or outside a bound counts as on it. An infinite bound never
+  // holds, a NaN nowhere.
+  __device__ __forceinline__ bool label_held(int j, double u, double qu) const {
+    return (u <= lo[j] && qu < 0.0) || (u >= hi[j] && qu > 0.0);
+  }
+};
+
+// Bound-aware labels (cacto_ddp_backward_box): with f the controls of a node that no bound holds,
+//   V_x = Q_x - Q_xu[:, f] Qbar[f, f]^-1 Q_u[f],   V_xx = Q_xx - Q_xu[:, f] Qbar[f, f]^-1 Q_xu[:, f]^T
+// (f empty: V_x = Q_x, V_xx = Q_xx), by masking: for a held j, Q_u[j] = 0, column j of Q_xu = 0, row and
+// column j of Qbar = Q_uu + mu I the unit vector. The node's small_inverse and products then run as
+// without bounds: the inverse of the masked Qbar is Qbar[f, f]^-1 on f and the identity on the rest, and
+// every term a held control would add is an exact zero. A node with nothing held is left as it was,
+// so its arithmetic is the unbounded pass's operation for operation. The decision is first order (the
+// rule of the solver's stopping test, not its box QP): it needs no positive definite Qbar, which the
+// label pass never asks for, and no iteration.
+template <int N, int M>
+__device__ __forceinline__ void ddp_label_mask(const ToBoxDev& bx, const double* u, double* Qu, double* Qbar,
+                                               double* Qxu) {
+#pragma unroll
+  for (int j = 0; j < M; ++j)
+    if (bx.label_held(j, u[j], Qu[j])) {
+      Qu[j] = 0.0;
+#pragma unroll
+      for (int r = 0; r < N; ++r) Qxu[r * M + j] = 0.0;
+#pragma unroll
+      for (int k = 0; k < M; ++k) {
+        Qbar[j * M + k] = 0.0;
+        Qbar[k * M + j] = 0.0;
+      }
+      Qbar[j * M + j] = 1.0;
+    }
+}
+
+// cacto_to_box: NULL and mode NONE mean no bounds (lo, hi are then not looked at). A box needs
+// lo[j] < hi[j], neither a NaN, for j < na; an infinite entry leaves that side open.
+inline bool to_box_on(const cacto_to_box* b) { return b && b->mode == CACTO_TO_BOUNDS_BOX; }
+inline bool to_box_ok(const cacto_to_box* b, int na) {
+  if (!b) return true;
+  if ((b->mode != CACTO_TO_BOUNDS_NONE && b->mode != CACTO_TO_BOUNDS_BOX) || b->reserved != 0) return false;
+  if (b->mode == CACTO_TO_BOUNDS_BOX)
+    for (int j = 0; j < na && j < CACTO_MAX_ACTION; ++j)
+      if (!(b->lo[j] < b->hi[j])) return false;  // also a NaN
+  return true;
+}
+// A null system leaves nb_action unknown: the first entry, which every system has, is checked
+inline int to_box_na(const cacto_sys* sys) { return sys ? sys->host.p.nb_action : 1; }
+inline ToBoxDev to_box_dev(const cacto_to_box* b) {
+  ToBoxDev d;
+  for (int j = 0; j < CACTO_MAX_ACTION; ++j) {
+    d.lo[j] = b->lo[j];
+    d.hi[j] = b->hi[j];
+  }
+  return d;
+}
+// f(bounds of the call as the kernels take them)
+template <class F>
+int to_with_box(const cacto_to_box* box, F f) {
+  if (to_box_on(box)) return f(to_box_dev(box));
+  return f(ToNoBox{});
+}
+
+// The bounds are a property of the call alone: reported before the other arguments and before the
+// system is looked at, so with a null one (nb_action unknown) the first entry is what is checked
+#define CACTO_TO_REQUIRE_BOX(box, sys, who)             \
+  CACTO_REQUIRE(to_box_ok(box, to_box_na(sys)),         \
+                who ": bad bounds (mode: CACTO_TO_BOUNDS_NONE or CACTO_TO_BOUNDS_BOX; reserved 0; lo[j] < hi[j], no NaN)")
+
 }  // namespace cacto

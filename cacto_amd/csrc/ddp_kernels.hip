@@ -87,12 +87,14 @@ __global__ void k_jac_extract(const double* __restrict__ ws, int B, double* __re
 }
 
 // The fused pass for the closed-form systems (SI, car, DI): one thread per episode computes each
-// step's A, B, l_x, l_xx inline and runs the Riccati recursion (sequential in t).
-template <int NJ>
+// step's A, B, l_x, l_xx inline and runs the Riccati recursion (sequential in t). BX: the bounds of
+// the call (ToNoBox / ToBoxDev, ddp_device.h); under bounds each node's Q_u, Q_xu and Qbar_uu are masked
+// (ddp_label_mask) before the same inverse and products.
+template <int NJ, class BX>
 __global__ void __launch_bounds__(64) k_ddp_backward(const SysDevice* __restrict__ sdp, const double* __restrict__ S,
                                                       int64_t ldS, const double* __restrict__ U, int64_t ldU,
                                                       const int32_t* __restrict__ nsteps, int n_ep, double mu,
-                                                      double* __restrict__ dVdx) {
+                                                      double* __restrict__ dVdx, BX bx) {
   constexpr int N = DdpDims<NJ>::N, M = DdpDims<NJ>::M, ns = Dims<NJ>::NS, na = Dims<NJ>::NA;
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n_ep) return;
@@ -205,6 +207,7 @@ __global__ void __launch_bounds__(64) k_ddp_backward(const SysDevice* __restrict
         const double luu = r == c ? p.scale * (-w_run[6] * (2.0 + p.w_b * 90.0 * pow(u[r] / um, 8.0) / (um * um))) : 0.0;
         Quu[r * M + c] = luu + s + (r == c ? mu : 0.0);
       }
+    if constexpr (BX::on) ddp_label_mask<N, M>(bx, u, Qu, Quu, Qxu);
     double Qi[M * M];
     small_inverse<M>(Quu, Qi);
     // K = Qbar^-1 Q_xu^T [M x N], k = Qbar^-1 Q_u [M]
@@ -250,13 +253,16 @@ __global__ void __launch_bounds__(64) k_ddp_backward(const SysDevice* __restrict
 // The Riccati recursion of the split pass with one wavefront per episode: the lanes share each
 // step's matrix products (outputs spread over lanes, operands in LDS), so the N = 12 recursion of
 // UR5 is ~N^3 / 64 dependent FMAs per product instead of N^3 on one thread. Same products, same
-// summation order as k_ddp_backward; Qbar_uu^-1 (M x M) on lane 0.
-template <int NJ>
+// summation order as k_ddp_backward; Qbar_uu^-1 (M x M) on lane 0, which under bounds (BX) also
+// decides which controls are held and masks Qbar_uu, Q_u and the columns of Q_xu (ddp_label_mask): no
+// other lane touches those between the barriers around its stage, and the barrier after it makes the
+// zeroed columns visible to the V_x / Q_xu Qbar^-1 stage.
+template <int NJ, class BX>
 __global__ void __launch_bounds__(64) k_ddp_riccati_wave(const SysDevice* __restrict__ sdp,
                                                          const double* __restrict__ U, int64_t ldU,
                                                          const int32_t* __restrict__ nsteps, int n_ep, double mu,
                                                          const double* __restrict__ ws, int64_t ldS,
-                                                         double* __restrict__ dVdx) {
+                                                         double* __restrict__ dVdx, BX bx) {
   using RC = DdpRec<NJ>;
   constexpr int N = RC::N, M = RC::M, ns = Dims<NJ>::NS, na = Dims<NJ>::NA;
   __shared__ double sA[N * N], sB[N * M], sLx[N], sLxx[N * N], sVx[N], sVxx[N * N], sU[M];
@@ -342,6 +348,7 @@ __global__ void __launch_bounds__(64) k_ddp_riccati_wave(const SysDevice* __rest
       double a[M * M], inv[M * M];
 #pragma unroll
       for (int k = 0; k < M * M; ++k) a[k] = sQuu[k];
+      if constexpr (BX::on) ddp_label_mask<N, M>(bx, sU, sQu, a, sQxu);
       small_inverse<M>(a, inv);
 #pragma unroll
       for (int r = 0; r < M; ++r) {
@@ -404,7 +411,7 @@ int ddp_workspace(cacto_sys* sys, size_t bytes, double** out) {
 template <int NJ>
 struct LaunchDdp {
   static int run(const cacto_sys* sys, const double* S, int64_t ldS, const double* U, int64_t ldU, const int32_t* n,
-                 int n_ep, double mu, double* out, hipStream_t st) {
+                 int n_ep, double mu, const cacto_to_box* box, double* out, hipStream_t st) {
     if constexpr (!DdpDims<NJ>::ok) {
       set_error("cacto_ddp_backward: supported for the single integrator, car and prismatic chains (double integrator)");
       return CACTO_EUNSUPPORTED;
@@ -450,11 +457,18 @@ struct LaunchDdp {
           hipLaunchKernelGGL(k_ddp_derivs<NJ>, dim3(ceil_div(n_ep, 64), (unsigned)ldS), dim3(64), 0, st, sys->dev, S,
                              ldS, U, ldU, n, n_ep, ws);
         CACTO_CHECK_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_ddp_riccati_wave<NJ>, dim3(n_ep), dim3(64), 0, st, sys->dev, U, ldU, n, n_ep, mu, ws,
-                           ldS, out);
+        // the recursion: one instantiation per bounds mode (the derivative kernels know no bounds)
+        to_with_box(box, [&](auto bx) {
+          hipLaunchKernelGGL((k_ddp_riccati_wave<NJ, decltype(bx)>), dim3(n_ep), dim3(64), 0, st, sys->dev, U, ldU, n,
+                             n_ep, mu, ws, ldS, out, bx);
+          return CACTO_OK;
+        });
       } else {
-        hipLaunchKernelGGL(k_ddp_backward<NJ>, dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S, ldS, U, ldU,
-                           n, n_ep, mu, out);
+        to_with_box(box, [&](auto bx) {
+          hipLaunchKernelGGL((k_ddp_backward<NJ, decltype(bx)>), dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S,
+                             ldS, U, ldU, n, n_ep, mu, out, bx);
+          return CACTO_OK;
+        });
       }
       CACTO_CHECK_HIP(hipGetLastError());
       return CACTO_OK;
@@ -507,14 +521,21 @@ struct LaunchJac {
 
 int cacto_ddp_workspace(cacto_sys* sys, size_t bytes, double** out) { return ddp_workspace(sys, bytes, out); }
 
-extern "C" int cacto_ddp_backward(const cacto_sys* sys, const double* S_traj_d, int64_t ldS, const double* U_traj_d,
-                                  int64_t ldU, const int32_t* nsteps_d, int n_ep, double mu, double* dVdx_d,
-                                  void* stream) {
+extern "C" int cacto_ddp_backward_box(const cacto_sys* sys, const double* S_traj_d, int64_t ldS, const double* U_traj_d,
+                                      int64_t ldU, const int32_t* nsteps_d, int n_ep, double mu, double* dVdx_d,
+                                      void* stream, const cacto_to_box* box) {
+  CACTO_TO_REQUIRE_BOX(box, sys, "cacto_ddp_backward");
   CACTO_REQUIRE(sys && S_traj_d && U_traj_d && nsteps_d && dVdx_d && n_ep >= 0 && ldS >= 1 && ldU >= 0,
                 "cacto_ddp_backward: bad arguments");
   if (n_ep == 0) return CACTO_OK;
-  return dispatch_nj<LaunchDdp>(sys->host.p, sys, S_traj_d, ldS, U_traj_d, ldU, nsteps_d, n_ep, mu, dVdx_d,
+  return dispatch_nj<LaunchDdp>(sys->host.p, sys, S_traj_d, ldS, U_traj_d, ldU, nsteps_d, n_ep, mu, box, dVdx_d,
                                 as_stream(stream));
+}
+
+extern "C" int cacto_ddp_backward(const cacto_sys* sys, const double* S_traj_d, int64_t ldS, const double* U_traj_d,
+                                  int64_t ldU, const int32_t* nsteps_d, int n_ep, double mu, double* dVdx_d,
+                                  void* stream) {
+  return cacto_ddp_backward_box(sys, S_traj_d, ldS, U_traj_d, ldU, nsteps_d, n_ep, mu, dVdx_d, stream, nullptr);
 }
 
 extern "C" int cacto_env_jacobians(const cacto_sys* sys, const double* S_d, const double* A_d, int B, double* Fx_d,

@@ -75,25 +75,8 @@ struct Gains {
   View k, K;  // K: element (i, j) of step t at index i * N + j
 };
 
-// The control bounds of a call (cacto_to_box), a template parameter of every kernel below and its
-// last argument. ToNoBox: the unbounded problem; every function is then what it is without the
-// parameter. ToBoxDev: lo <= u <= hi holds for every control a roll-out applies (the warm start's
-// included), and every node of the backward pass solves a box QP (box_qp.h) in place of the linear
-// system: control-limited DDP (Tassa, Mansard, Todorov, ICRA 2014).
-struct ToNoBox {
-  static constexpr bool on = false;
-  __device__ __forceinline__ double clamp(int, double v) const { return v; }
-};
-struct ToBoxDev {
-  static constexpr bool on = true;
-  double lo[CACTO_MAX_ACTION], hi[CACTO_MAX_ACTION];
-  __device__ __forceinline__ double clamp(int j, double v) const { return fmin(fmax(v, lo[j]), hi[j]); }
-  // control j sits on a bound and the gradient component qu points out of the box: it takes no part
-  // in the stopping rule
-  __device__ __forceinline__ bool held(int j, double u, double qu) const {
-    return (u == lo[j] && qu > 0.0) || (u == hi[j] && qu < 0.0);
-  }
-};
+// The control bounds of a call (ToNoBox / ToBoxDev, ddp_device.h) are a template parameter of every
+// kernel below and its last argument.
 
 // The gains of a node under bounds, on one thread: k = argmin 1/2 x^T Qbar x + Q_u^T x over
 // lo - ubar <= x <= hi - ubar (the offsets by box_offset_lo / box_offset_hi, so that a clamped control's
@@ -1393,33 +1376,6 @@ inline bool to_opts_ok(const cacto_to_opts* o) {
 }
 inline bool to_opts_psd(const cacto_to_opts* o) { return o && o->hessian == CACTO_TO_HESS_PSD; }
 
-// cacto_to_box: NULL and mode NONE mean no bounds (lo, hi are then not looked at). A box needs
-// lo[j] < hi[j], neither a NaN, for j < na; an infinite entry leaves that side open.
-inline bool to_box_on(const cacto_to_box* b) { return b && b->mode == CACTO_TO_BOUNDS_BOX; }
-inline bool to_box_ok(const cacto_to_box* b, int na) {
-  if (!b) return true;
-  if ((b->mode != CACTO_TO_BOUNDS_NONE && b->mode != CACTO_TO_BOUNDS_BOX) || b->reserved != 0) return false;
-  if (b->mode == CACTO_TO_BOUNDS_BOX)
-    for (int j = 0; j < na && j < CACTO_MAX_ACTION; ++j)
-      if (!(b->lo[j] < b->hi[j])) return false;  // also a NaN
-  return true;
-}
-// A null system leaves nb_action unknown: the first entry, which every system has, is checked
-inline int to_box_na(const cacto_sys* sys) { return sys ? sys->host.p.nb_action : 1; }
-inline ToBoxDev to_box_dev(const cacto_to_box* b) {
-  ToBoxDev d;
-  for (int j = 0; j < CACTO_MAX_ACTION; ++j) {
-    d.lo[j] = b->lo[j];
-    d.hi[j] = b->hi[j];
-  }
-  return d;
-}
-// f(bounds of the call as the kernels take them)
-template <class F>
-int to_with_box(const cacto_to_box* box, F f) {
-  if (to_box_on(box)) return f(to_box_dev(box));
-  return f(ToNoBox{});
-}
 
 // the (dynamics, reward) combinations of the six systems, as cacto_ddp_backward
 template <int NJ>
@@ -1633,11 +1589,7 @@ struct LaunchToPlan {
 // other arguments are looked at.
 #define CACTO_TO_REQUIRE_OPTS(opts, who) \
   CACTO_REQUIRE(to_opts_ok(opts), who ": bad options (hessian: CACTO_TO_HESS_EXACT or CACTO_TO_HESS_PSD; reserved words 0)")
-// ... and so are the bounds, right after them: before the system is looked at, so with a null one
-// (nb_action unknown) the first entry is what is checked
-#define CACTO_TO_REQUIRE_BOX(box, sys, who)             \
-  CACTO_REQUIRE(to_box_ok(box, to_box_na(sys)),         \
-                who ": bad bounds (mode: CACTO_TO_BOUNDS_NONE or CACTO_TO_BOUNDS_BOX; reserved 0; lo[j] < hi[j], no NaN)")
+// ... and so are the bounds, right after them (CACTO_TO_REQUIRE_BOX, ddp_device.h)
 
 // The kernels a plan describes are the same with and without bounds (the box QP needs no LDS and no
 // launch of its own)

@@ -32,7 +32,8 @@ def parse_args(argv=None):
     that many loops), --to-path (which kernels solve the TO batch, cacto_amd.to.PATHS) and
     --accept-maxiter (keep episodes whose solve stopped at max_iter). --to-hessian (the node Hessian
     of the TO's backward pass, cacto_amd.to.HESSIANS; exact when absent), --to-bounds (hard control
-    limits of the TO, the conf's u_min / u_max; none when absent), --plots, --fig-path and
+    limits of the TO, the conf's u_min / u_max; none when absent), --to-labels (the Sobolev labels
+    after a solve, cacto_amd.to.LABELS; bounded needs --to-bounds conf; reference when absent), --plots, --fig-path and
     --eval-every (the evaluation stage) and --seeds (several seeds at once, train_ensemble; not with
     --seed or --plots) are in the dict only when they are given. Returns a dict."""
     p = argparse.ArgumentParser(prog="python -m cacto_amd.main", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -71,6 +72,9 @@ def parse_args(argv=None):
     p.add_argument("--to-bounds", type=str, default=argparse.SUPPRESS, choices=["none", "conf"],
                    help="Hard control limits of the trajectory optimiser: none (the reference's penalty alone), or "
                         "the conf's u_min / u_max enforced by control-limited DDP (default: none)")
+    p.add_argument("--to-labels", type=str, default=argparse.SUPPRESS, choices=["reference", "bounded"],
+                   help="Sobolev labels after a TO solve: the reference's unconstrained dV/dx, or with --to-bounds conf "
+                        "the recursion that leaves the controls a limit holds out (default: reference)")
     p.add_argument("--plots", action="store_true", default=argparse.SUPPRESS,
                    help="Run the evaluation stage: value grid, TO trajectories, return and roll-out figures")
     p.add_argument("--fig-path", type=str, default=argparse.SUPPRESS,
@@ -78,6 +82,8 @@ def parse_args(argv=None):
     p.add_argument("--eval-every", type=int, default=argparse.SUPPRESS,
                    help="With --plots: evaluate in every K-th loop only (default: 1)")
     args = vars(p.parse_args(argv))
+    if args.get("to_labels") == "bounded" and args.get("to_bounds", "none") != "conf":
+        p.error("--to-labels bounded needs --to-bounds conf: the labels take the bounds of the solve")
     if "seeds" in args:
         if seed_given:
             p.error("--seed and --seeds exclude each other")
@@ -94,6 +100,8 @@ def train_kwargs(args):
         kw["to_cfg"]["hessian"] = args["to_hessian"]
     if "to_bounds" in args:
         kw["to_cfg"]["bounds"] = args["to_bounds"]
+    if "to_labels" in args:
+        kw["to_cfg"]["labels"] = args["to_labels"]
     if args.get("plots"):
         kw.update(evaluate=True, eval_every=args.get("eval_every", 1))
     return args["system_id"], kw

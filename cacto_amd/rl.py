@@ -665,7 +665,7 @@ class RL_AC:
         if pre is None:
             return res
         sol = TrOp.solve_batch(pre["S0"], pre["warm"], pre["live"], cfg=cfg)
-        return self.samples_collect(res, pre, sol, TrOp, buffer, accept_maxiter)
+        return self.samples_collect(res, pre, sol, TrOp, buffer, accept_maxiter, cfg=cfg)
 
     def samples_rollout(self, ep, ICS_list):
         """compute_samples up to its TrOp.solve_batch: the result dict with its counters at zero, and
@@ -689,10 +689,12 @@ class RL_AC:
         live = torch.where((roll["status"] == 0) & (n_d > 0), n_d, torch.full_like(n_d, -1))
         return res, dict(E=E, T=T, S0=S0_d, n=n_d, roll_status=roll["status"], warm=warm, live=live)
 
-    def samples_collect(self, res, pre, sol, TrOp, buffer, accept_maxiter=False):
+    def samples_collect(self, res, pre, sol, TrOp, buffer, accept_maxiter=False, cfg=None):
         """compute_samples from its TrOp.solve_batch on: `sol` is the solve of samples_rollout's
-        inputs `pre` (S [E, T + 1, ns], U [E, T, na], step_cost [E, T + 1], status, iters). Fills and
-        returns `res`."""
+        inputs `pre` (S [E, T + 1, ns], U [E, T, na], step_cost [E, T + 1], status, iters). `cfg`: the
+        solve's; its `labels` key says which Sobolev labels follow (cacto_amd.to.label_bounds). Fills
+        and returns `res`."""
+        from .to import label_bounds
         E, T, S0_d, n_d = pre["E"], pre["T"], pre["S0"], pre["n"]
         roll = dict(status=pre["roll_status"])
         kept_d = torch.empty(E, dtype=torch.int32, device=DEVICE)
@@ -712,7 +714,7 @@ class RL_AC:
         if rows > buffer.N:
             raise ValueError("cannot add more rows than REPLAY_SIZE at once")
         if TrOp.w_S != 0:
-            dev["dVdx"] = TrOp.backward_pass_batch(sol["S"], sol["U"], kept_d)
+            dev["dVdx"] = TrOp.backward_pass_batch(sol["S"], sol["U"], kept_d, bounds=label_bounds(cfg))
         if self.conf.env_RL:
             dev["S_RL"], dev["R_RL"], dev["EE_RL"] = self.env_rl_episodes(S0_d, sol["U"], kept_d, T + 1)
             S_rows, R_rows, R_sum, negate = dev["S_RL"], dev["R_RL"], dev["R_RL"], 0
@@ -1036,5 +1038,5 @@ class Ensemble:
                         status=sol["status"][a:a + E].contiguous(), iters=sol["iters"][a:a + E].contiguous(),
                         J=sol["J"][a:a + E].contiguous())
             a += E
-            out[r] = self.learners[r].samples_collect(out[r], pre, part, TrOp, buffers[r], accept_maxiter)
+            out[r] = self.learners[r].samples_collect(out[r], pre, part, TrOp, buffers[r], accept_maxiter, cfg=cfg)
         return out

@@ -18,7 +18,8 @@ stationary point of the same problem, not necessarily the same one.
   TO_System_Solve        the reference's per-episode signature and return tuple (TO.py:100)
   TO_Solve               TO.py:102-117: + the time column and the Sobolev label dV/dx
   backward_pass[_batch]  TO.backward_pass (TO.py:119-202, `cacto_ddp_backward`) along any recorded
-                         trajectory — a TO solution or the policy roll-outs of RL_AC.rollout_batch
+                         trajectory — a TO solution or the policy roll-outs of RL_AC.rollout_batch;
+                         with `bounds` the bound-aware labels (`cacto_ddp_backward_box`)
 """
 import ctypes as C
 import numbers
@@ -47,13 +48,18 @@ CONVERGED, MAXITER, FAILED = L.CACTO_TO_CONVERGED, L.CACTO_TO_MAXITER, L.CACTO_T
 # node of the backward pass, feedback on the unclamped controls only, every roll-out and the warm start
 # clamped, gtol on the projected gradient). "none" / None: the reference's problem, where the penalty
 # alone holds the controls; "conf": conf.u_min, conf.u_max; a pair (lo, hi) of nb_action values each
-# (+-inf: that side open). Every returned control then lies in [lo, hi] exactly. The Sobolev labels
-# (backward_pass) stay the reference's unconstrained dV/dx along the bounded trajectory.
+# (+-inf: that side open). Every returned control then lies in [lo, hi] exactly.
+# labels: which Sobolev labels follow a solve (TO_Solve, RL_AC.compute_samples; the solver itself does
+# not read the key). "reference": TO.backward_pass as the reference has it, the unconstrained dV/dx
+# along the solution, bounded or not; "bounded": backward_pass with the bounds of the same cfg, which
+# leaves the controls a bound holds out of the recursion (cacto_ddp_backward_box). Needs `bounds`.
 DEFAULT_CFG = dict(max_iter=400, max_ls=10, gtol=1e-4, armijo=1e-4, mu_min=1e-6, mu_up=10.0, mu_down=10.0,
-                   mu_max=1e10, poll_every=8, path=0, hessian="exact", bounds="none")
+                   mu_max=1e10, poll_every=8, path=0, hessian="exact", bounds="none", labels="reference")
 PATHS = {"default": L.CACTO_TO_PATH_DEFAULT, "wave": L.CACTO_TO_PATH_WAVE}
 HESSIANS = {"exact": L.CACTO_TO_HESS_EXACT, "psd": L.CACTO_TO_HESS_PSD}
-NOT_FIELDS = ("hessian", "bounds")      # cfg keys that travel beside the ToCfg (make_opts, make_box)
+LABELS = ("reference", "bounded")
+NOT_FIELDS = ("hessian", "bounds", "labels")    # cfg keys that travel beside the ToCfg (make_opts, make_box,
+                                                # label_bounds)
 
 
 def make_opts(cfg=None):
@@ -111,11 +117,31 @@ def make_box(cfg=None, conf=None):
     return box
 
 
+def label_bounds(cfg=None):
+    """The `bounds` that the labels after a solve with `cfg` take (backward_pass's argument): None for
+    labels="reference" (and for a ToCfg, which holds no such key), the cfg's own `bounds` for
+    labels="bounded". ValueError for an unknown `labels`, and for "bounded" in a cfg without bounds."""
+    if not isinstance(cfg, dict):
+        return None
+    lab = cfg.get("labels", DEFAULT_CFG["labels"])
+    if not isinstance(lab, str) or lab not in LABELS:
+        raise ValueError("unknown TO labels %r (one of %s)" % (lab, list(LABELS)))
+    if lab == "reference":
+        return None
+    b = cfg.get("bounds", DEFAULT_CFG["bounds"])
+    none = isinstance(b, L.ToBox) and b.mode == L.CACTO_TO_BOUNDS_NONE
+    if b is None or (isinstance(b, str) and b == "none") or none:
+        raise ValueError("TO labels=\"bounded\" needs bounds (\"conf\" or a pair (lo, hi)) in the same cfg, "
+                         "not bounds=%r" % (b,))
+    return b
+
+
 def make_cfg(cfg=None):
-    """The 64-byte ToCfg (cacto_to_cfg) of a cfg dict over DEFAULT_CFG. The `hessian` and `bounds` keys
-    are checked here but are no fields of that struct: they travel in the ToOpts that make_opts(cfg)
-    and the ToBox that make_box(cfg, conf) give, and a caller who hands solve_batch / solve_plan a
-    ToCfg passes those as `opts` and `bounds`."""
+    """The 64-byte ToCfg (cacto_to_cfg) of a cfg dict over DEFAULT_CFG. The `hessian`, `bounds` and
+    `labels` keys are checked here but are no fields of that struct: they travel in the ToOpts that
+    make_opts(cfg) and the ToBox that make_box(cfg, conf) give, and a caller who hands solve_batch /
+    solve_plan a ToCfg passes those as `opts` and `bounds`; `labels` is read after the solve
+    (label_bounds)."""
     vals = dict(DEFAULT_CFG)
     vals.update(cfg or {})
     unknown = set(vals) - set(DEFAULT_CFG)
@@ -127,6 +153,7 @@ def make_cfg(cfg=None):
         vals["path"] = PATHS[vals["path"]]
     make_opts(vals)
     make_box(vals)
+    label_bounds(vals)
     c = L.ToCfg()
     for k, v in vals.items():
         if k not in NOT_FIELDS:
@@ -273,14 +300,15 @@ class TO:
     def TO_Solve(self, ICS_state, init_TO_states, init_TO_controls, T, cfg=None, accept_maxiter=False):
         """TO.py:102-117: (TO_controls, TO_states [T+1, ns] with the time column ICS time + dt * t,
         success_flag, TO_ee_pos_arr, TO_step_cost, dVdx [T+1, ns]); dVdx from backward_pass
-        (mu = 1e-9) when w_S != 0, else zeros. On failure (None, None, 0, None, None, None)."""
+        (mu = 1e-9; with labels="bounded" in cfg under the cfg's bounds) when w_S != 0, else zeros.
+        On failure (None, None, 0, None, None, None)."""
         flag, U, X, ee, _, step_cost = self.TO_System_Solve(ICS_state, init_TO_states, init_TO_controls, T, cfg=cfg,
                                                             accept_maxiter=accept_maxiter)
         if flag == 0:
             return None, None, flag, None, None, None
         T = int(T)
         if self.w_S != 0:
-            dVdx = self.backward_pass(T + 1, X, U)
+            dVdx = self.backward_pass(T + 1, X, U, bounds=label_bounds(cfg))
         else:
             dVdx = np.zeros((T + 1, self.conf.nb_state))
         t0 = float(np.asarray(ICS_state, dtype=np.float64).reshape(-1)[-1])
@@ -288,30 +316,38 @@ class TO:
         return U, X, flag, ee, step_cost, dVdx
 
     # ------------------------------------------------------------------ Sobolev labels
-    def backward_pass(self, T, TO_states, TO_controls, mu=1e-9):
+    def backward_pass(self, T, TO_states, TO_controls, mu=1e-9, bounds=None):
         """TO.py:119-202 for one episode: T states s_0..s_{T-1} ([T, >= ns-1]; a time column is
-        ignored), T-1 controls. Returns V_x [T, ns] (numpy float64, last column 0)."""
+        ignored), T-1 controls. Returns V_x [T, ns] (numpy float64, last column 0). bounds: as
+        backward_pass_batch's."""
         ns, na = self.conf.nb_state, self.conf.nb_action
         S = np.zeros((1, T, ns))
         S[0, :, :ns - 1] = np.asarray(TO_states, dtype=np.float64)[:T, :ns - 1]
         U = np.zeros((1, max(T - 1, 1), na))
         U[0, :T - 1] = np.asarray(TO_controls, dtype=np.float64)[:T - 1, :na]
         out = self.backward_pass_batch(torch.as_tensor(S, device=DEVICE), torch.as_tensor(U, device=DEVICE),
-                                       torch.tensor([T - 1], dtype=torch.int32, device=DEVICE), mu=mu)
+                                       torch.tensor([T - 1], dtype=torch.int32, device=DEVICE), mu=mu, bounds=bounds)
         return out[0].cpu().numpy()
 
-    def backward_pass_batch(self, S_traj, U_traj, nsteps, mu=1e-9, out=None, status=None):
+    def backward_pass_batch(self, S_traj, U_traj, nsteps, mu=1e-9, out=None, status=None, bounds=None):
         """Device batch: S_traj [E, ldS, ns] f64, U_traj [E, ldU, na] f64, nsteps [E] int32 (Te per
         episode: Te + 1 states). Returns dVdx [E, ldS, ns] f64 (rows past Te untouched).
         status [E] int32 (device, a rollout's): episodes with status != 0 were dropped for a NaN
-        state (RL.py:229-231, main.py:236) and get no labels (their rows stay untouched)."""
+        state (RL.py:229-231, main.py:236) and get no labels (their rows stay untouched).
+        bounds (as the cfg key; None / "none": the reference's recursion, cacto_ddp_backward): the
+        bound-aware labels of cacto_ddp_backward_box. A control that sits on a limit with the reward's
+        gradient Q_u pointing out of the box is held: it takes no part in that node's
+        V_x = Q_x - Q_xu Qbar^-1 Q_u, V_xx = Q_xx - Q_xu Qbar^-1 Q_xu^T. On a trajectory where no
+        control is held the result is the unbounded call's bit for bit."""
         E, ldS = S_traj.shape[0], S_traj.shape[1]
         if out is None:
             out = torch.zeros_like(S_traj)
         if status is not None:
             nsteps = torch.where(status.to(device=DEVICE) == 0, nsteps.to(device=DEVICE, dtype=torch.int32),
                                  torch.full_like(nsteps, -1, dtype=torch.int32, device=DEVICE)).contiguous()
-        L.lib().call("cacto_ddp_backward", self.sys.handle, dptr(S_traj, torch.float64), ldS,
+        box = make_box(bounds, self.conf)
+        sfx, extra = ("_box", (C.byref(box),)) if box is not None else ("", ())
+        L.lib().call("cacto_ddp_backward" + sfx, self.sys.handle, dptr(S_traj, torch.float64), ldS,
                      dptr(U_traj, torch.float64), U_traj.shape[1], dptr(nsteps, torch.int32), E, float(mu),
-                     dptr(out, torch.float64), stream())
+                     dptr(out, torch.float64), stream(), *extra)
         return out

@@ -13,7 +13,9 @@
  *   cacto_env_bound_control_cost  Env.bound_control_cost environment.py:158-163
  *   cacto_rollout          RL_AC.create_TO_init loop RL.py:223-231 / PLOT.rollout plot_utils.py:245-279
  *   cacto_rollout_rewards  Env.step reward / get_end_effector_position over recorded trajectories
- *   cacto_ddp_backward     TO.backward_pass TO.py:119-202 (dV/dx Sobolev labels)
+ *   cacto_ddp_backward     TO.backward_pass TO.py:119-202 (dV/dx Sobolev labels);
+ *                          cacto_ddp_backward_box: the same pass under the solve's hard control limits
+ *                          (cacto_to_box), the labels of the bounded problem (no reference counterpart)
  *   cacto_to_solve         TO.TO_System_Solve TO.py:37-100: the trajectory optimisation itself, as a
  *                          batched iLQR on the same cost and dynamics (the reference: CasADi + IPOPT,
  *                          one NLP per episode); cacto_to_backward_gains / cacto_to_forward are its
@@ -614,8 +616,9 @@ typedef struct {
  *               candidates and cacto_to_forward_box's open-loop roll-out included. The warm start is
  *               clamped the same way before it is rolled out, and J[0] is the clamped warm start's cost.
  *     Every control the solver returns lies in [lo, hi] exactly. The two solvers of a system agree
- *     bit for bit. cacto_ddp_backward (the Sobolev labels) knows no bounds: along a bounded trajectory
- *     it gives the reference's unconstrained dV/dx (TO.py:119-202).
+ *     bit for bit. The Sobolev labels take the bounds through cacto_ddp_backward_box (below);
+ *     cacto_ddp_backward itself stays the reference's unconstrained dV/dx (TO.py:119-202) along any
+ *     trajectory, a bounded one included.
  * An unknown mode, a non-zero reserved word, or with CACTO_TO_BOUNDS_BOX a NaN or lo[j] >= hi[j] for
  * some j < nb_action: CACTO_EINVAL "bad bounds" (workspace query: 0), no device work, reported right
  * after the options and before the other arguments; with a null system, where nb_action is not known
@@ -627,6 +630,24 @@ typedef struct {
   int32_t reserved; /* must be 0 */
   double lo[CACTO_MAX_ACTION], hi[CACTO_MAX_ACTION]; /* first nb_action entries; -inf / +inf: that side open */
 } cacto_to_box;     /* 136 bytes */
+
+/* cacto_ddp_backward under bounds: the Sobolev labels of the problem a bounded solve solved. Per
+ * node, from Q_x, Q_u, Q_xx, Q_xu, Qbar_uu = Q_uu + mu I formed exactly as in cacto_ddp_backward (the
+ * reward's derivatives), control j is held when it sits on or outside a limit and the gradient points
+ * out of the box: u_j <= lo_j with Q_u,j < 0, or u_j >= hi_j with Q_u,j > 0 (the first-order rule of
+ * the solver's stopping test in the reward's sign; no box QP, so no positive definite Qbar_uu is
+ * asked for). With f the controls not held,
+ *   V_x = Q_x - Q_xu[:, f] Qbar_uu[f, f]^-1 Q_u[f],  V_xx = Q_xx - Q_xu[:, f] Qbar_uu[f, f]^-1 Q_xu[:, f]^T
+ * (f empty: V_x = Q_x, V_xx = Q_xx). At a stationary point of the bounded problem Q_u[f] = 0, and V_x
+ * is the adjoint of the constrained problem: the gradient of its optimal cost. Along a trajectory on
+ * which no control is held the output equals cacto_ddp_backward's bit for bit. Everything else (the
+ * terminal row, the time column, nsteps_d[e] < 0, rows past Te, the exact cost Hessian whatever
+ * Hessian the solve used, the workspace) is cacto_ddp_backward's. NULL or mode CACTO_TO_BOUNDS_NONE:
+ * that call itself. Bad bounds: CACTO_EINVAL "bad bounds" before the other arguments are looked at,
+ * no device work. */
+int cacto_ddp_backward_box(const cacto_sys* sys, const double* S_traj_d, int64_t ldS, const double* U_traj_d,
+                           int64_t ldU, const int32_t* nsteps_d, int n_ep, double mu, double* dVdx_d, void* stream,
+                           const cacto_to_box* box);
 
 /* One regularised backward pass along given trajectories (cost convention, l_xu = 0):
  *   Qbar_uu = Q_uu + mu I, k = -Qbar_uu^-1 Q_u, K = -Qbar_uu^-1 Q_ux,

@@ -1,14 +1,94 @@
 """Diagnostic: cacto_ddp_backward time for a system's bench rollout batch (the bench's ddp_labels).
-    python tools/ddp_time.py SYSTEM R"""
+    python tools/ddp_time.py SYSTEM R [--bounds conf [--on-limit SHARE]]
+--bounds conf: clamp the rollout's controls to the conf's u_min / u_max (the states stay the
+rollout's: the label pass reads a recorded trajectory, it does not simulate), then time both entries
+on those trajectories — cacto_ddp_backward and cacto_ddp_backward_box under the conf's bounds — three
+rounds of K calls each, alternating, and print the share of controls on a limit and, from the CPU
+helper (tests/ddp_box_ref.py) on the first episodes, the share a bound holds. --on-limit SHARE (0..1)
+first scales each control dimension so that about that share of the rollout's controls reaches a limit
+(an untrained actor's stay far inside): the cost of the pass where controls are held."""
 import os
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 
 
+def _time(to, S, A, n, out, K, bounds):
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(K):
+        to.backward_pass_batch(S, A, n, out=out, bounds=bounds)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / K
+
+
+def bounded(system, R, K=10, rounds=3, sample=4, on_limit=0.0):
+    import numpy as np
+    import torch
+    from cacto_amd.to import TO
+    conf, env, rl = bench.make_learner(system)
+    roll = bench.rollout_phase(rl, conf, env, R, 3, 1, 1, 0)
+    to = TO(env, conf, w_S=rl.w_S)
+    lo = torch.as_tensor(np.asarray(conf.u_min, dtype=np.float64), device="cuda")
+    hi = torch.as_tensor(np.asarray(conf.u_max, dtype=np.float64), device="cuda")
+    S = roll["out"]["S"]
+    A = roll["out"]["A"].double()
+    nsteps = roll["nsteps"].astype(np.int32)
+    n = torch.as_tensor(nsteps, device="cuda")
+    live = torch.arange(A.shape[1], device="cuda")[None, :, None] < n[:, None, None]
+    if on_limit > 0.0:
+        for j in range(A.shape[2]):
+            mag = A[:, :, j][live[:, :, 0]].abs()
+            A[:, :, j] *= float(hi[j]) / max(float(torch.quantile(mag[:1000000], 1.0 - on_limit).item()), 1e-300)
+    A = torch.minimum(torch.maximum(A, lo), hi).contiguous()
+    on = float((((A <= lo) | (A >= hi)) & live).sum().item()) / max(float(live.sum().item()) * A.shape[2], 1.0)
+    plain, box = to.backward_pass_batch(S, A, n), to.backward_pass_batch(S, A, n, bounds="conf")     # warm-up
+    differ = int((plain != box).any(dim=2).any(dim=1).sum().item())
+    ms = {None: [], "conf": []}
+    for _ in range(rounds):
+        for b in (None, "conf"):
+            ms[b].append(_time(to, S, A, n, plain if b is None else box, K, b))
+    steps = int(nsteps.sum())
+    print("%s R=%d clamped rollouts: %d Riccati steps, %.1f%% of the controls on a limit, %d of %d episodes' labels "
+          "differ between the entries" % (system, R, steps, 100.0 * on, differ, R))
+    for b, name in ((None, "cacto_ddp_backward"), ("conf", "cacto_ddp_backward_box")):
+        v = ms[b]
+        print("  %-24s %s ms (min %.3f, spread %.1f%%)" % (name, " ".join("%.3f" % x for x in v), min(v),
+                                                          100.0 * (max(v) - min(v)) / min(v)))
+    print("  box / plain (min over rounds): %.3f" % (min(ms["conf"]) / min(ms[None])))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ddp_box_ref as D
+    Sh, Ah = S[:sample].cpu().numpy(), A[:sample].cpu().numpy()
+    held = total = 0
+    for e in range(min(sample, R)):
+        Te = int(nsteps[e])
+        h = D.backward_pass_box(conf, Sh[e, :Te + 1], Ah[e, :Te], conf.u_min, conf.u_max)[1]
+        held, total = held + int(h.sum()), total + h.size
+    print("  held share (CPU helper, first %d episodes): %.1f%% of %d controls" % (min(sample, R),
+                                                                              100.0 * held / max(total, 1), total))
+
+
 def main():
-    system, R = sys.argv[1], int(sys.argv[2])
+    args = [a for a in sys.argv[1:]]
+    bounds = None
+    if "--bounds" in args:
+        i = args.index("--bounds")
+        bounds = args[i + 1]
+        del args[i:i + 2]
+        if bounds != "conf":
+            sys.exit("ddp_time.py: --bounds takes conf")
+    on_limit = 0.0
+    if "--on-limit" in args:
+        i = args.index("--on-limit")
+        on_limit = float(args[i + 1])
+        del args[i:i + 2]
+    system, R = args[0], int(args[1])
+    if bounds:
+        return bounded(system, R, on_limit=on_limit)
     conf, env, rl = bench.make_learner(system)
     roll = bench.rollout_phase(rl, conf, env, R, 3, 1, 1, 0)
     _, d = bench.ddp_labels(rl, conf, env, roll, K=10)
