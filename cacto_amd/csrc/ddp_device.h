@@ -1,6 +1,7 @@
 // Device code shared by the DDP label pass (ddp_kernels.hip) and the trajectory optimiser
-// (to_kernels.hip): cost and dynamics derivatives of every system, and the per-(episode, step)
-// derivative kernels of the split pass with their [t][k][e] record layout.
+// (to_kernels.hip): cost and dynamics derivatives of every system, the per-(episode, step)
+// derivative kernels of the split pass with their [t][k][e] record layout and its sizing, the
+// control bounds of a call and, host side, the support check of both files' entries.
 #pragma once
 #include "ad.h"
 #include "internal.h"
@@ -214,6 +215,14 @@ __device__ inline void ddp_lx(const SysDevice& sd, const double* w, const double
       }
     }
   }
+}
+
+// l_u and the diagonal entry of l_uu of the reward - w6 scale (u^2 + w_b (u / u_max)^10) at control
+// u_j (bound_control_cost, environment_TO.py:201-206); the optimiser (the cost) negates them.
+__device__ __forceinline__ void ddp_lu(const cacto_sys_params& p, double w6, double u, int j, double* lu, double* luu) {
+  const double um = p.u_max[j];
+  *lu = p.scale * (-w6 * (2.0 * u + p.w_b * 10.0 * pow(u / um, 9.0) / um));
+  *luu = p.scale * (-w6 * (2.0 + p.w_b * 90.0 * pow(u / um, 8.0) / (um * um)));
 }
 
 // Discrete dynamics Jacobians A [N*N], B [N*M] (augmented_derivative).
@@ -452,6 +461,15 @@ template <int NJ>
 struct DdpPrim {
   static constexpr int MINV = 0, QDD = NJ * NJ, R = NJ * NJ + NJ;
 };
+
+// Doubles of the derivative records of `steps` steps of n_ep episodes, followed (revolute chains) by
+// the primal block k_ddp_prim hands to k_ddp_tan: what cacto_ddp_launch_derivs writes at `rec`.
+template <int NJ>
+inline size_t ddp_rec_doubles(int n_ep, int64_t steps) {
+  size_t n = (size_t)steps * DdpRec<NJ>::R * n_ep;
+  if constexpr (NJ > 2) n += (size_t)steps * DdpPrim<NJ>::R * n_ep;
+  return n;
+}
 
 template <int NJ>
 __global__ void __launch_bounds__(64) k_ddp_prim(const SysDevice* __restrict__ sdp, const double* __restrict__ S,
@@ -700,6 +718,23 @@ template <class F>
 int to_with_box(const cacto_to_box* box, F f) {
   if (to_box_on(box)) return f(to_box_dev(box));
   return f(ToNoBox{});
+}
+
+// Host: the (dynamics, reward) combinations of the six systems, for every entry of the label pass
+// and the optimiser (chains: the prismatic pair, or 3 / 6 revolute joints). who: the entry's name.
+template <int NJ>
+inline bool ddp_supported(const cacto_sys* sys, const char* who) {
+  bool ok = DdpDims<NJ>::ok;
+  if (ok) {
+    const int rk = sys->host.p.reward_kind;
+    const bool rk_ok = NJ == -2 ? rk == CACTO_REW_CAR_PARK
+                                : NJ > 0 ? (sys->host.p.const_dyn ? rk == CACTO_REW_PLANAR
+                                                                 : rk == CACTO_REW_MANIPULATOR || rk == CACTO_REW_UR5)
+                                         : rk == CACTO_REW_PLANAR;
+    ok = rk_ok && !(NJ > 0 && (sys->host.p.const_dyn ? NJ != 2 : NJ == 2));
+  }
+  if (!ok) set_error(std::string(who) + ": unsupported (dynamics, reward) combination");
+  return ok;
 }
 
 // The bounds are a property of the call alone: reported before the other arguments and before the

@@ -23,6 +23,9 @@
 // differentiated by hyper-dual numbers (ad.h); revolute chains (manipulator NJ = 3, UR5 NJ = 6) take
 // ddq_dq, ddq_dv from hyper-dual RNEA (computeABADerivatives) and l_x, l_xx through hyper-dual
 // forward kinematics.
+// cacto_ddp_launch_derivs (internal.h) is the library's one launcher of the derivative kernels (label
+// pass, cacto_env_jacobians, to_kernels.hip). Each pass keeps its wave recursion written out in its
+// own file: a shared front half was slower.
 #include "ddp_device.h"
 
 namespace cacto {
@@ -147,9 +150,8 @@ __global__ void __launch_bounds__(64) k_ddp_backward(const SysDevice* __restrict
     }
 #pragma unroll
     for (int j = 0; j < M; ++j) {
-      // l_u, l_uu: - w6 * (u^2 + w_b (u / u_max)^10) (bound_control_cost, environment_TO.py:201-206)
-      const double um = p.u_max[j];
-      const double lu = p.scale * (-w_run[6] * (2.0 * u[j] + p.w_b * 10.0 * pow(u[j] / um, 9.0) / um));
+      double lu, luu;
+      ddp_lu(p, w_run[6], u[j], j, &lu, &luu);
       double s = 0.0;
 #pragma unroll
       for (int k = 0; k < N; ++k)
@@ -203,8 +205,8 @@ __global__ void __launch_bounds__(64) k_ddp_backward(const SysDevice* __restrict
 #pragma unroll
         for (int k = 0; k < N; ++k)
           if (b_nz<NJ>(k, r)) s += B[k * M + r] * VB[k * M + c];
-        const double um = p.u_max[r];
-        const double luu = r == c ? p.scale * (-w_run[6] * (2.0 + p.w_b * 90.0 * pow(u[r] / um, 8.0) / (um * um))) : 0.0;
+        double lu, luu = 0.0;
+        if (r == c) ddp_lu(p, w_run[6], u[r], r, &lu, &luu);
         Quu[r * M + c] = luu + s + (r == c ? mu : 0.0);
       }
     if constexpr (BX::on) ddp_label_mask<N, M>(bx, u, Qu, Quu, Qxu);
@@ -312,8 +314,8 @@ __global__ void __launch_bounds__(64) k_ddp_riccati_wave(const SysDevice* __rest
         sQx[r] = sLx[r] + s;
       } else {
         const int j = o - N * N - N * M - N;
-        const double um = p.u_max[j], u = sU[j];
-        const double lu = p.scale * (-w6 * (2.0 * u + p.w_b * 10.0 * pow(u / um, 9.0) / um));
+        double lu, luu;
+        ddp_lu(p, w6, sU[j], j, &lu, &luu);
 #pragma unroll
         for (int k = 0; k < N; ++k) s += sB[k * M + j] * sVx[k];
         sQu[j] = lu + s;
@@ -337,9 +339,8 @@ __global__ void __launch_bounds__(64) k_ddp_riccati_wave(const SysDevice* __rest
         const int q = o - N * N - N * M, r = q / M, c = q - r * M;
 #pragma unroll
         for (int k = 0; k < N; ++k) s += sB[k * M + r] * sVB[k * M + c];
-        const double um = p.u_max[r];
-        const double luu =
-            r == c ? p.scale * (-w6 * (2.0 + p.w_b * 90.0 * pow(sU[r] / um, 8.0) / (um * um))) : 0.0;
+        double lu, luu = 0.0;
+        if (r == c) ddp_lu(p, w6, sU[r], r, &lu, &luu);
         sQuu[q] = luu + s + (r == c ? mu : 0.0);
       }
     }
@@ -393,10 +394,9 @@ __global__ void __launch_bounds__(64) k_ddp_riccati_wave(const SysDevice* __rest
 
 using namespace cacto;
 
-namespace {
 // Grow-only device workspace of the split pass, owned by the system handle (freed by
 // cacto_sys_destroy). Growing frees the old block (hipFree synchronises the device).
-int ddp_workspace(cacto_sys* sys, size_t bytes, double** out) {
+int cacto_ddp_workspace(cacto_sys* sys, size_t bytes, double** out) {
   if (bytes > sys->ddp_ws_bytes) {
     if (sys->ddp_ws) CACTO_CHECK_HIP(hipFree(sys->ddp_ws));
     sys->ddp_ws = nullptr;
@@ -408,6 +408,41 @@ int ddp_workspace(cacto_sys* sys, size_t bytes, double** out) {
   return CACTO_OK;
 }
 
+namespace {
+// The derivative kernels over (episode, step < steps): k_ddp_derivs for car_park; for the revolute
+// chains the primal / cost-derivative / per-direction tangent kernels, the primal block behind the
+// records, or with CACTO_DDP_SPLIT=0 k_ddp_derivs too (the same records bit for bit).
+template <int NJ>
+struct LaunchDerivs {
+  static int run(const cacto_sys* sys, const double* S, int64_t ldS, const double* U, int64_t ldU, const int32_t* n,
+                 int n_ep, double* rec, int64_t steps, bool want_lx, hipStream_t st) {
+    if constexpr (NJ > 2 || NJ == -2) {
+      const dim3 g(ceil_div(n_ep, 64), (unsigned)steps);
+      if constexpr (NJ > 2) {
+        static const char* split_env = std::getenv("CACTO_DDP_SPLIT");
+        if (!(split_env && split_env[0] == '0')) {
+          double* pw = rec + (size_t)steps * DdpRec<NJ>::R * n_ep;
+          hipLaunchKernelGGL(k_ddp_prim<NJ>, g, dim3(64), 0, st, sys->dev, S, ldS, U, ldU, n, n_ep, rec, pw);
+          CACTO_CHECK_HIP(hipGetLastError());
+          if (want_lx) {
+            hipLaunchKernelGGL(k_ddp_lx<NJ>, g, dim3(64), 0, st, sys->dev, S, ldS, n, n_ep, rec);
+            CACTO_CHECK_HIP(hipGetLastError());
+          }
+          hipLaunchKernelGGL(k_ddp_tan<NJ>, dim3(g.x, g.y, 2 * NJ), dim3(64), 0, st, sys->dev, S, ldS, n, n_ep, rec, pw);
+          CACTO_CHECK_HIP(hipGetLastError());
+          return CACTO_OK;
+        }
+      }
+      hipLaunchKernelGGL(k_ddp_derivs<NJ>, g, dim3(64), 0, st, sys->dev, S, ldS, U, ldU, n, n_ep, rec);
+      CACTO_CHECK_HIP(hipGetLastError());
+      return CACTO_OK;
+    } else {  // not reached: every caller is a car_park or revolute-chain instantiation
+      set_error("cacto_ddp_launch_derivs: the closed-form systems have no derivative records");
+      return CACTO_EUNSUPPORTED;
+    }
+  }
+};
+
 template <int NJ>
 struct LaunchDdp {
   static int run(const cacto_sys* sys, const double* S, int64_t ldS, const double* U, int64_t ldU, const int32_t* n,
@@ -416,48 +451,15 @@ struct LaunchDdp {
       set_error("cacto_ddp_backward: supported for the single integrator, car and prismatic chains (double integrator)");
       return CACTO_EUNSUPPORTED;
     } else {
-      const int rk = sys->host.p.reward_kind;
-      const bool rk_ok = NJ == -2 ? rk == CACTO_REW_CAR_PARK
-                                  : NJ > 0 ? (sys->host.p.const_dyn ? rk == CACTO_REW_PLANAR
-                                                                   : rk == CACTO_REW_MANIPULATOR || rk == CACTO_REW_UR5)
-                                           : rk == CACTO_REW_PLANAR;
-      // chains: the DI's prismatic pair (constant M) or revolute chains of 3 / 6 joints
-      if (!rk_ok || (NJ > 0 && (sys->host.p.const_dyn ? NJ != 2 : NJ == 2))) {
-        set_error("cacto_ddp_backward: unsupported (dynamics, reward) combination");
-        return CACTO_EUNSUPPORTED;
-      }
+      if (!ddp_supported<NJ>(sys, "cacto_ddp_backward")) return CACTO_EUNSUPPORTED;
+      // one instantiation of a recursion per bounds mode (the derivative kernels know no bounds)
       if constexpr (NJ > 2 || NJ == -2) {
         // split pass: per-step derivatives over (episode, step), then the recursion
-        using RC = DdpRec<NJ>;
         double* ws = nullptr;
-        const int rc = ddp_workspace(const_cast<cacto_sys*>(sys), (size_t)ldS * RC::R * n_ep * sizeof(double), &ws);
+        const int rc = cacto_ddp_workspace(const_cast<cacto_sys*>(sys), ddp_rec_doubles<NJ>(n_ep, ldS) * sizeof(double), &ws);
         if (rc != CACTO_OK) return rc;
-        // revolute chains: primal / per-direction tangent / cost-derivative kernels (CACTO_DDP_SPLIT=0:
-        // the one-thread-per-step k_ddp_derivs)
-        static const char* split_env = std::getenv("CACTO_DDP_SPLIT");
-        const bool split = NJ > 2 && !(split_env && split_env[0] == '0');
-        if constexpr (NJ > 2) {
-          if (split) {
-            using PC = DdpPrim<NJ>;
-            double* pw = nullptr;
-            const size_t rec_bytes = (size_t)ldS * RC::R * n_ep * sizeof(double);
-            const int rc2 = ddp_workspace(const_cast<cacto_sys*>(sys), rec_bytes + (size_t)ldS * PC::R * n_ep * sizeof(double),
-                                          &ws);
-            if (rc2 != CACTO_OK) return rc2;
-            pw = ws + (size_t)ldS * RC::R * n_ep;
-            const dim3 g(ceil_div(n_ep, 64), (unsigned)ldS);
-            hipLaunchKernelGGL(k_ddp_prim<NJ>, g, dim3(64), 0, st, sys->dev, S, ldS, U, ldU, n, n_ep, ws, pw);
-            CACTO_CHECK_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_ddp_lx<NJ>, g, dim3(64), 0, st, sys->dev, S, ldS, n, n_ep, ws);
-            CACTO_CHECK_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_ddp_tan<NJ>, dim3(g.x, g.y, 2 * NJ), dim3(64), 0, st, sys->dev, S, ldS, n, n_ep, ws, pw);
-          }
-        }
-        if (!split)
-          hipLaunchKernelGGL(k_ddp_derivs<NJ>, dim3(ceil_div(n_ep, 64), (unsigned)ldS), dim3(64), 0, st, sys->dev, S,
-                             ldS, U, ldU, n, n_ep, ws);
-        CACTO_CHECK_HIP(hipGetLastError());
-        // the recursion: one instantiation per bounds mode (the derivative kernels know no bounds)
+        const int rc2 = LaunchDerivs<NJ>::run(sys, S, ldS, U, ldU, n, n_ep, ws, ldS, true, st);
+        if (rc2 != CACTO_OK) return rc2;
         to_with_box(box, [&](auto bx) {
           hipLaunchKernelGGL((k_ddp_riccati_wave<NJ, decltype(bx)>), dim3(n_ep), dim3(64), 0, st, sys->dev, U, ldU, n,
                              n_ep, mu, ws, ldS, out, bx);
@@ -471,8 +473,8 @@ struct LaunchDdp {
         });
       }
       CACTO_CHECK_HIP(hipGetLastError());
-      return CACTO_OK;
     }
+    return CACTO_OK;
   }
 };
 template <int NJ>
@@ -489,24 +491,18 @@ struct LaunchJac {
       }
       if constexpr (NJ > 2) {
         using RC = DdpRec<NJ>;
-        using PC = DdpPrim<NJ>;
         constexpr int ns = Dims<NJ>::NS;
-        // step 0 of B one-step episodes: only A, B are read, so no l_x kernel
-        const size_t rec = (size_t)2 * RC::R * B, pwn = (size_t)PC::R * B, s2 = (size_t)2 * B * ns;
+        // step 0 of B one-step episodes: only A, B are read, so no l_x, l_xx
+        const size_t rec = ddp_rec_doubles<NJ>(B, 1), s2 = (size_t)2 * B * ns;
         double* ws = nullptr;
-        const int rc = ddp_workspace(const_cast<cacto_sys*>(sys), (rec + pwn + s2 + B) * sizeof(double), &ws);
+        const int rc = cacto_ddp_workspace(const_cast<cacto_sys*>(sys), (rec + s2 + B) * sizeof(double), &ws);
         if (rc != CACTO_OK) return rc;
-        double* pw = ws + rec;
-        double* S2 = pw + pwn;
+        double* S2 = ws + rec;
         int32_t* n1 = reinterpret_cast<int32_t*>(S2 + s2);
         hipLaunchKernelGGL(k_jac_prep<NJ>, dim3(ceil_div(B * 2 * ns, 256)), dim3(256), 0, st, S, B, S2, n1);
         CACTO_CHECK_HIP(hipGetLastError());
-        const dim3 g(ceil_div(B, 64), 1);
-        hipLaunchKernelGGL(k_ddp_prim<NJ>, g, dim3(64), 0, st, sys->dev, S2, (int64_t)2, U, (int64_t)1, n1, B, ws, pw);
-        CACTO_CHECK_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_ddp_tan<NJ>, dim3(g.x, 1, 2 * NJ), dim3(64), 0, st, sys->dev, S2, (int64_t)2, n1, B, ws,
-                           pw);
-        CACTO_CHECK_HIP(hipGetLastError());
+        const int rc2 = LaunchDerivs<NJ>::run(sys, S2, 2, U, 1, n1, B, ws, 1, false, st);
+        if (rc2 != CACTO_OK) return rc2;
         constexpr int per = RC::N * RC::N + RC::N * RC::M;
         hipLaunchKernelGGL(k_jac_extract<NJ>, dim3(ceil_div(B * per, 256)), dim3(256), 0, st, ws, B, Fx, Fu);
       } else {
@@ -519,7 +515,10 @@ struct LaunchJac {
 };
 }  // namespace
 
-int cacto_ddp_workspace(cacto_sys* sys, size_t bytes, double** out) { return ddp_workspace(sys, bytes, out); }
+int cacto_ddp_launch_derivs(const cacto_sys* sys, const double* S, int64_t ldS, const double* U, int64_t ldU,
+                            const int32_t* nsteps, int n_ep, double* rec, int64_t steps, bool want_lx, hipStream_t st) {
+  return dispatch_nj<LaunchDerivs>(sys->host.p, sys, S, ldS, U, ldU, nsteps, n_ep, rec, steps, want_lx, st);
+}
 
 extern "C" int cacto_ddp_backward_box(const cacto_sys* sys, const double* S_traj_d, int64_t ldS, const double* U_traj_d,
                                       int64_t ldU, const int32_t* nsteps_d, int n_ep, double mu, double* dVdx_d,

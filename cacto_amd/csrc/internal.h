@@ -55,6 +55,11 @@ int cacto_const_dyn_init(cacto_sys* sys);  // SysDevice::cd_* of a prismatic-onl
 int cacto_build_wgrad_adam_items(cacto_sys* sys);  // learn_kernels.hip
 // ddp_kernels.hip: the handle's grow-only device workspace (derivative records), at least `bytes`
 int cacto_ddp_workspace(cacto_sys* sys, size_t bytes, double** out);
+// ddp_kernels.hip: the derivative records (DdpRec, [t][k][e]) of steps 0 .. steps-1 of n_ep
+// episodes at rec, ddp_rec_doubles(n_ep, steps) doubles (car_park, revolute chains); want_lx: l_x,
+// l_xx too. The one launcher of k_ddp_prim / _lx / _tan / _derivs and reader of CACTO_DDP_SPLIT.
+int cacto_ddp_launch_derivs(const cacto_sys* sys, const double* S, int64_t ldS, const double* U, int64_t ldU,
+                            const int32_t* nsteps, int n_ep, double* rec, int64_t steps, bool want_lx, hipStream_t st);
 void cacto_dp_release(cacto_sys* sys);  // learn_host.hip: the RCCL communicators and buffers
 // replay_kernels.hip: the one PER route (which sampler and priority update a batch of B takes on a
 // tree of `capacity` leaves, whether the pipelined loops defer the sampler's count into the priority

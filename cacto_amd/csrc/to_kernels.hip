@@ -17,7 +17,9 @@
 //   mu         x mu_up (at least mu_min) after a failed factorisation or line search, / mu_down
 //              after an accepted step (0 once below mu_min).
 // The derivatives are those of cacto_ddp_backward (ddp_device.h; they are the reward's, so the
-// signs flip on the way in). Everything is float64 VALU and LDS; there is no matrix-core work here.
+// signs flip on the way in; car_park's and the chains' records come from cacto_ddp_launch_derivs of
+// ddp_kernels.hip, this file instantiates no derivative kernel). Everything is float64 VALU and
+// LDS; there is no matrix-core work here.
 // With cacto_to_opts.hessian = CACTO_TO_HESS_PSD every node's l_xx is first replaced by its projection
 // onto the positive semidefinite cone (psd_project.h): a bool template parameter of the solving
 // kernels, and for the records of the label pass's derivative kernels one more kernel
@@ -95,14 +97,6 @@ __device__ __forceinline__ bool to_box_gain(const ToBoxDev& bx, const double* Qu
     bh[j] = box_offset_hi(ub[j], bx.hi[j]);
   }
   return to_box_qp<M>(Hb, Qu, bl, bh, k, free_mask, Lf);
-}
-
-// l_u, l_uu (diagonal) of the cost at control u_j: w6 scale (u^2 + w_b (u/u_max)^10)' — the
-// expressions of k_ddp_backward with the sign of the cost
-__device__ __forceinline__ void to_lu(const cacto_sys_params& p, double w6, double u, int j, double* lu, double* luu) {
-  const double um = p.u_max[j];
-  *lu = -(p.scale * (-w6 * (2.0 * u + p.w_b * 10.0 * pow(u / um, 9.0) / um)));
-  *luu = -(p.scale * (-w6 * (2.0 + p.w_b * 90.0 * pow(u / um, 8.0) / (um * um))));
 }
 
 // The TO cost of one node: -Env.reward; UR5.reward leaves the bound penalty to reward_batch
@@ -374,10 +368,10 @@ __device__ inline void to_node_record(const SysDevice& sd, const double* Minv, c
   for (int k = 0; k < N * M; ++k) r[RC::B + k] = B[k];
 #pragma unroll
   for (int j = 0; j < M; ++j) {
-    double lu, luu;
-    to_lu(p, w[6], cur.U.at(t, j), j, &lu, &luu);
-    r[TR::LU + j] = lu;
-    r[TR::LUU + j] = luu;
+    double lu, luu;  // the reward's, as l_x, l_xx above
+    ddp_lu(p, w[6], cur.U.at(t, j), j, &lu, &luu);
+    r[TR::LU + j] = -lu;
+    r[TR::LUU + j] = -luu;
   }
 }
 
@@ -718,14 +712,6 @@ constexpr int TO_SPLIT_THREADS = 256;
 
 inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 
-// doubles of derivative records (and, revolute chains, the primal workspace) for ldS steps
-template <int NJ>
-size_t to_rec_doubles(int n_ep, int64_t ldS) {
-  size_t n = (size_t)ldS * DdpRec<NJ>::R * n_ep;
-  if constexpr (NJ > 2) n += (size_t)ldS * DdpPrim<NJ>::R * n_ep;
-  return n;
-}
-
 // The workspace of cacto_to_solve as a solver sees it: 256-byte aligned blocks, carved in the
 // constructor and nowhere else (ws may be null: bytes alone is wanted). E = n_ep, L = ldS.
 //   thread  order [E] + hist [L + 1] | lanes: S [L][ns][E], U [L][na][E], cost [L][E], k [L][na][E],
@@ -779,7 +765,7 @@ struct ToWs {
         K = take<double>(ws, G);
       }
       close();
-      rec = take<double>(ws, to_rec_doubles<NJ>(n_ep, ldS));
+      rec = take<double>(ws, ddp_rec_doubles<NJ>(n_ep, ldS));
       close();
     }
   }
@@ -1059,11 +1045,11 @@ __device__ __forceinline__ ToPass to_gains_episode(ToGainsLds<NJ>& L, const cact
         L.sQx[r] = L.sLx[r] + s;
       } else {
         const int j = o - N * N - N * M - N;
-        double lu, luu;
-        to_lu(p, w6, L.sU[j], j, &lu, &luu);
+        double lu, luu;  // the reward's: negated
+        ddp_lu(p, w6, L.sU[j], j, &lu, &luu);
 #pragma unroll
         for (int k = 0; k < N; ++k) s += L.sB[k * M + j] * L.sVx[k];
-        L.sQu[j] = lu + s;
+        L.sQu[j] = -lu + s;
       }
     }
     __syncthreads();
@@ -1085,7 +1071,10 @@ __device__ __forceinline__ ToPass to_gains_episode(ToGainsLds<NJ>& L, const cact
 #pragma unroll
         for (int k = 0; k < N; ++k) s += L.sB[k * M + r] * L.sVB[k * M + c];
         double lu, luu = 0.0;
-        if (r == c) to_lu(p, w6, L.sU[r], r, &lu, &luu);
+        if (r == c) {
+          ddp_lu(p, w6, L.sU[r], r, &lu, &luu);
+          luu = -luu;
+        }
         L.sQuu[q] = luu + s;
       }
     }
@@ -1376,44 +1365,15 @@ inline bool to_opts_ok(const cacto_to_opts* o) {
 }
 inline bool to_opts_psd(const cacto_to_opts* o) { return o && o->hessian == CACTO_TO_HESS_PSD; }
 
-
-// the (dynamics, reward) combinations of the six systems, as cacto_ddp_backward
-template <int NJ>
-bool to_supported(const cacto_sys* sys, const char* who) {
-  bool ok = DdpDims<NJ>::ok;
-  if (ok) {
-    const int rk = sys->host.p.reward_kind;
-    const bool rk_ok = NJ == -2 ? rk == CACTO_REW_CAR_PARK
-                                : NJ > 0 ? (sys->host.p.const_dyn ? rk == CACTO_REW_PLANAR
-                                                                 : rk == CACTO_REW_MANIPULATOR || rk == CACTO_REW_UR5)
-                                         : rk == CACTO_REW_PLANAR;
-    ok = rk_ok && !(NJ > 0 && (sys->host.p.const_dyn ? NJ != 2 : NJ == 2));
-  }
-  if (!ok) set_error(std::string(who) + ": unsupported (dynamics, reward) combination");
-  return ok;
-}
-
-// the derivative kernels of the label pass over (episode, step); psd: then the projection of the
-// records' l_xx blocks (one launch more)
+// the label pass's derivative records over (episode, step) (cacto_ddp_launch_derivs,
+// ddp_kernels.hip); psd: then the projection of the records' l_xx blocks, on the launcher's grid
 template <int NJ>
 int to_launch_derivs(const cacto_sys* sys, const double* S, int64_t ldS, const double* U, int64_t ldU, const int32_t* n,
                      int n_ep, double* rec, bool psd, hipStream_t st) {
-  const dim3 g(ceil_div(n_ep, 64), (unsigned)ldS);
-  if constexpr (NJ > 2) {
-    double* pw = rec + (size_t)ldS * DdpRec<NJ>::R * n_ep;
-    hipLaunchKernelGGL(k_ddp_prim<NJ>, g, dim3(64), 0, st, sys->dev, S, ldS, U, ldU, n, n_ep, rec, pw);
-    CACTO_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_ddp_lx<NJ>, g, dim3(64), 0, st, sys->dev, S, ldS, n, n_ep, rec);
-    CACTO_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_ddp_tan<NJ>, dim3(g.x, g.y, 2 * NJ), dim3(64), 0, st, sys->dev, S, ldS, n, n_ep, rec, pw);
-  } else {
-    hipLaunchKernelGGL(k_ddp_derivs<NJ>, g, dim3(64), 0, st, sys->dev, S, ldS, U, ldU, n, n_ep, rec);
-  }
+  const int rc = cacto_ddp_launch_derivs(sys, S, ldS, U, ldU, n, n_ep, rec, ldS, true, st);
+  if (rc != CACTO_OK || !psd) return rc;
+  hipLaunchKernelGGL(k_to_psd_records<NJ>, dim3(ceil_div(n_ep, 64), (unsigned)ldS), dim3(64), 0, st, n, n_ep, rec);
   CACTO_CHECK_HIP(hipGetLastError());
-  if (psd) {
-    hipLaunchKernelGGL(k_to_psd_records<NJ>, g, dim3(64), 0, st, n, n_ep, rec);
-    CACTO_CHECK_HIP(hipGetLastError());
-  }
   return CACTO_OK;
 }
 
@@ -1422,7 +1382,7 @@ struct LaunchToGains {
   static int run(const cacto_sys* sys, const double* S, int64_t ldS, const double* U, int64_t ldU, const int32_t* n,
                  int n_ep, double mu, bool psd, const cacto_to_box* box, double* k, double* K, double* dJ, int32_t* pd,
                  hipStream_t st) {
-    if (!to_supported<NJ>(sys, "cacto_to_backward_gains")) return CACTO_EUNSUPPORTED;
+    if (!ddp_supported<NJ>(sys, "cacto_to_backward_gains")) return CACTO_EUNSUPPORTED;
     return to_with_box(box, [&](auto bx) { return go(sys, S, ldS, U, ldU, n, n_ep, mu, psd, bx, k, K, dJ, pd, st); });
   }
   template <class BX>
@@ -1431,7 +1391,7 @@ struct LaunchToGains {
     if constexpr (DdpDims<NJ>::ok) {
       if constexpr (to_split<NJ>()) {
         double* rec = nullptr;
-        const int rc = cacto_ddp_workspace(const_cast<cacto_sys*>(sys), to_rec_doubles<NJ>(n_ep, ldS) * sizeof(double), &rec);
+        const int rc = cacto_ddp_workspace(const_cast<cacto_sys*>(sys), ddp_rec_doubles<NJ>(n_ep, ldS) * sizeof(double), &rec);
         if (rc != CACTO_OK) return rc;
         const int rc2 = to_launch_derivs<NJ>(sys, S, ldS, U, ldU, n, n_ep, rec, psd, st);
         if (rc2 != CACTO_OK) return rc2;
@@ -1456,7 +1416,7 @@ struct LaunchToForward {
   static int run(const cacto_sys* sys, const double* S, int64_t ldS, const double* U, int64_t ldU, const double* k,
                  const double* K, const int32_t* n, int n_ep, double alpha, const cacto_to_box* box, double* Sn, double* Un,
                  double* cost, hipStream_t st) {
-    if (!to_supported<NJ>(sys, "cacto_to_forward")) return CACTO_EUNSUPPORTED;
+    if (!ddp_supported<NJ>(sys, "cacto_to_forward")) return CACTO_EUNSUPPORTED;
     return to_with_box(box, [&](auto bx) -> int {
       if constexpr (DdpDims<NJ>::ok) {
         hipLaunchKernelGGL((k_to_forward<NJ, decltype(bx)>), dim3(ceil_div(n_ep, 64)), dim3(64), 0, st, sys->dev, S, ldS, U,
@@ -1495,7 +1455,7 @@ struct LaunchToSolve {
   static int run(const cacto_sys* sys, const double* S0, const double* U_init, int64_t ldU, const int32_t* n, int n_ep,
                  int64_t ldS, const cacto_to_cfg* cfg, bool psd, const cacto_to_box* box, double* S, double* U, double* cost,
                  int32_t* status, int32_t* iters, double* J, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (!to_supported<NJ>(sys, "cacto_to_solve")) return CACTO_EUNSUPPORTED;
+    if (!ddp_supported<NJ>(sys, "cacto_to_solve")) return CACTO_EUNSUPPORTED;
     return to_with_box(box, [&](auto bx) {
       return go(sys, S0, U_init, ldU, n, n_ep, ldS, cfg, psd, bx, S, U, cost, status, iters, J, ws, ws_bytes, st);
     });
@@ -1566,7 +1526,7 @@ struct LaunchToSolve {
 template <int NJ>
 struct LaunchToPlan {
   static int run(const cacto_sys* sys, int path, bool psd, cacto_to_plan* out) {
-    if (!to_supported<NJ>(sys, "cacto_to_solve_plan")) return CACTO_EUNSUPPORTED;
+    if (!ddp_supported<NJ>(sys, "cacto_to_solve_plan")) return CACTO_EUNSUPPORTED;
     if constexpr (DdpDims<NJ>::ok) {
       switch (to_route<NJ>(path)) {
         case TO_SOLVER_THREAD: *out = cacto_to_plan{1, 64, 0, 0}; break;

@@ -24,11 +24,14 @@ def _setup(system):
     return conf, oenv.make_env(conf), TO(genv, conf, w_S=1e-2)
 
 
-def _episodes(conf, oe, n_ep, rng, zero_len=()):
-    """Trajectories of Env.simulate under random controls, lengths NSTEPS - int(t/dt)."""
+def _episodes(conf, oe, n_ep, rng, zero_len=(), max_steps=None):
+    """Trajectories of Env.simulate under random controls, lengths NSTEPS - int(t/dt) (at most
+    max_steps when given)."""
     ns, na = conf.nb_state, conf.nb_action
     S0 = [oe.reset(rng) for _ in range(n_ep)]
     T = [conf.NSTEPS - int(s[-1] / conf.dt) for s in S0]
+    if max_steps is not None:
+        T = [min(t, max_steps) for t in T]
     for k in zero_len:
         T[k] = 0
     L = max(T) + 1
@@ -87,6 +90,26 @@ def test_ddp_backward_bad_arguments_fail_loudly():
         L.lib().call("cacto_ddp_backward", to.sys.handle, dptr(S, torch.float64), 0, dptr(U, torch.float64), 3,
                      dptr(torch.tensor([2], dtype=torch.int32, device="cuda"), torch.int32), 1, 1e-9,
                      dptr(S, torch.float64), stream())
+
+
+def test_ddp_label_workspace_grows_between_calls():
+    """The handle's derivative-record workspace (records, then the chains' primal block: one
+    grow-only allocation sized by one function) grown by a later, larger call: the labels of 70
+    episodes on a handle that first ran 3 are those of a fresh handle bit for bit."""
+    from cacto_amd.environment import make_env
+    from cacto_amd.to import TO
+    conf = load_conf("manipulator")
+    S, U, T = _episodes(conf, oenv.make_env(conf), 70, random.Random(4), max_steps=6)
+    assert T.max() == 6
+    dev = lambda a, e: torch.as_tensor(np.ascontiguousarray(a[:e]), device="cuda")  # noqa: E731
+    grown = TO(make_env(conf), conf, w_S=1e-2)
+    grown.backward_pass_batch(dev(S, 3), dev(U, 3), dev(T, 3))
+    got = grown.backward_pass_batch(dev(S, 70), dev(U, 70), dev(T, 70))
+    fresh = TO(make_env(conf), conf, w_S=1e-2).backward_pass_batch(dev(S, 70), dev(U, 70), dev(T, 70))
+    torch.cuda.synchronize()
+    got, fresh = got.cpu().numpy(), fresh.cpu().numpy()
+    assert np.isfinite(fresh).all() and (fresh[int(T.argmax()), 0] != 0).any()
+    assert np.array_equal(got.view(np.uint64), fresh.view(np.uint64))
 
 
 def _labels_in_subprocess(system, split, S, U, T):
