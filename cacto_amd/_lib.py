@@ -119,6 +119,10 @@ CACTO_TO_PATH_DEFAULT, CACTO_TO_PATH_WAVE = 0, 1
 CACTO_TO_HESS_EXACT, CACTO_TO_HESS_PSD = 0, 1
 CACTO_TO_BOUNDS_NONE, CACTO_TO_BOUNDS_BOX = 0, 1
 PER_UPDATE_SET, PER_UPDATE_SUB, PER_UPDATE_CHAIN = 0, 1, 2
+# columns of cacto_validate's per_ep / totals (CACTO_VAL_* in the header)
+(CACTO_VAL_ROWS, CACTO_VAL_SUM_G, CACTO_VAL_SUM_G2, CACTO_VAL_SUM_V, CACTO_VAL_SSE_V, CACTO_VAL_SSE_G,
+ CACTO_VAL_SUM_L2, CACTO_VAL_SSE_CLOG, CACTO_VAL_SSE_U) = range(9)
+CACTO_VAL_COLS = CACTO_VAL_SSE_U + MAX_ACTION
 PER_RUN_SUB, PER_RUN_EMPTY = 256, 0x7f7f7f7f
 
 vp, i32, i64, dbl, flt, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_float, C.c_size_t
@@ -210,6 +214,9 @@ _SIGS = {
     "cacto_env_rl_episodes": (C.c_int, [vp, vp, vp, i64, vp, C.c_int, i64, vp, vp, vp, vp]),
     "cacto_collect_plan": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
     "cacto_episode_returns": (C.c_int, [vp, i64, vp, C.c_int, C.c_int, vp, vp]),
+    "cacto_validate_workspace_bytes": (sz, [vp, i64]),
+    "cacto_validate": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, vp, i64, C.c_int, vp, vp, vp, C.c_int, i64, vp, vp,
+                                 vp, sz, vp]),
     "cacto_buffer_gather": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "cacto_per_init": (C.c_int, [vp, vp, i64, vp]),
     "cacto_per_set_range": (C.c_int, [vp, vp, i64, i64, i64, i64, dbl, vp]),

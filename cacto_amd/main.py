@@ -3,6 +3,7 @@ evaluation stage (main.py:168, :249-252, :273, :279) as an option.
 
     python -m cacto_amd.main --system-id double_integrator --w-S 1e-2 [--plots]
     python -m cacto_amd.main --system-id double_integrator --w-S 1e-2 --seeds 0,1,2   # train_ensemble
+    python -m cacto_amd.main --system-id double_integrator --w-S 1e-2 --validate [--validate-csv FILE]
 
 Per loop: EP_UPDATE initial states from Env.reset (the host's `random`, as the reference), one
 RL_AC.compute_samples (roll-outs -> batched TO -> filter -> labels -> RL_Solve + ring write, all on
@@ -17,8 +18,15 @@ Env.reset per loop; car: 961 np.random.uniform per loop), so only a run with it 
 initial states on those systems. It is off by default: its TO solves over the full NSTEPS cost
 about a second per loop and each figure 0.07-0.08 s (DESIGN.md §3, "The evaluation stage");
 --eval-every K runs it in every K-th loop only.
+
+With --validate (train(validate=True)) every loop also compares the critic and the actor with the
+loop's TO trajectories before they are trained on (RL_AC.validate_samples: their initial states were
+drawn for this loop, so it is a held-out test) and logs one line; --validate-csv FILE writes the
+numbers, one row per loop (per seed and loop with --seeds). The stage draws no host random number and
+changes nothing that is trained; it is off by default ("The validation stage").
 """
 import argparse
+import csv
 import os
 import random
 
@@ -35,7 +43,8 @@ def parse_args(argv=None):
     limits of the TO, the conf's u_min / u_max; none when absent), --to-labels (the Sobolev labels
     after a solve, cacto_amd.to.LABELS; bounded needs --to-bounds conf; reference when absent), --plots, --fig-path and
     --eval-every (the evaluation stage) and --seeds (several seeds at once, train_ensemble; not with
-    --seed or --plots) are in the dict only when they are given. Returns a dict."""
+    --seed or --plots), --validate and --validate-csv (the validation stage; allowed with --seeds) are
+    in the dict only when they are given. Returns a dict."""
     p = argparse.ArgumentParser(prog="python -m cacto_amd.main", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument("--test-n", type=int, default=0, help="Test number")
     seed_given = []
@@ -81,7 +90,13 @@ def parse_args(argv=None):
                    help="Where --plots writes (default: 'Results <system-id>/Figures')")
     p.add_argument("--eval-every", type=int, default=argparse.SUPPRESS,
                    help="With --plots: evaluate in every K-th loop only (default: 1)")
+    p.add_argument("--validate", action="store_true", default=argparse.SUPPRESS,
+                   help="Run the validation stage: critic and actor against each loop's fresh TO trajectories")
+    p.add_argument("--validate-csv", type=str, default=argparse.SUPPRESS,
+                   help="With --validate: write the validation numbers to this CSV file, one row per loop")
     args = vars(p.parse_args(argv))
+    if "validate_csv" in args and not args.get("validate"):
+        p.error("--validate-csv needs --validate")
     if args.get("to_labels") == "bounded" and args.get("to_bounds", "none") != "conf":
         p.error("--to-labels bounded needs --to-bounds conf: the labels take the bounds of the solve")
     if "seeds" in args:
@@ -104,7 +119,32 @@ def train_kwargs(args):
         kw["to_cfg"]["labels"] = args["to_labels"]
     if args.get("plots"):
         kw.update(evaluate=True, eval_every=args.get("eval_every", 1))
+    if args.get("validate"):
+        kw["validate"] = True
     return args["system_id"], kw
+
+
+def validation_line(v, prefix=""):
+    """One log line for a validation record (train's `validation` entries)."""
+    fmt = lambda x: "-" if x is None else ("%.4g" % x if isinstance(x, float) else str(x))
+    keys = ("rows", "value_rmse", "value_r2", "grad_rel", "sobolev_loss", "actor_rmse_u", "warm", "gap_mean",
+            "gap_rel_median")
+    return "{}Validation loop {} (updates {}): {}".format(prefix, v["ep"], v["update_step_counter"],
+                                                         "  ".join("%s=%s" % (k, fmt(v[k])) for k in keys))
+
+
+def write_validation_csv(path, outs, with_seed=False):
+    """train's (or each of train_ensemble's) `validation` lists as one CSV: a row per loop, in the
+    order of `outs`; with_seed: `seed` and `N_try` columns first. A None (no labels) is an empty cell."""
+    from .rl import VALIDATION_KEYS
+    cols = (["seed", "N_try"] if with_seed else []) + ["ep", "update_step_counter"] + list(VALIDATION_KEYS)
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(cols)
+        for o in outs:
+            for v in o["validation"]:
+                row = dict(v, seed=o.get("seed"), N_try=o.get("N_try"))
+                w.writerow(["" if row[c] is None else row[c] for c in cols])
 
 
 # main.py:249: these evaluate after every learn_and_update, UR5 only when the update counter hits
@@ -113,7 +153,7 @@ EVALUATED_EVERY_LOOP = ("single_integrator", "double_integrator", "car_park", "c
 
 
 def train(conf, seed=0, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=False, n_loops=None, weights=None,
-          recover_training=None, log=print, evaluate=False, draw=True, eval_every=1):
+          recover_training=None, log=print, evaluate=False, draw=True, eval_every=1, validate=False):
     """main.py:145-165, :216-262, :276. `to_cfg`: a dict over cacto_amd.to.DEFAULT_CFG; `weights`:
     setup_model's dict of initial weights; `recover_training`: (path, N_try, step) of checkpoints to
     start from (the update counter starts at step). A loop in which no episode is kept raises
@@ -127,8 +167,15 @@ def train(conf, seed=0, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=False, n_l
     conf.Fig_path unless `draw` is false or Fig_path is unset; the data is computed either way.
     Without `evaluate` nothing of it runs and no random number is drawn for it.
 
+    `validate`: run the validation stage in every loop (RL_AC.validate_samples, inside
+    compute_samples, before the loop's rows are trained on) and log one line per loop. It reads the
+    networks and writes nothing they or the replay buffer depend on, so the trained result is the
+    same bits with and without it.
+
     Returns dict(update_step_counter, ep_reward_arr, counts_per_loop, RLAC, buffer, evaluation,
-    returns, evaluation_seconds): evaluation is the stage's records in call order, each dict(kind
+    returns, evaluation_seconds, validation): validation is one validate_samples dict per loop with
+    `ep` and `update_step_counter` (the counter before that loop's updates) added, an empty list
+    without `validate`; evaluation is the stage's records in call order, each dict(kind
     ('traj' | 'value' | 'return' | 'rollout'), update_step_counter, ep (None outside the loop),
     data (the numbers behind the figure; for 'rollout' dict(returns, p_ee, states))); returns is
     PLOT.rollout's dict (None without evaluate); evaluation_seconds PLOT.seconds."""
@@ -171,14 +218,20 @@ def train(conf, seed=0, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=False, n_l
     ep_arr_idx = 0
     ep_reward_arr = np.zeros(int(conf.EP_UPDATE) * n_sched) * np.nan
     counts_per_loop = []
+    validation = []
+    val_kw = dict(validate=True) if validate else {}     # off: compute_samples is called as it always was
     for ep in range(loops):
         init_rand_state = [env.reset() for _ in range(conf.EP_UPDATE)]
-        res = RLAC.compute_samples(ep, init_rand_state, TrOp, buffer, cfg=to_cfg, accept_maxiter=accept_maxiter)
+        res = RLAC.compute_samples(ep, init_rand_state, TrOp, buffer, cfg=to_cfg, accept_maxiter=accept_maxiter,
+                                   **val_kw)
         counts_per_loop.append({k: res[k] for k in ("rows", "n_kept", "zero_length", "nan_rollouts", "converged",
                                                     "maxiter", "failed")})
         n = res["n_kept"]
         if n == 0:
             raise RuntimeError("loop %d: no episode of %d was kept (%s)" % (ep, conf.EP_UPDATE, counts_per_loop[-1]))
+        if validate:
+            validation.append(dict(res["validation"], ep=ep, update_step_counter=update_step_counter))
+            log(validation_line(validation[-1]))
         update_step_counter = RLAC.learn_and_update(update_step_counter, buffer, ep)
         if evaluate and ep % eval_every == 0 and (update_step_counter % conf.plot_rollout_interval_diff_loc == 0
                                                   or conf.system_id in EVALUATED_EVERY_LOOP):
@@ -208,7 +261,7 @@ def train(conf, seed=0, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=False, n_l
                                      states=np.array(plot_fun.states_all_sim)))
     return dict(update_step_counter=update_step_counter, ep_reward_arr=ep_reward_arr, counts_per_loop=counts_per_loop,
                 RLAC=RLAC, buffer=buffer, evaluation=evaluation, returns=returns,
-                evaluation_seconds=dict(plot_fun.seconds) if evaluate else None)
+                evaluation_seconds=dict(plot_fun.seconds) if evaluate else None, validation=validation)
 
 
 class HostRng:
@@ -240,7 +293,7 @@ class HostRng:
 
 
 def train_ensemble(conf, seeds, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=False, n_loops=None, weights=None,
-                   recover_training=None, log=print):
+                   recover_training=None, log=print, validate=False):
     """train for every seed of `seeds` at once (the reference's ten-seed sets,
     generate_tests_set_script.py) in one process on one GPU: one Env, one TO, per seed an NN, an
     RL_AC (replica r runs as N_try + r) and a replay buffer; per loop one Ensemble.compute_samples
@@ -250,7 +303,8 @@ def train_ensemble(conf, seeds, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=Fa
     train(conf, seed=seed, N_try=N_try + r, ...), bit for bit: every replica has its own copy of the
     host generators (HostRng), swapped in around its draws in train's order.
 
-    train's arguments without the evaluation stage (which draws host random numbers of its own).
+    train's arguments without the evaluation stage (which draws host random numbers of its own);
+    `validate` as train's, per replica with that replica's networks (it draws none).
     `weights`: one setup_model dict for all replicas, or a list of one per seed. `recover_training`:
     (path, N_try, step) as train's, read as the checkpoints of an earlier ensemble run: replica r
     starts from <path>/N_try_<N_try + r>/*_<step>.h5 — what train(seed, N_try=N_try + r,
@@ -300,12 +354,15 @@ def train_ensemble(conf, seeds, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=Fa
     ep_arr_idx = [0] * R
     ep_reward_arr = [np.zeros(int(conf.EP_UPDATE) * n_sched) * np.nan for _ in range(R)]
     counts_per_loop = [[] for _ in range(R)]
+    validation = [[] for _ in range(R)]
+    val_kw = dict(validate=True) if validate else {}
     for ep in range(loops):
         ics = []
         for r in range(R):
             with rngs[r]:
                 ics.append([env.reset() for _ in range(conf.EP_UPDATE)])
-        res = ens.compute_samples(ep, ics, TrOp, buffers, cfg=to_cfg, accept_maxiter=accept_maxiter)
+        res = ens.compute_samples(ep, ics, TrOp, buffers, cfg=to_cfg, accept_maxiter=accept_maxiter,
+                                  **val_kw)
         for r in range(R):
             counts_per_loop[r].append({k: res[r][k] for k in ("rows", "n_kept", "zero_length", "nan_rollouts",
                                                               "converged", "maxiter", "failed")})
@@ -313,6 +370,10 @@ def train_ensemble(conf, seeds, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=Fa
             if res[r]["n_kept"] == 0:
                 raise RuntimeError("seed %d (N_try %d), loop %d: no episode of %d was kept (%s)"
                                    % (seeds[r], N_try + r, ep, conf.EP_UPDATE, counts_per_loop[r][-1]))
+        if validate:
+            for r in range(R):
+                validation[r].append(dict(res[r]["validation"], ep=ep, update_step_counter=update_step_counter))
+                log(validation_line(validation[r][-1], prefix="N_try {} ".format(N_try + r)))
         update_step_counter = ens.learn_and_update(update_step_counter, buffers, ep)
         for r in range(R):
             n, ep_return = res[r]["n_kept"], res[r]["ep_return"]
@@ -328,7 +389,8 @@ def train_ensemble(conf, seeds, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=Fa
     ens.close()
     return [dict(update_step_counter=update_step_counter, ep_reward_arr=ep_reward_arr[r],
                  counts_per_loop=counts_per_loop[r], RLAC=learners[r], buffer=buffers[r], evaluation=[], returns=None,
-                 evaluation_seconds=None, seed=seeds[r], N_try=N_try + r) for r in range(R)]
+                 evaluation_seconds=None, seed=seeds[r], N_try=N_try + r, validation=validation[r])
+            for r in range(R)]
 
 
 def main(argv=None):
@@ -348,6 +410,8 @@ def main(argv=None):
         for o in outs:
             print("seed {} (N_try {}): updates {}  kept per loop: {}".format(
                 o["seed"], o["N_try"], o["update_step_counter"], [c["n_kept"] for c in o["counts_per_loop"]]))
+        if "validate_csv" in args:
+            write_validation_csv(args["validate_csv"], outs, with_seed=True)
         return outs
     if kw.get("evaluate") and (args.get("fig_path") or not getattr(conf, "Fig_path", None)):
         conf.Fig_path = args.get("fig_path") or os.path.join(os.getcwd(), "Results " + system_id, "Figures")
@@ -363,6 +427,8 @@ def main(argv=None):
         log("Evaluation: {} records, seconds {}{}".format(
             len(out["evaluation"]), {k: round(v, 3) for k, v in out["evaluation_seconds"].items()},
             "  figures in " + os.path.join(conf.Fig_path, "N_try_%s" % kw["N_try"]) if conf.Fig_path else ""))
+    if "validate_csv" in args:
+        write_validation_csv(args["validate_csv"], [out])
     return out
 
 

@@ -34,6 +34,49 @@ def dp_update_step(critic_grad, actor_grad, apply, all_reduce, soft_update):
     apply("actor", ga, False)
 
 
+def _ratio(a, b):
+    return float(a) / float(b) if b != 0 else float("nan")
+
+
+def _sqrt(x):
+    return math.sqrt(x) if x >= 0 else float("nan")
+
+
+VALIDATION_KEYS = ("rows", "episodes", "value_rmse", "value_r2", "grad_rmse", "grad_rel", "sobolev_loss",
+                   "actor_rmse_u", "warm", "warm_cost_mean", "to_cost_mean", "gap_mean", "gap_rel_median",
+                   "gap_rel_left_out")
+
+
+def validation_metrics(totals, J, ns, na, u_max, labels, warm):
+    """RL_AC.validate_samples' dict from cacto_validate's totals [CACTO_VAL_COLS] (host float64), the
+    kept episodes' J [n, 2] = (cost of the warm start, cost of the solution), and whether Sobolev
+    labels were compared. Host arithmetic in a fixed order: equal inputs give equal floats."""
+    t = [float(x) for x in totals]
+    rows, n = t[L.CACTO_VAL_ROWS], len(J)
+    sse_V, sse_g = t[L.CACTO_VAL_SSE_V], t[L.CACTO_VAL_SSE_G]
+    var = t[L.CACTO_VAL_SUM_G2] - _ratio(t[L.CACTO_VAL_SUM_G] ** 2, rows)
+    su = 0.0
+    for j in range(na):
+        su += t[L.CACTO_VAL_SSE_U + j] / float(u_max[j]) ** 2
+    J0, J1 = (J[:, 0], J[:, 1]) if n else (np.zeros(0), np.zeros(0))
+    gap = J0 - J1
+    nz = J1 != 0
+    out = dict(rows=int(rows), episodes=int(n),
+               value_rmse=_sqrt(_ratio(sse_V, rows)),
+               value_r2=1.0 - _ratio(sse_V, var) if var > 0 else float("nan"),
+               grad_rmse=_sqrt(_ratio(sse_g, rows * (ns - 1))) if labels else None,
+               grad_rel=_sqrt(_ratio(sse_g, t[L.CACTO_VAL_SUM_L2])) if labels else None,
+               sobolev_loss=_ratio(t[L.CACTO_VAL_SSE_CLOG], rows * (ns - 1)) if labels else None,
+               actor_rmse_u=_sqrt(_ratio(su, (rows - n) * na)),
+               warm=warm,
+               warm_cost_mean=float(J0.mean()) if n else float("nan"),
+               to_cost_mean=float(J1.mean()) if n else float("nan"),
+               gap_mean=float(gap.mean()) if n else float("nan"),
+               gap_rel_median=float(np.median(gap[nz] / np.abs(J1[nz]))) if nz.any() else float("nan"),
+               gap_rel_left_out=int(n - nz.sum()))
+    return out
+
+
 class _Done:
     """The handle of an exchange that completed when it was issued (a synchronous all-reduce)."""
 
@@ -642,7 +685,7 @@ class RL_AC:
 
     COUNTERS = ("rows", "kept", "zero_length", "nan_rollouts", "converged", "maxiter", "failed")
 
-    def compute_samples(self, ep, ICS_list, TrOp, buffer, cfg=None, accept_maxiter=False):
+    def compute_samples(self, ep, ICS_list, TrOp, buffer, cfg=None, accept_maxiter=False, validate=False):
         """compute_sample (main.py:174-195) for every initial state of an iteration, followed by the
         buffer.add of main.py:240, on the device: one roll-out launch (create_TO_init), one
         TrOp.solve_batch (TO_System_Solve), the filter of main.py:181-187 / :236 with the ring offsets
@@ -660,18 +703,21 @@ class RL_AC:
         Returns a dict: kept (host int32 [E]: NSTEPS_SH, or -1 for a dropped episode), the counters
         of COUNTERS (rows, kept as n_kept, ...), ep_return (host float64, kept episodes in order) and
         dev, the device tensors S, U, step_cost, status, iters, dVdx (None with w_S == 0), EE_TO, and
-        with env_RL S_RL, R_RL, EE_RL."""
+        with env_RL S_RL, R_RL, EE_RL.
+
+        `validate`: also run the validation stage (validate_samples) on the kept episodes before
+        they reach the ring: res["validation"] and res["dev"]["validation"]. Off, nothing of it runs."""
         res, pre = self.samples_rollout(ep, ICS_list)
         if pre is None:
             return res
         sol = TrOp.solve_batch(pre["S0"], pre["warm"], pre["live"], cfg=cfg)
-        return self.samples_collect(res, pre, sol, TrOp, buffer, accept_maxiter, cfg=cfg)
+        return self.samples_collect(res, pre, sol, TrOp, buffer, accept_maxiter, cfg=cfg, validate=validate)
 
     def samples_rollout(self, ep, ICS_list):
         """compute_samples up to its TrOp.solve_batch: the result dict with its counters at zero, and
         the solve's inputs — dict(E, T, S0 [E, ns], n [E] int32, roll_status [E], warm [E, T, na] f64,
-        live [E] int32 (NSTEPS_SH, or -1 for an episode the roll-out dropped)), all on the device —
-        or None when no episode has a step to take (nothing was launched)."""
+        live [E] int32 (NSTEPS_SH, or -1 for an episode the roll-out dropped)), all on the device, and
+        ep — or None when no episode has a step to take (nothing was launched)."""
         ICS = np.asarray(ICS_list, dtype=np.float64).reshape(len(ICS_list), -1)
         E = ICS.shape[0]
         ns_ = np.array([self.nsteps_sh(s) for s in ICS], dtype=np.int32)
@@ -687,13 +733,14 @@ class RL_AC:
         roll = self.rollout_batch(ICS, ns_, T, ep=ep, want=("S", "A"), inputs=inputs)
         warm = roll["A"].double() if ep != 0 else torch.zeros(E, T, na, dtype=torch.float64, device=DEVICE)
         live = torch.where((roll["status"] == 0) & (n_d > 0), n_d, torch.full_like(n_d, -1))
-        return res, dict(E=E, T=T, S0=S0_d, n=n_d, roll_status=roll["status"], warm=warm, live=live)
+        return res, dict(E=E, T=T, S0=S0_d, n=n_d, roll_status=roll["status"], warm=warm, live=live, ep=ep)
 
-    def samples_collect(self, res, pre, sol, TrOp, buffer, accept_maxiter=False, cfg=None):
+    def samples_collect(self, res, pre, sol, TrOp, buffer, accept_maxiter=False, cfg=None, validate=False):
         """compute_samples from its TrOp.solve_batch on: `sol` is the solve of samples_rollout's
-        inputs `pre` (S [E, T + 1, ns], U [E, T, na], step_cost [E, T + 1], status, iters). `cfg`: the
-        solve's; its `labels` key says which Sobolev labels follow (cacto_amd.to.label_bounds). Fills
-        and returns `res`."""
+        inputs `pre` (S [E, T + 1, ns], U [E, T, na], step_cost [E, T + 1], status, iters; J [E, 2] for
+        `validate`). `cfg`: the solve's; its `labels` key says which Sobolev labels follow
+        (cacto_amd.to.label_bounds). `validate`: run validate_samples once the labels exist, before
+        the ring write. Fills and returns `res`."""
         from .to import label_bounds
         E, T, S0_d, n_d = pre["E"], pre["T"], pre["S0"], pre["n"]
         roll = dict(status=pre["roll_status"])
@@ -720,6 +767,8 @@ class RL_AC:
             S_rows, R_rows, R_sum, negate = dev["S_RL"], dev["R_RL"], dev["R_RL"], 0
         else:                                       # RL.py:166-167: the TO's states, rwrd = -TO_step_cost
             S_rows, R_rows, R_sum, negate = sol["S"], -sol["step_cost"], sol["step_cost"], 1
+        if validate:
+            self.validate_samples(res, pre, sol, kept_d, off_d, S_rows, R_sum, negate)
         buffer.add_episodes_planned(S_rows, R_rows, off_d, rows, T, dVdx=dev["dVdx"])
         ret_d = torch.empty(E, dtype=torch.float64, device=DEVICE)
         L.lib().call("cacto_episode_returns", dptr(R_sum, torch.float64), R_sum.shape[1], dptr(kept_d), E, negate,
@@ -730,6 +779,50 @@ class RL_AC:
         res["kept"] = kept_d.cpu().numpy()
         res["ep_return"] = ret_d.cpu().numpy()[res["kept"] >= 0]
         return res
+
+    def validate_samples(self, res, pre, sol, kept_d, off_d, S_rows, R_sum, negate):
+        """The validation stage: this learner's current critic and actor against the kept TO
+        trajectories of `sol`, whose initial states were drawn for this loop and which no update has
+        seen yet (one cacto_validate; the header defines the sums and their order). kept_d / off_d:
+        cacto_collect_plan's; S_rows [E, T + 1, ns] and R_sum [E, T + 1] with `negate`: the states and
+        rewards the ring write takes (the TO's, or with env_RL the re-simulation's). Labels:
+        res["dev"]["dVdx"]. Stores res["dev"]["validation"], the per-episode table [E, CACTO_VAL_COLS]
+        on the device, and res["validation"], a dict of plain floats over all kept rows:
+
+          rows, episodes    counts
+          value_rmse        sqrt(sse_V / rows), V against the float64 reward-to-go G of the trajectory
+          value_r2          1 - sse_V / (sum_G2 - sum_G^2 / rows); NaN when G has no variance
+          grad_rmse         sqrt(sse_g / (rows (ns - 1))), dV/ds against the Sobolev labels
+          grad_rel          sqrt(sse_g / sum_l2)
+          sobolev_loss      sse_clog / (rows (ns - 1)): the Sobolev term of the critic loss
+          actor_rmse_u      sqrt(sum_j sse_u[j] / u_max_j^2 / ((rows - episodes) na)): actor against TO
+                            controls, in units of u_max
+          warm              "zero" for ep == 0, else "actor": what the solve was warm-started with
+          warm_cost_mean, to_cost_mean   means of J[:, 0] and J[:, 1] over kept episodes
+          gap_mean          mean of J0 - J; with warm == "actor" the policy's optimality gap
+          gap_rel_median    median of (J0 - J) / |J| over kept episodes with J != 0
+          gap_rel_left_out  kept episodes with J == 0
+
+        The three gradient keys are None without labels (w_S == 0); a ratio over nothing is NaN."""
+        E, ns, na = pre["E"], self.conf.nb_state, self.conf.nb_action
+        rows = res["rows"]
+        dVdx = res["dev"].get("dVdx")
+        f64 = dict(dtype=torch.float64, device=DEVICE)
+        per_ep = torch.empty(E, L.CACTO_VAL_COLS, **f64)
+        totals_d = torch.empty(L.CACTO_VAL_COLS, **f64)
+        nbytes = L.lib().raw("cacto_validate_workspace_bytes")(self.sys.handle, rows)
+        ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=DEVICE)
+        L.lib().call("cacto_validate", self.sys.handle, dptr(self.critic_model.buf), dptr(self.actor_model.buf),
+                     dptr(S_rows, torch.float64), S_rows.shape[1], dptr(sol["U"], torch.float64), sol["U"].shape[1],
+                     dptr(R_sum, torch.float64), R_sum.shape[1], int(negate), dptr(dVdx, torch.float64), dptr(kept_d),
+                     dptr(off_d), E, rows, dptr(per_ep), dptr(totals_d), dptr(ws), ws.numel() * 4, stream())
+        tot = totals_d.cpu().numpy()
+        keep = kept_d.cpu().numpy() >= 0
+        J = sol["J"].cpu().numpy()[keep]
+        res["dev"]["validation"] = per_ep
+        res["validation"] = validation_metrics(tot, J, ns, na, np.asarray(self.conf.u_max, dtype=np.float64),
+                                               dVdx is not None, "zero" if pre["ep"] == 0 else "actor")
+        return res["validation"]
 
     def RL_save_weights(self, update_step_counter='final'):
         """RL.py:191-195: Keras-2.11 .h5 files the reference can load."""
@@ -1006,12 +1099,13 @@ class Ensemble:
         return update_step_counter
 
     # ---- main.py:174-195 for every replica, one TO solve ----
-    def compute_samples(self, ep, ICS_lists, TrOp, buffers, cfg=None, accept_maxiter=False):
+    def compute_samples(self, ep, ICS_lists, TrOp, buffers, cfg=None, accept_maxiter=False, validate=False):
         """RL_AC.compute_samples for every replica with ONE TrOp.solve_batch: per replica the roll-out
         with its own actor (samples_rollout), then one solve over all replicas' episodes (start
         states, warm starts and live lengths concatenated, the warm starts padded to the largest
         horizon), then per replica, on its slice of the solution, samples_collect. The solver
-        treats every episode on its own, so a replica's slice equals its solo solve. Returns one
+        treats every episode on its own, so a replica's slice equals its solo solve. `validate`: the
+        validation stage per replica, with that replica's networks on its own slice. Returns one
         compute_samples dict per replica."""
         if len(ICS_lists) != len(self.learners) or len(buffers) != len(self.learners):
             raise ValueError("Ensemble.compute_samples: one ICS list and one buffer per learner")
@@ -1038,5 +1132,6 @@ class Ensemble:
                         status=sol["status"][a:a + E].contiguous(), iters=sol["iters"][a:a + E].contiguous(),
                         J=sol["J"][a:a + E].contiguous())
             a += E
-            out[r] = self.learners[r].samples_collect(out[r], pre, part, TrOp, buffers[r], accept_maxiter, cfg=cfg)
+            out[r] = self.learners[r].samples_collect(out[r], pre, part, TrOp, buffers[r], accept_maxiter, cfg=cfg,
+                                                      validate=validate)
         return out

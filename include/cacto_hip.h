@@ -39,6 +39,8 @@
  *   cacto_buffer_add       ReplayBuffer.add ring write replay_buffer.py:25-36
  *   cacto_rl_solve_add     RL_AC.RL_Solve n-step targets RL.py:145-189 fused with the
  *                          buffer.add of its output (main.py:240)
+ *   cacto_validate         the critic and the actor against an iteration's fresh TO trajectories
+ *                          (value, Sobolev-gradient and action errors; no reference counterpart)
  *   cacto_per_*            PrioritizedReplayBuffer + segment trees replay_buffer.py:87-218,
  *                          segment_tree.py:4-145 (cacto_per_plan: which kernels a batch takes; no
  *                          reference counterpart)
@@ -833,6 +835,55 @@ int cacto_collect_plan(const int32_t* nsteps_d, const int32_t* rollout_status_d,
  * One thread per episode. */
 int cacto_episode_returns(const double* R_d, int64_t ldR, const int32_t* kept_d, int n_ep, int negate,
                           double* ret_d, void* stream);
+
+/* The validation stage: the critic and the actor against the trajectories of an iteration's freshly
+ * drawn initial states, before learn_and_update has seen them (no reference counterpart). Columns of
+ * per_ep_d / totals_d: */
+#define CACTO_VAL_ROWS 0     /* Te + 1 */
+#define CACTO_VAL_SUM_G 1    /* sum_t G_t */
+#define CACTO_VAL_SUM_G2 2   /* sum_t G_t^2 */
+#define CACTO_VAL_SUM_V 3    /* sum_t V_t */
+#define CACTO_VAL_SSE_V 4    /* sum_t (V_t - G_t)^2 */
+#define CACTO_VAL_SSE_G 5    /* sum_t sum_{j < ns-1} (g_tj - l_tj)^2 */
+#define CACTO_VAL_SUM_L2 6   /* sum_t sum_{j < ns-1} l_tj^2 */
+#define CACTO_VAL_SSE_CLOG 7 /* sum_t sum_{j < ns-1} (clog(g_tj) - clog(l_tj))^2 */
+#define CACTO_VAL_SSE_U 8    /* + j, j < nb_action: sum_{t < Te} (a_tj - u_tj)^2; the rest 0 */
+#define CACTO_VAL_COLS 16    /* CACTO_VAL_SSE_U + CACTO_MAX_ACTION */
+/* With Te = kept_d[e] (Te < 0: nothing of episode e is read, its per_ep row is all zero) and
+ * kept_d, row_off_d, total_rows exactly what cacto_collect_plan produced:
+ *   1. the live rows S_traj_d[e, t], t = 0..Te, are cast to float32 as NN.eval casts them and written
+ *      at row row_off_d[e] + t of a compact [total_rows, ns] matrix in the workspace;
+ *   2. G_t, the reward-to-go, in float64 by the backward recursion G_Te = r_Te, G_t = r_t + G_{t+1},
+ *      r_t = R_d[e, t], or -R_d[e, t] with negate (pass TO_step_cost with negate = 1 for env_RL = 0, as
+ *      for cacto_episode_returns). This is a NEW quantity: it is not RL_Solve's total_reward_to_go,
+ *      which is a left-to-right sum rounded to float32 (cacto_rl_solve_add's total_d);
+ *   3. V_t and g_t = dV/ds(s_t) by cacto_critic_input_grad's launcher and a_t by cacto_actor_forward's
+ *      on the compact matrix (in chunks of 2^24 rows): bit for bit what those entries give on the same
+ *      float32 rows;
+ *   4. per_ep_d [n_ep, CACTO_VAL_COLS]: the sums named above in float64, l = dVdx_d[e, t] (the Sobolev
+ *      labels, [n_ep, ldS, ns]), clog = custom_logarithm (NeuralNetwork.py:140-148) in float64, the
+ *      components j < ns - 1 as compute_critic_grad takes them (NeuralNetwork.py:168), u = U_traj_d[e, t]
+ *      ([n_ep, ldU, na]). One wave per episode: lane i adds the terms of t = i, i + 64, ... within
+ *      1024-step chunks taken last chunk first, and the lanes' partial sums are combined pairwise
+ *      (lane distance 32, 16, .., 1), so a row depends on its episode alone;
+ *   5. totals_d [CACTO_VAL_COLS] = 0.0 + per_ep[0] + per_ep[1] + ... left to right in episode order.
+ * Two runs on the same inputs give the same bits, and so do the same episodes inside a larger batch
+ * whose other episodes are dropped.
+ * dVdx_d, critic_netbuf_d and actor_netbuf_d may each be NULL: that part is skipped and its columns
+ * are 0 (SSE_G and SSE_CLOG need the labels and the critic, SUM_L2 the labels alone). Needs Te < ldS,
+ * Te <= ldU, Te < ldR and row_off_d[e] + Te + 1 <= total_rows; an episode that violates this is not
+ * read and its per_ep row (and so the totals) is NaN. workspace_d: cacto_validate_workspace_bytes(sys,
+ * total_rows) bytes (0 for a null handle or total_rows < 0). Stream-ordered, no synchronisation; five
+ * launches per 2^24 rows, whatever n_ep; total_rows == 0 only zeroes the two outputs. CACTO_EINVAL,
+ * before anything is enqueued: a null required argument, n_ep < 1, total_rows < 0, a leading dimension
+ * < 1, a workspace that is too small. This stage is bound by launch and memory latency (a few tens of
+ * thousands of rows), not by throughput. */
+size_t cacto_validate_workspace_bytes(const cacto_sys* sys, int64_t total_rows);
+int cacto_validate(const cacto_sys* sys, const float* critic_netbuf_d, const float* actor_netbuf_d,
+                   const double* S_traj_d, int64_t ldS, const double* U_traj_d, int64_t ldU, const double* R_d,
+                   int64_t ldR, int negate, const double* dVdx_d, const int32_t* kept_d, const int64_t* row_off_d,
+                   int n_ep, int64_t total_rows, double* per_ep_d, double* totals_d, void* workspace_d,
+                   size_t workspace_bytes, void* stream);
 
 /* replay_buffer.py:47-61: S, R, S_next, dVdx, d as float32, term float64; any may be NULL. */
 int cacto_buffer_gather(const cacto_sys* sys, const double* storage_d, const int32_t* idx_d, int B,
