@@ -118,6 +118,7 @@ CACTO_TO_CONVERGED, CACTO_TO_MAXITER, CACTO_TO_FAILED = 0, 1, 2
 CACTO_TO_PATH_DEFAULT, CACTO_TO_PATH_WAVE = 0, 1
 CACTO_TO_HESS_EXACT, CACTO_TO_HESS_PSD = 0, 1
 CACTO_TO_BOUNDS_NONE, CACTO_TO_BOUNDS_BOX = 0, 1
+CACTO_TO_STARTS_MAX = 16     # candidates per episode of a multi-start solve (cacto_to_starts / cacto_to_select)
 PER_UPDATE_SET, PER_UPDATE_SUB, PER_UPDATE_CHAIN = 0, 1, 2
 # columns of cacto_validate's per_ep / totals (CACTO_VAL_* in the header)
 (CACTO_VAL_ROWS, CACTO_VAL_SUM_G, CACTO_VAL_SUM_G2, CACTO_VAL_SUM_V, CACTO_VAL_SSE_V, CACTO_VAL_SSE_G,
@@ -208,6 +209,10 @@ _SIGS = {
                                      sz, vp, C.POINTER(ToOpts), C.POINTER(ToBox)]),
     "cacto_to_solve_plan_box": (C.c_int, [vp, C.POINTER(ToCfg), C.POINTER(ToPlan), C.POINTER(ToOpts),
                                           C.POINTER(ToBox)]),
+    "cacto_to_starts": (C.c_int, [vp, vp, vp, i64, vp, C.c_int, C.c_int, dbl, C.c_int, vp, C.c_int, C.c_uint64, vp, vp,
+                                  vp, vp]),
+    "cacto_to_select": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, i64, i64, C.c_int, vp, vp, vp, vp,
+                                  vp, vp, vp, vp, vp, vp, vp]),
     "cacto_buffer_add": (C.c_int, [vp, vp, i64, i64, vp, i64, vp]),
     "cacto_rl_solve_add": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp, C.c_int, C.c_int, i64, C.c_int, C.c_int, vp,
                                      i64, i64, vp, vp]),

@@ -16,7 +16,8 @@ ARCH = os.environ.get("CACTO_OFFLOAD_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=" + ARCH,
          "-Wall", "-Wno-unused-function", "-Wno-unused-variable"]
 SOURCES = ["core.hip", "env_kernels.hip", "net_kernels.hip", "rollout_kernels.hip", "ddp_kernels.hip", "to_kernels.hip",
-           "learn_kernels.hip", "elu_kernels.hip", "learn_host.hip", "replay_kernels.hip", "collect_kernels.hip"]
+           "learn_kernels.hip", "elu_kernels.hip", "learn_host.hip", "replay_kernels.hip", "collect_kernels.hip",
+           "multistart_kernels.hip"]
 
 
 def hipcc():

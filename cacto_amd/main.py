@@ -41,7 +41,9 @@ def parse_args(argv=None):
     --accept-maxiter (keep episodes whose solve stopped at max_iter). --to-hessian (the node Hessian
     of the TO's backward pass, cacto_amd.to.HESSIANS; exact when absent), --to-bounds (hard control
     limits of the TO, the conf's u_min / u_max; none when absent), --to-labels (the Sobolev labels
-    after a solve, cacto_amd.to.LABELS; bounded needs --to-bounds conf; reference when absent), --plots, --fig-path and
+    after a solve, cacto_amd.to.LABELS; bounded needs --to-bounds conf; reference when absent), --to-starts,
+    --to-start-sigma and --to-start-hold (several warm starts per TO episode, the cfg keys `starts`,
+    `start_sigma`, `start_hold`; one start when absent), --plots, --fig-path and
     --eval-every (the evaluation stage) and --seeds (several seeds at once, train_ensemble; not with
     --seed or --plots), --validate and --validate-csv (the validation stage; allowed with --seeds) are
     in the dict only when they are given. Returns a dict."""
@@ -84,6 +86,15 @@ def parse_args(argv=None):
     p.add_argument("--to-labels", type=str, default=argparse.SUPPRESS, choices=["reference", "bounded"],
                    help="Sobolev labels after a TO solve: the reference's unconstrained dV/dx, or with --to-bounds conf "
                         "the recursion that leaves the controls a limit holds out (default: reference)")
+    p.add_argument("--to-starts", type=int, default=argparse.SUPPRESS,
+                   help="Solve every TO episode from this many warm starts (1..16) in one solve and keep the best: "
+                        "the actor's roll-out, zero controls, and perturbed roll-outs (default: 1, one solve)")
+    p.add_argument("--to-start-sigma", type=float, default=argparse.SUPPRESS,
+                   help="With --to-starts: size of the perturbations, as a fraction of half the control range "
+                        "(default: cacto_amd.to.DEFAULT_CFG, an unmeasured working value)")
+    p.add_argument("--to-start-hold", type=int, default=argparse.SUPPRESS,
+                   help="With --to-starts: steps over which a perturbation stays constant (default: "
+                        "cacto_amd.to.DEFAULT_CFG, an unmeasured working value)")
     p.add_argument("--plots", action="store_true", default=argparse.SUPPRESS,
                    help="Run the evaluation stage: value grid, TO trajectories, return and roll-out figures")
     p.add_argument("--fig-path", type=str, default=argparse.SUPPRESS,
@@ -99,6 +110,12 @@ def parse_args(argv=None):
         p.error("--validate-csv needs --validate")
     if args.get("to_labels") == "bounded" and args.get("to_bounds", "none") != "conf":
         p.error("--to-labels bounded needs --to-bounds conf: the labels take the bounds of the solve")
+    from .to import make_starts
+    try:
+        make_starts({k: args[a] for k, a in (("starts", "to_starts"), ("start_sigma", "to_start_sigma"),
+                                             ("start_hold", "to_start_hold")) if a in args})
+    except ValueError as err:
+        p.error(str(err))
     if "seeds" in args:
         if seed_given:
             p.error("--seed and --seeds exclude each other")
@@ -117,6 +134,9 @@ def train_kwargs(args):
         kw["to_cfg"]["bounds"] = args["to_bounds"]
     if "to_labels" in args:
         kw["to_cfg"]["labels"] = args["to_labels"]
+    for key, arg in (("starts", "to_starts"), ("start_sigma", "to_start_sigma"), ("start_hold", "to_start_hold")):
+        if arg in args:
+            kw["to_cfg"][key] = args[arg]
     if args.get("plots"):
         kw.update(evaluate=True, eval_every=args.get("eval_every", 1))
     if args.get("validate"):
@@ -131,6 +151,12 @@ def validation_line(v, prefix=""):
             "gap_rel_median")
     return "{}Validation loop {} (updates {}): {}".format(prefix, v["ep"], v["update_step_counter"],
                                                          "  ".join("%s=%s" % (k, fmt(v[k])) for k in keys))
+
+
+def multistart_line(m, prefix=""):
+    """One log line for a loop's multi-start record (train's `multistart` entries)."""
+    return "{}Multi-start loop {}: starts={}  rescued={}  improved={}  won_by={}  gain_rel_median={:.4g}".format(
+        prefix, m["ep"], m["starts"], m["rescued"], m["improved"], m["won_by"], m["gain_rel_median"])
 
 
 def write_validation_csv(path, outs, with_seed=False):
@@ -172,8 +198,13 @@ def train(conf, seed=0, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=False, n_l
     networks and writes nothing they or the replay buffer depend on, so the trained result is the
     same bits with and without it.
 
+    `to_cfg["starts"]` > 1: every TO episode of a loop is solved from that many warm starts and the
+    best is kept (RL_AC.compute_samples); the candidates' generator is keyed by `seed` and the loop
+    index and draws no host random number. One log line per loop; `multistart` in the result is one
+    rl.multistart_stats dict per loop with `ep` added, an empty list with one start.
+
     Returns dict(update_step_counter, ep_reward_arr, counts_per_loop, RLAC, buffer, evaluation,
-    returns, evaluation_seconds, validation): validation is one validate_samples dict per loop with
+    returns, evaluation_seconds, validation, multistart): validation is one validate_samples dict per loop with
     `ep` and `update_step_counter` (the counter before that loop's updates) added, an empty list
     without `validate`; evaluation is the stage's records in call order, each dict(kind
     ('traj' | 'value' | 'return' | 'rollout'), update_step_counter, ep (None outside the loop),
@@ -191,6 +222,7 @@ def train(conf, seed=0, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=False, n_l
     NN_inst = NN(env, conf, w_S, seed=seed)
     TrOp = TO(env, conf, w_S)
     RLAC = RL_AC(env, NN_inst, conf, N_try)
+    RLAC.start_seed = seed          # the multi-start candidates' stream (to_cfg["starts"] > 1) follows the run's seed
     buffer = ReplayBuffer(conf) if conf.prioritized_replay_alpha == 0 else PrioritizedReplayBuffer(conf)
     if getattr(conf, "NNs_path", None):
         os.makedirs(os.path.join(conf.NNs_path, "N_try_%s" % N_try), exist_ok=True)
@@ -219,6 +251,7 @@ def train(conf, seed=0, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=False, n_l
     ep_reward_arr = np.zeros(int(conf.EP_UPDATE) * n_sched) * np.nan
     counts_per_loop = []
     validation = []
+    multistart = []
     val_kw = dict(validate=True) if validate else {}     # off: compute_samples is called as it always was
     for ep in range(loops):
         init_rand_state = [env.reset() for _ in range(conf.EP_UPDATE)]
@@ -229,6 +262,9 @@ def train(conf, seed=0, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=False, n_l
         n = res["n_kept"]
         if n == 0:
             raise RuntimeError("loop %d: no episode of %d was kept (%s)" % (ep, conf.EP_UPDATE, counts_per_loop[-1]))
+        if "multistart" in res:
+            multistart.append(dict(res["multistart"], ep=ep))
+            log(multistart_line(multistart[-1]))
         if validate:
             validation.append(dict(res["validation"], ep=ep, update_step_counter=update_step_counter))
             log(validation_line(validation[-1]))
@@ -261,7 +297,8 @@ def train(conf, seed=0, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=False, n_l
                                      states=np.array(plot_fun.states_all_sim)))
     return dict(update_step_counter=update_step_counter, ep_reward_arr=ep_reward_arr, counts_per_loop=counts_per_loop,
                 RLAC=RLAC, buffer=buffer, evaluation=evaluation, returns=returns,
-                evaluation_seconds=dict(plot_fun.seconds) if evaluate else None, validation=validation)
+                evaluation_seconds=dict(plot_fun.seconds) if evaluate else None, validation=validation,
+                multistart=multistart)
 
 
 class HostRng:
@@ -339,6 +376,7 @@ def train_ensemble(conf, seeds, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=Fa
     for r, seed in enumerate(seeds):
         with rngs[r]:
             rl = RL_AC(env, NN(env, conf, w_S, seed=seed), conf, N_try + r)
+            rl.start_seed = seed    # as train sets it: the replica's multi-start stream is its solo run's
             buffers.append(ReplayBuffer(conf))
             if getattr(conf, "NNs_path", None):
                 os.makedirs(os.path.join(conf.NNs_path, "N_try_%s" % (N_try + r)), exist_ok=True)
@@ -355,6 +393,7 @@ def train_ensemble(conf, seeds, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=Fa
     ep_reward_arr = [np.zeros(int(conf.EP_UPDATE) * n_sched) * np.nan for _ in range(R)]
     counts_per_loop = [[] for _ in range(R)]
     validation = [[] for _ in range(R)]
+    multistart = [[] for _ in range(R)]
     val_kw = dict(validate=True) if validate else {}
     for ep in range(loops):
         ics = []
@@ -370,6 +409,10 @@ def train_ensemble(conf, seeds, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=Fa
             if res[r]["n_kept"] == 0:
                 raise RuntimeError("seed %d (N_try %d), loop %d: no episode of %d was kept (%s)"
                                    % (seeds[r], N_try + r, ep, conf.EP_UPDATE, counts_per_loop[r][-1]))
+        for r in range(R):
+            if "multistart" in res[r]:
+                multistart[r].append(dict(res[r]["multistart"], ep=ep))
+                log(multistart_line(multistart[r][-1], prefix="N_try {} ".format(N_try + r)))
         if validate:
             for r in range(R):
                 validation[r].append(dict(res[r]["validation"], ep=ep, update_step_counter=update_step_counter))
@@ -389,7 +432,8 @@ def train_ensemble(conf, seeds, N_try=0, w_S=0.0, to_cfg=None, accept_maxiter=Fa
     ens.close()
     return [dict(update_step_counter=update_step_counter, ep_reward_arr=ep_reward_arr[r],
                  counts_per_loop=counts_per_loop[r], RLAC=learners[r], buffer=buffers[r], evaluation=[], returns=None,
-                 evaluation_seconds=None, seed=seeds[r], N_try=N_try + r, validation=validation[r])
+                 evaluation_seconds=None, seed=seeds[r], N_try=N_try + r, validation=validation[r],
+                 multistart=multistart[r])
             for r in range(R)]
 
 

@@ -77,6 +77,30 @@ def validation_metrics(totals, J, ns, na, u_max, labels, warm):
     return out
 
 
+def multistart_stats(sol, kept, accept_maxiter=False):
+    """What the extra warm starts of a multi-start solve were worth, from TO.solve_multistart's dict
+    `sol` (start [E], J_starts / status_starts [E, N]; device tensors or arrays) and compute_samples'
+    `kept` [E] (>= 0: the episode went into the ring). A plain dict: starts = N; rescued, the kept
+    episodes whose candidate 0 was not acceptable (CONVERGED, or MAXITER with accept_maxiter, and a
+    finite cost) and that another candidate won; improved, the kept episodes another candidate won
+    although candidate 0 was acceptable; won_by [N], the kept episodes per winning candidate;
+    gain_rel_median, the median of (J_0 - J_winner) / |J_0| over the improved episodes with J_0 != 0
+    (NaN when there is none). Host arithmetic on four small arrays."""
+    host = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+    start, J, st = host(sol["start"]), host(sol["J_starts"]), host(sol["status_starts"])
+    N = J.shape[1]
+    keep = np.asarray(kept) >= 0
+    ok0 = ((st[:, 0] == L.CACTO_TO_CONVERGED) | (bool(accept_maxiter) & (st[:, 0] == L.CACTO_TO_MAXITER))) \
+        & np.isfinite(J[:, 0])
+    other = keep & (start > 0)
+    improved = other & ok0
+    e = np.nonzero(improved & (J[:, 0] != 0))[0]
+    gain = (J[e, 0] - J[e, start[e]]) / np.abs(J[e, 0])
+    return dict(starts=int(N), rescued=int((other & ~ok0).sum()), improved=int(improved.sum()),
+                won_by=[int((keep & (start == c)).sum()) for c in range(N)],
+                gain_rel_median=float(np.median(gain)) if len(e) else float("nan"))
+
+
 class _Done:
     """The handle of an exchange that completed when it was issued (a synchronous all-reduce)."""
 
@@ -152,6 +176,7 @@ class RL_AC:
         self.NSTEPS_SH = 0
         self._ws = None
         self._ws_B = 0
+        self.start_seed = 0     # the run's half of the multi-start generator key (compute_samples; train sets its seed)
 
     # ---- RL.py:61-99 ----
     def setup_model(self, recover_training=None, weights=None):
@@ -706,12 +731,28 @@ class RL_AC:
         with env_RL S_RL, R_RL, EE_RL.
 
         `validate`: also run the validation stage (validate_samples) on the kept episodes before
-        they reach the ring: res["validation"] and res["dev"]["validation"]. Off, nothing of it runs."""
+        they reach the ring: res["validation"] and res["dev"]["validation"]. Off, nothing of it runs.
+
+        cfg["starts"] > 1: every episode is solved from that many warm starts in one solve
+        (TrOp.solve_multistart) and its best acceptable candidate goes on: candidate 0 is the warm
+        start above, candidate 1 zero controls (from loop 1 on; at loop 0 the warm start is zero
+        itself), the rest perturbations drawn on the device from the stream
+        stream_key(self.start_seed, ep) — no host random number. Everything after the solve is as
+        with one start; res["multistart"] (multistart_stats) says what the extra starts were worth.
+        With starts == 1 nothing of it runs and the key is absent."""
+        from .to import make_starts, stream_key
         res, pre = self.samples_rollout(ep, ICS_list)
         if pre is None:
             return res
-        sol = TrOp.solve_batch(pre["S0"], pre["warm"], pre["live"], cfg=cfg)
-        return self.samples_collect(res, pre, sol, TrOp, buffer, accept_maxiter, cfg=cfg, validate=validate)
+        N = make_starts(cfg)[0]
+        if N == 1:
+            sol = TrOp.solve_batch(pre["S0"], pre["warm"], pre["live"], cfg=cfg)
+            return self.samples_collect(res, pre, sol, TrOp, buffer, accept_maxiter, cfg=cfg, validate=validate)
+        sol = TrOp.solve_multistart(pre["S0"], pre["warm"], pre["live"], cfg=cfg, seed=stream_key(self.start_seed, ep),
+                                    zero_start=(ep != 0), accept_maxiter=accept_maxiter)
+        res = self.samples_collect(res, pre, sol, TrOp, buffer, accept_maxiter, cfg=cfg, validate=validate)
+        res["multistart"] = multistart_stats(sol, res["kept"], accept_maxiter)
+        return res
 
     def samples_rollout(self, ep, ICS_list):
         """compute_samples up to its TrOp.solve_batch: the result dict with its counters at zero, and
@@ -1106,7 +1147,7 @@ class Ensemble:
         horizon), then per replica, on its slice of the solution, samples_collect. The solver
         treats every episode on its own, so a replica's slice equals its solo solve. `validate`: the
         validation stage per replica, with that replica's networks on its own slice. Returns one
-        compute_samples dict per replica."""
+        compute_samples dict per replica. cfg["starts"] > 1: _compute_samples_multistart."""
         if len(ICS_lists) != len(self.learners) or len(buffers) != len(self.learners):
             raise ValueError("Ensemble.compute_samples: one ICS list and one buffer per learner")
         pres = [rl.samples_rollout(ep, ics) for rl, ics in zip(self.learners, ICS_lists)]
@@ -1114,6 +1155,10 @@ class Ensemble:
         out = [res for res, _ in pres]
         if not live:
             return out
+        from .to import make_starts
+        N = make_starts(cfg)[0]
+        if N > 1:
+            return self._compute_samples_multistart(N, ep, live, out, TrOp, buffers, cfg, accept_maxiter, validate)
         na = self.conf.nb_action
         Tmax = max(pre["T"] for _, pre in live)
         Etot = sum(pre["E"] for _, pre in live)
@@ -1134,4 +1179,40 @@ class Ensemble:
             a += E
             out[r] = self.learners[r].samples_collect(out[r], pre, part, TrOp, buffers[r], accept_maxiter, cfg=cfg,
                                                       validate=validate)
+        return out
+
+    def _compute_samples_multistart(self, N, ep, live, out, TrOp, buffers, cfg, accept_maxiter, validate):
+        """compute_samples with cfg["starts"] = N > 1: per replica the candidate batch of its own
+        episodes (TO.multistart_expand with that replica's start_seed, its episodes numbered from 0 as
+        in its solo run), ONE solve_batch over every replica's N E_r candidates, then per replica the
+        selection on its slice and samples_collect — RL_AC.compute_samples' steps, so a replica's
+        result equals its solo run bit for bit."""
+        from .to import stream_key
+        na = self.conf.nb_action
+        Tmax = max(pre["T"] for _, pre in live)
+        rows = sum(N * pre["E"] for _, pre in live)
+        warm = torch.zeros(rows, Tmax, na, dtype=torch.float64, device=DEVICE)
+        S0_all, n_all = [], []
+        a = 0
+        for r, pre in live:
+            S0_r, U_r, n_r = TrOp.multistart_expand(pre["S0"], pre["warm"], pre["live"], cfg,
+                                                    seed=stream_key(self.learners[r].start_seed, ep),
+                                                    zero_start=(ep != 0))
+            warm[a:a + N * pre["E"], :pre["T"]] = U_r
+            S0_all.append(S0_r)
+            n_all.append(n_r)
+            a += N * pre["E"]
+        sol = TrOp.solve_batch(torch.cat(S0_all).contiguous(), warm, torch.cat(n_all).contiguous(), cfg=cfg)
+        a = 0
+        for r, pre in live:
+            E, T = pre["E"], pre["T"]
+            b = a + N * E
+            part = dict(S=sol["S"][a:b, :T + 1].contiguous(), U=sol["U"][a:b, :T].contiguous(),
+                        step_cost=sol["step_cost"][a:b, :T + 1].contiguous(), status=sol["status"][a:b].contiguous(),
+                        iters=sol["iters"][a:b].contiguous(), J=sol["J"][a:b].contiguous())
+            a = b
+            best = TrOp.multistart_select(part, pre["live"], N, accept_maxiter=accept_maxiter)
+            out[r] = self.learners[r].samples_collect(out[r], pre, best, TrOp, buffers[r], accept_maxiter, cfg=cfg,
+                                                      validate=validate)
+            out[r]["multistart"] = multistart_stats(best, out[r]["kept"], accept_maxiter)
         return out

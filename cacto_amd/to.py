@@ -12,6 +12,8 @@ UR5.reward leaves out), the dynamics Env.simulate. It is a local method like IPO
 stationary point of the same problem, not necessarily the same one.
 
   solve_batch            the solver on device tensors
+  solve_multistart       solve_batch from cfg["starts"] warm starts per episode, the best one kept
+                         (multistart_expand, one solve_batch, multistart_select)
   solve_plan             what solve_batch runs for a config (one kernel or a host-issued loop)
   backward_gains_batch   one regularised backward pass (gains k, K, expected decrease, PD verdict)
   forward_batch          one closed-loop roll-out with step size alpha
@@ -53,13 +55,25 @@ CONVERGED, MAXITER, FAILED = L.CACTO_TO_CONVERGED, L.CACTO_TO_MAXITER, L.CACTO_T
 # not read the key). "reference": TO.backward_pass as the reference has it, the unconstrained dV/dx
 # along the solution, bounded or not; "bounded": backward_pass with the bounds of the same cfg, which
 # leaves the controls a bound holds out of the recursion (cacto_ddp_backward_box). Needs `bounds`.
+# starts: candidate warm starts per episode (solve_multistart; solve_batch itself does not read the
+# key). 1: the one solve from the caller's warm start, nothing else launched. N in 2..STARTS_MAX: every
+# episode is solved from N warm starts in one solve over N E episodes — the caller's own, all-zero
+# controls, and the caller's plus a perturbation that is constant over start_hold steps and uniform
+# within +- start_sigma times half the control range (cacto_to_starts) — and the acceptable candidate
+# with the lowest final cost is kept (cacto_to_select). start_seed: the generator's stream for callers
+# of solve_multistart / TO_System_Solve that pass no seed (RL_AC.compute_samples makes its own key
+# from RL_AC.start_seed and the loop index).
+# start_sigma = 0.5 and start_hold = 8 are working values that NOBODY HAS MEASURED: nothing rests on
+# them while starts defaults to 1, and the table of DESIGN.md §6 is where a measured pair belongs.
 DEFAULT_CFG = dict(max_iter=400, max_ls=10, gtol=1e-4, armijo=1e-4, mu_min=1e-6, mu_up=10.0, mu_down=10.0,
-                   mu_max=1e10, poll_every=8, path=0, hessian="exact", bounds="none", labels="reference")
+                   mu_max=1e10, poll_every=8, path=0, hessian="exact", bounds="none", labels="reference",
+                   starts=1, start_sigma=0.5, start_hold=8, start_seed=0)
 PATHS = {"default": L.CACTO_TO_PATH_DEFAULT, "wave": L.CACTO_TO_PATH_WAVE}
 HESSIANS = {"exact": L.CACTO_TO_HESS_EXACT, "psd": L.CACTO_TO_HESS_PSD}
 LABELS = ("reference", "bounded")
-NOT_FIELDS = ("hessian", "bounds", "labels")    # cfg keys that travel beside the ToCfg (make_opts, make_box,
-                                                # label_bounds)
+STARTS_MAX = L.CACTO_TO_STARTS_MAX
+# cfg keys that travel beside the ToCfg (make_opts, make_box, label_bounds, make_starts)
+NOT_FIELDS = ("hessian", "bounds", "labels", "starts", "start_sigma", "start_hold", "start_seed")
 
 
 def make_opts(cfg=None):
@@ -136,12 +150,36 @@ def label_bounds(cfg=None):
     return b
 
 
+def make_starts(cfg=None):
+    """(starts, start_sigma, start_hold, start_seed) of a cfg dict, checked: starts an integer in
+    [1, STARTS_MAX], start_sigma finite and >= 0, start_hold an integer >= 1, start_seed an integer.
+    A ToCfg (which holds none of them) and None give the defaults: one start."""
+    d = cfg if isinstance(cfg, dict) else {}
+    n, sigma, hold, seed = (d.get(k, DEFAULT_CFG[k]) for k in ("starts", "start_sigma", "start_hold", "start_seed"))
+    integer = lambda v: isinstance(v, numbers.Integral) and not isinstance(v, bool)
+    if not integer(n) or not 1 <= int(n) <= STARTS_MAX:
+        raise ValueError("TO starts must be an integer in [1, %d], not %r" % (STARTS_MAX, n))
+    if isinstance(sigma, bool) or not isinstance(sigma, numbers.Real) or not np.isfinite(sigma) or sigma < 0:
+        raise ValueError("TO start_sigma must be finite and >= 0, not %r" % (sigma,))
+    if not integer(hold) or int(hold) < 1:
+        raise ValueError("TO start_hold must be an integer >= 1, not %r" % (hold,))
+    if not integer(seed):
+        raise ValueError("TO start_seed must be an integer, not %r" % (seed,))
+    return int(n), float(sigma), int(hold), int(seed)
+
+
+def stream_key(seed, ep=0):
+    """The 64-bit generator key of cacto_to_starts for a run's seed and a loop index: seed mod 2^32 in
+    the high word, ep mod 2^32 in the low one, so no two loops of a run and no two runs share a stream."""
+    return ((int(seed) & 0xFFFFFFFF) << 32) | (int(ep) & 0xFFFFFFFF)
+
+
 def make_cfg(cfg=None):
     """The 64-byte ToCfg (cacto_to_cfg) of a cfg dict over DEFAULT_CFG. The `hessian`, `bounds` and
     `labels` keys are checked here but are no fields of that struct: they travel in the ToOpts that
     make_opts(cfg) and the ToBox that make_box(cfg, conf) give, and a caller who hands solve_batch /
     solve_plan a ToCfg passes those as `opts` and `bounds`; `labels` is read after the solve
-    (label_bounds)."""
+    (label_bounds). Neither are the multi-start keys (make_starts), which solve_multistart reads."""
     vals = dict(DEFAULT_CFG)
     vals.update(cfg or {})
     unknown = set(vals) - set(DEFAULT_CFG)
@@ -154,6 +192,7 @@ def make_cfg(cfg=None):
     make_opts(vals)
     make_box(vals)
     label_bounds(vals)
+    make_starts(vals)
     c = L.ToCfg()
     for k, v in vals.items():
         if k not in NOT_FIELDS:
@@ -227,6 +266,103 @@ class TO:
                      dptr(ws), nbytes, stream(), *extra)
         return out
 
+    # ------------------------------------------------------------------ several warm starts per episode
+    def _half_range(self, cfg=None, bounds=None):
+        """Half the control range per action, the unit of start_sigma: (hi - lo) / 2 under bounds
+        where both sides are finite, else conf.u_max."""
+        half = np.array(np.asarray(self.conf.u_max, dtype=np.float64).reshape(-1)[:self.conf.nb_action])
+        box = _cfg_box(cfg, self.conf, bounds)
+        if box is not None and box.mode == L.CACTO_TO_BOUNDS_BOX:
+            for j in range(self.conf.nb_action):
+                if np.isfinite(box.lo[j]) and np.isfinite(box.hi[j]):
+                    half[j] = (box.hi[j] - box.lo[j]) / 2
+        return np.ascontiguousarray(np.abs(half))
+
+    def multistart_expand(self, S0, U_init, nsteps, cfg=None, seed=None, zero_start=True, bounds=None):
+        """cacto_to_starts: the candidate batch of a multi-start solve, (S0_all [N E, ns], U_all
+        [N E, ldU, na], nsteps_all [N E]) with N = cfg["starts"], candidate-major (candidate c of
+        episode e is row c E + e; block 0 is the caller's batch, bit for bit). Candidate 1 is all
+        zeros when zero_start (clear it when U_init is zero already); the others are U_init plus
+        start_sigma * half range * xi, xi uniform in [-1, 1) and constant over start_hold steps, from
+        the counter-based generator the header states, keyed by `seed` (a 64-bit integer; None:
+        cfg["start_seed"]). Draws no host random number. One launch, asynchronous."""
+        N, sigma, hold, cfg_seed = make_starts(cfg)
+        seed = cfg_seed if seed is None else int(seed)
+        E, ldU = U_init.shape[0], U_init.shape[1]
+        ns, na = self.conf.nb_state, self.conf.nb_action
+        S0_all = torch.empty(N * E, ns, dtype=torch.float64, device=DEVICE)
+        U_all = torch.empty(N * E, ldU, na, dtype=torch.float64, device=DEVICE)
+        n_all = torch.empty(N * E, dtype=torch.int32, device=DEVICE)
+        half = self._half_range(cfg, bounds)
+        L.lib().call("cacto_to_starts", self.sys.handle, dptr(S0, torch.float64, (E, ns), "S0"),
+                     dptr(U_init, torch.float64, (E, ldU, na), "U_init"), ldU,
+                     dptr(nsteps, torch.int32, (E,), "nsteps"), E, N, sigma, hold, half.ctypes.data_as(C.c_void_p),
+                     int(bool(zero_start)), seed & 0xFFFFFFFFFFFFFFFF, dptr(S0_all), dptr(U_all), dptr(n_all),
+                     stream())
+        return S0_all, U_all, n_all
+
+    def multistart_select(self, sol_all, nsteps, N, accept_maxiter=False, out=None):
+        """cacto_to_select: per episode the acceptable candidate (CONVERGED, or MAXITER with
+        accept_maxiter, and a finite final cost) with the lowest final cost of sol_all — solve_batch's
+        dict over the N E rows of multistart_expand — lowest index on a tie, candidate 0 when none is
+        acceptable. Returns solve_batch's E-shaped dict (`out`, optional, with solve_batch's masking:
+        rows past Te and skipped episodes keep what it held; J[:, 0] is candidate 0's warm-start
+        cost) plus start [E] int32 (-1: skipped), n_ok [E] int32, J_starts [E, N], status_starts
+        [E, N]. One launch, asynchronous."""
+        N = int(N)
+        E = nsteps.shape[0]
+        ldS, ldU = sol_all["S"].shape[1], sol_all["U"].shape[1]
+        ns, na = self.conf.nb_state, self.conf.nb_action
+        f64 = dict(dtype=torch.float64, device=DEVICE)
+        i32 = dict(dtype=torch.int32, device=DEVICE)
+        if out is None:
+            out = dict(S=torch.zeros(E, ldS, ns, **f64), U=torch.zeros(E, ldU, na, **f64),
+                       step_cost=torch.zeros(E, ldS, **f64), status=torch.full((E,), -1, **i32),
+                       iters=torch.zeros(E, **i32), J=torch.zeros(E, 2, **f64))
+        else:
+            out = dict(out)
+            for k in ("S", "U", "step_cost", "status", "iters", "J"):
+                if tuple(out[k].shape) != (E,) + tuple(sol_all[k].shape[1:]):
+                    raise ValueError("multistart_select: out[%r] is %s, not %s" % (k, tuple(out[k].shape),
+                                                                                    (E,) + tuple(sol_all[k].shape[1:])))
+        if not 1 <= N <= STARTS_MAX or any(sol_all[k].shape[0] != N * E for k in ("S", "U", "step_cost", "status",
+                                                                                  "iters", "J")):
+            raise ValueError("multistart_select: N = %d candidates of %d episodes need N in [1, %d] and N E rows in "
+                             "every array of sol_all (S has %d)" % (N, E, STARTS_MAX, sol_all["S"].shape[0]))
+        out.update(start=torch.empty(E, **i32), n_ok=torch.empty(E, **i32),
+                   J_starts=torch.empty(E, N, **f64), status_starts=torch.empty(E, N, **i32))
+        R = N * E
+        L.lib().call("cacto_to_select", self.sys.handle, dptr(sol_all["S"], torch.float64, (R, ldS, ns), "S"),
+                     dptr(sol_all["U"], torch.float64, (R, ldU, na), "U"),
+                     dptr(sol_all["step_cost"], torch.float64, (R, ldS), "step_cost"),
+                     dptr(sol_all["status"], torch.int32, (R,), "status"),
+                     dptr(sol_all["iters"], torch.int32, (R,), "iters"),
+                     dptr(sol_all["J"], torch.float64, (R, 2), "J"), dptr(nsteps, torch.int32, (E,), "nsteps"),
+                     E, N, ldS, ldU,
+                     int(bool(accept_maxiter)), dptr(out["S"], torch.float64), dptr(out["U"], torch.float64),
+                     dptr(out["step_cost"], torch.float64), dptr(out["status"], torch.int32),
+                     dptr(out["iters"], torch.int32), dptr(out["J"], torch.float64), dptr(out["start"]),
+                     dptr(out["n_ok"]), dptr(out["J_starts"]), dptr(out["status_starts"]), stream())
+        return out
+
+    def solve_multistart(self, S0, U_init, nsteps, cfg=None, out=None, opts=None, bounds=None, seed=None,
+                         zero_start=True, accept_maxiter=False):
+        """solve_batch from cfg["starts"] warm starts per episode: multistart_expand, ONE solve_batch
+        over the N E candidates, multistart_select. Returns solve_batch's dict plus start, n_ok,
+        J_starts, status_starts (multistart_select). With starts == 1 (the default, and any ToCfg) it
+        is solve_batch: that call and nothing else, its dict without the four extras. The solver
+        treats every episode on its own, so candidate 0's solve is the one solve_batch would have
+        run, and the winner's cost is never above it where it is acceptable. Two kernels more than
+        solve_batch (and the fills of the candidates' outputs), nothing read back: capturable where
+        solve_plan says on_device."""
+        N = make_starts(cfg)[0]
+        if N == 1:
+            return self.solve_batch(S0, U_init, nsteps, cfg=cfg, out=out, opts=opts, bounds=bounds)
+        S0_all, U_all, n_all = self.multistart_expand(S0, U_init, nsteps, cfg, seed=seed, zero_start=zero_start,
+                                                      bounds=bounds)
+        sol_all = self.solve_batch(S0_all, U_all, n_all, cfg=cfg, opts=opts, bounds=bounds)
+        return self.multistart_select(sol_all, nsteps, N, accept_maxiter=accept_maxiter, out=out)
+
     def solve_plan(self, cfg=None, opts=None, bounds=None):
         """cacto_to_solve_plan: what solve_batch runs for this system with cfg and opts (as
         solve_batch's), as a dict: on_device (1: the whole loop is one kernel, nothing synchronises, the
@@ -284,8 +420,11 @@ class TO:
         S0 = torch.as_tensor(np.asarray(ICS_state, dtype=np.float64).reshape(1, ns), device=DEVICE)
         U = np.zeros((1, max(T, 1), na))
         U[0, :T] = np.asarray(init_TO_controls, dtype=np.float64).reshape(-1, na)[:T]
-        out = self.solve_batch(S0, torch.as_tensor(U, device=DEVICE),
-                               torch.tensor([T], dtype=torch.int32, device=DEVICE), cfg=cfg)
+        # cfg["starts"] > 1: the best of that many warm starts (stream cfg["start_seed"]; the all-zero
+        # candidate only where the warm start is not zero itself); 1: solve_batch, as ever
+        out = self.solve_multistart(S0, torch.as_tensor(U, device=DEVICE),
+                                    torch.tensor([T], dtype=torch.int32, device=DEVICE), cfg=cfg,
+                                    zero_start=bool(U.any()), accept_maxiter=accept_maxiter)
         status = int(out["status"][0].item())
         states = out["S"][0, :T + 1]
         TO_states = states[:, :ns - 1].cpu().numpy()

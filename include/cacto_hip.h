@@ -753,6 +753,67 @@ int cacto_to_solve_plan_opts(const cacto_sys* sys, const cacto_to_cfg* cfg_h, ca
 int cacto_to_solve_plan_box(const cacto_sys* sys, const cacto_to_cfg* cfg_h, cacto_to_plan* out,
                             const cacto_to_opts* opts, const cacto_to_box* box);
 
+/* Multi-start solves (no reference counterpart): every episode is solved from n_starts candidate warm
+ * starts in ONE cacto_to_solve over n_starts * n_ep episodes, and the best acceptable candidate is
+ * kept. cacto_to_starts builds that batch, cacto_to_select reduces its solution to the n_ep-shaped
+ * outputs cacto_to_solve writes. Both enqueue one kernel on the given stream, synchronise nothing and
+ * read nothing back. The layout of every `_all` array is candidate-major: candidate c of episode e is
+ * row c * n_ep + e, so rows [0, n_ep) are the caller's own batch. */
+#define CACTO_TO_STARTS_MAX 16
+
+/* S0_all_d [n_starts n_ep, ns] and nsteps_all_d [n_starts n_ep] are S0_d and nsteps_d tiled.
+ * U_all_d [n_starts n_ep, ldU, na], for every t < ldU and k < na (whatever nsteps_d says):
+ *   candidate 0             U_init_d[e, t, k], the same bits;
+ *   candidate 1             0.0 when zero_start != 0 (a caller whose warm start is zero already passes
+ *                           zero_start = 0, and candidate 1 is then a perturbation like the rest);
+ *   every other candidate   U_init_d[e, t, k] + s_k * xi, s_k = sigma * half_range_h[k] (a host array of
+ *                           na doubles, each finite and >= 0), two roundings: the product xi s_k, then
+ *                           the sum (the library is built with -ffp-contract=off).
+ * xi is uniform in [-1, 1) and constant over blocks of `hold` steps, block = t / hold (a perturbation
+ * that is smooth in t moves the trajectory; white noise averages out). It comes from a counter-based
+ * generator in 64-bit integer arithmetic, every operation modulo 2^64:
+ *   mix(z):  z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *            z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)          (splitmix64)
+ *   packed = e * 2^31 + block * 2^7 + c * 2^3 + k      (e < 2^31, block < 2^24, c < 16, k < 8)
+ *   h      = mix(mix(seed) ^ packed)
+ *   xi     = (double)(h >> 11) * 2^-52 - 1.0           (53 bits: exact)
+ * so an element depends on (seed, e, c, block, k) alone: not on n_ep, n_starts or the launch. No host
+ * random number is drawn.
+ * CACTO_EINVAL, nothing enqueued: a null pointer; n_starts outside [1, CACTO_TO_STARTS_MAX]; hold < 1;
+ * sigma negative or not finite; n_ep <= 0; ldU outside [1, 2^24); a bad half_range_h entry. */
+int cacto_to_starts(const cacto_sys* sys, const double* S0_d, const double* U_init_d, int64_t ldU,
+                    const int32_t* nsteps_d, int n_ep, int n_starts, double sigma, int hold,
+                    const double* half_range_h, int zero_start, uint64_t seed, double* S0_all_d, double* U_all_d,
+                    int32_t* nsteps_all_d, void* stream);
+
+/* The `_all` inputs are cacto_to_solve's outputs over the n_starts * n_ep rows cacto_to_starts laid
+ * out (S [.., ldS, ns], U [.., ldU, na], step_cost [.., ldS], status, iters, J [.., 2]); nsteps_d [n_ep]
+ * are the caller's lengths. Per episode e with Te = nsteps_d[e]:
+ *   acceptable  candidate c is acceptable when its status is CACTO_TO_CONVERGED, or CACTO_TO_MAXITER
+ *               with accept_maxiter != 0, AND its final cost J_all[c n_ep + e, 1] is finite;
+ *   winner      the acceptable candidate with the lowest final cost, the lowest index among equal
+ *               costs; candidate 0 when none is acceptable (the episode then fares as it does with
+ *               one start);
+ *   outputs     S_d[e, 0..Te], U_d[e, 0..Te-1], step_cost_d[e, 0..Te], status_d[e], iters_d[e] are the
+ *               winner's; J_d[e, 0] = J_all[e, 0], the cost of candidate 0's warm start (the caller's
+ *               own warm start, whoever wins), J_d[e, 1] the winner's final cost. Rows past Te keep
+ *               what the outputs held;
+ *   extras      start_d[e] = the winner's index, n_ok_d[e] = the number of acceptable candidates,
+ *               J_starts_d[e, c] = J_all[c n_ep + e, 1], status_starts_d[e, c] = status_all[c n_ep + e]
+ *               ([n_ep, n_starts] each).
+ * Te < 0 (a skipped episode; also a Te that does not fit ldS / ldU): none of the six outputs is
+ * written, start_d[e] = -1, n_ok_d[e] = 0, and J_starts_d / status_starts_d hold what the `_all`
+ * arrays held. These are cacto_to_solve's own masking rules, so with n_starts = 1 the outputs are a
+ * copy of the inputs' live parts. The outputs must not overlap the inputs.
+ * CACTO_EINVAL, nothing enqueued: a null pointer; n_starts outside [1, CACTO_TO_STARTS_MAX];
+ * n_ep <= 0; ldS <= 0; ldU <= 0. */
+int cacto_to_select(const cacto_sys* sys, const double* S_all_d, const double* U_all_d,
+                    const double* step_cost_all_d, const int32_t* status_all_d, const int32_t* iters_all_d,
+                    const double* J_all_d, const int32_t* nsteps_d, int n_ep, int n_starts, int64_t ldS, int64_t ldU,
+                    int accept_maxiter, double* S_d, double* U_d, double* step_cost_d, int32_t* status_d,
+                    int32_t* iters_d, double* J_d, int32_t* start_d, int32_t* n_ok_d, double* J_starts_d,
+                    int32_t* status_starts_d, void* stream);
+
 /* What cacto_rollout_sched runs for B episodes under a schedule (groups, workgroups), decided by the
  * same function that launches it. "eight" = the systems whose step needs no workgroup-wide dynamics
  * (SI, car, car_park, the prismatic DI), "planar" = a planar 3-joint chain (the manipulator), CUs =

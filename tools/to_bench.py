@@ -5,6 +5,10 @@ from 1e-6). Prints one JSON line: episodes/s, mean and max backward passes, the 
 
     python tools/to_bench.py [--system double_integrator] [--episodes 4096] [--path default|wave] [--repeat 3]
                              [--hessian exact|psd] [--bounds none|conf] [--helper 8]
+                             [--starts 1,2,4,8 [--start-sigma 0.5] [--start-hold 8] [--accept-maxiter]]
+
+--starts with anything but 1 measures the multi-start solve (TO.solve_multistart) instead and prints
+one JSON line with a row per value, starts = 1 (the plain solve) timed in the same rotation.
 
 --path wave runs the one-workgroup-per-episode persistent kernel (cacto_to_cfg.path; not the
 manipulator and UR5, which have none):
@@ -46,6 +50,11 @@ def main():
     ap.add_argument("--hessian", default="exact", choices=["exact", "psd"])
     ap.add_argument("--bounds", default="none", choices=["none", "conf"])
     ap.add_argument("--helper-only", action="store_true", help="time the helper alone (needs no GPU)")
+    ap.add_argument("--starts", default=[1], type=lambda s: [int(v) for v in s.split(",")],
+                    help="warm starts per episode, or a list timed in rotation, e.g. 1,2,4,8 (multistart below)")
+    ap.add_argument("--start-sigma", type=float, default=0.5)
+    ap.add_argument("--start-hold", type=int, default=8)
+    ap.add_argument("--accept-maxiter", action="store_true", help="with --starts: MAXITER counts as kept")
     args = ap.parse_args()
 
     import ilqr_ref as R
@@ -74,6 +83,9 @@ def main():
     dev = lambda a: torch.as_tensor(np.ascontiguousarray(a), device="cuda")  # noqa: E731
     S0_d, Te_d = dev(S0), dev(Te)
     U0_d = torch.zeros(args.episodes, max(int(Te.max()), 1), conf.nb_action, dtype=torch.float64, device="cuda")
+    if args.starts != [1]:
+        print(json.dumps(multistart(args, R, to, cfg, plan, S0_d, U0_d, Te_d, Te)))
+        return
     times = []
     for _ in range(args.repeat + 1):        # the first run warms up (workspace, code objects)
         torch.cuda.synchronize()
@@ -102,6 +114,43 @@ def main():
         res["gpu_status_same_episodes"] = status[:args.helper].tolist()
         res["gpu_iters_same_episodes"] = iters[:args.helper].tolist()
     print(json.dumps(res))
+
+
+def multistart(args, R, to, cfg, plan, S0_d, U0_d, Te_d, Te):
+    """--starts N[,N..]: TO.solve_multistart for every N of the list on the same episodes, timed in
+    rotation (each round runs every N once, in the list's order; the first round warms up), so that
+    starts = 1 — solve_batch itself — is the baseline of the same run. Per N: the best seconds, the
+    share of kept episodes (CONVERGED, or MAXITER with --accept-maxiter), the mean final cost of the
+    kept ones, and rl.multistart_stats (rescued, improved, won_by, gain_rel_median). The warm start
+    is zero, so there is no all-zero candidate: every candidate past 0 is a perturbation."""
+    import torch
+    from cacto_amd.rl import multistart_stats
+    times = {N: [] for N in args.starts}
+    outs = {}
+    for _ in range(args.repeat + 1):
+        for N in args.starts:
+            c = dict(cfg, starts=N, start_sigma=args.start_sigma, start_hold=args.start_hold)
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            outs[N] = to.solve_multistart(S0_d, U0_d, Te_d, cfg=c, seed=0, zero_start=False,
+                                          accept_maxiter=args.accept_maxiter)
+            torch.cuda.synchronize()
+            times[N].append(time.perf_counter() - t)
+    rows = []
+    for N in args.starts:
+        status, J = outs[N]["status"].cpu().numpy(), outs[N]["J"].cpu().numpy()
+        keep = (status == R.CONVERGED) | (args.accept_maxiter & (status == R.MAXITER))
+        row = dict(starts=N, seconds=min(times[N][1:]), seconds_all=times[N][1:], kept_share=float(keep.mean()),
+                   kept_cost_mean=float(J[keep, 1].mean()) if keep.any() else None,
+                   status_share=dict(converged=float((status == R.CONVERGED).mean()),
+                                     maxiter=float((status == R.MAXITER).mean()),
+                                     failed=float((status == R.FAILED).mean())))
+        if N > 1:
+            row.update(multistart_stats(outs[N], np.where(keep, Te, -1), args.accept_maxiter))
+        rows.append(row)
+    return dict(metric="to_multistart", system=args.system, path=args.path, hessian=args.hessian, bounds=args.bounds,
+                episodes=args.episodes, mean_steps=float(Te.mean()), accept_maxiter=bool(args.accept_maxiter),
+                start_sigma=args.start_sigma, start_hold=args.start_hold, plan=plan, rows=rows)
 
 
 def helper(R, args, S0, Te):

@@ -7,7 +7,9 @@ and per config and loop the mean +- std over the seeds of every validation metri
                                    [--w-S 1e-2] [--to-path wave] [--out FILE.json]
     python tools/validate_modes.py --cost double_integrator,car [--runs 3] [--to-path default]
 
-A mode is a comma-separated list of key=value pairs over cacto_amd.to.DEFAULT_CFG ("default": none).
+A mode is a comma-separated list of key=value pairs over cacto_amd.to.DEFAULT_CFG ("default": none),
+e.g. "starts=4" or "starts=4,start_sigma=0.25,start_hold=4" for several warm starts per TO episode;
+such a mode's rows also carry the loop's rescued and improved episodes.
 
 What is comparable across modes: gap_* and warm / to costs (the solver's own cost of the actor's
 roll-out against its solution) and value_* (V against the reward-to-go of the trajectory) measure
@@ -34,6 +36,8 @@ sys.path.insert(0, ROOT)
 DEFAULT_MODES = "default;hessian=psd;bounds=conf;bounds=conf,labels=bounded"
 METRICS = ("rows", "value_rmse", "value_r2", "grad_rmse", "grad_rel", "sobolev_loss", "actor_rmse_u",
            "warm_cost_mean", "to_cost_mean", "gap_mean", "gap_rel_median")
+NUMERIC = dict(starts=int, start_hold=int, start_seed=int, start_sigma=float)
+MULTISTART = ("rescued", "improved")     # per loop, of a mode with starts=N > 1 (train's `multistart` records)
 
 
 def parse_mode(text):
@@ -41,7 +45,9 @@ def parse_mode(text):
     if text.strip() not in ("", "default"):
         for part in text.split(","):
             k, v = part.split("=")
-            cfg[k.strip()] = v.strip()
+            k, v = k.strip(), v.strip()
+            # the multi-start keys are numbers ("starts=4", "start_sigma=0.25", "start_hold=4"); the rest are names
+            cfg[k] = NUMERIC[k](v) if k in NUMERIC else v
     return cfg
 
 
@@ -65,13 +71,16 @@ def run_modes(args):
                     row[k] = None
                 else:
                     row[k] = (float(np.mean(vals)), float(np.std(vals)))
+            for k in MULTISTART:
+                vals = [o["multistart"][ep][k] for o in outs if len(o["multistart"]) > ep]
+                row[k] = (float(np.mean(vals)), float(np.std(vals))) if vals else None
             table.append(row)
     print("system %s, seeds %s, w_S %g, to-path %s, accept_maxiter %s: mean +- std over the seeds"
           % (args.system_id, seeds, args.w_S, args.to_path, args.accept_maxiter))
-    print("| mode | loop | warm | " + " | ".join(METRICS) + " |")
-    print("|" + "---|" * (3 + len(METRICS)))
+    print("| mode | loop | warm | " + " | ".join(METRICS + MULTISTART) + " |")
+    print("|" + "---|" * (3 + len(METRICS + MULTISTART)))
     for row in table:
-        cells = ["-" if row[k] is None else "%.4g ± %.2g" % row[k] for k in METRICS]
+        cells = ["-" if row[k] is None else "%.4g ± %.2g" % row[k] for k in METRICS + MULTISTART]
         print("| %s | %d | %s | %s |" % (row["mode"], row["ep"], row["warm"], " | ".join(cells)))
     if args.out:
         with open(args.out, "w") as f:
