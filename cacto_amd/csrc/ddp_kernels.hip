@@ -15,7 +15,14 @@
 // here the planar-family derivatives are closed forms of the same expression (ellipses and the
 // peak term as softplus of their arguments: d softplus(z)/dz = sigmoid(z)). Qbar is inverted by
 // Gauss-Jordan with partial pivoting (np.linalg.pinv in the reference equals the inverse for the
-// nonsingular, mu-regularised Qbar): float64 results within 1e-9 relative of the oracle.
+// nonsingular, mu-regularised Qbar): float64 results within 1e-9 relative of the oracle at the short
+// horizons of tests/test_gpu_ddp.py (<= 24 steps). At full episode length the oracle's own formula is
+// not accurate in float64: it never symmetrises V_xx, and the antisymmetric rounding residue of
+// A^T V_xx A grows geometrically (a factor ~2.5 per step on a solved double-integrator episode; no
+// correct digit ~60 steps from the end). Both recursions below therefore end each node with
+//     V_xx = (V_xx + V_xx^T) / 2
+// (after the masked products, so bounds and no bounds share it) and are checked at full length against
+// the recursion at 80 digits (tests/ddp_mp_ref.py, tests/test_gpu_ddp_long.py).
 //
 // Every system: the single integrator (NJ = 0), car (NJ = -1) and prismatic Pinocchio chains (the
 // double integrator: M and nle constant, so ddq_dq = ddq_dv = 0 and Fu = dt [0; M^-1]) use closed
@@ -246,6 +253,11 @@ __global__ void __launch_bounds__(64) k_ddp_backward(const SysDevice* __restrict
         Vxx[r * N + c] = Qxx[r * N + c] - s;
       }
     }
+    // V_xx = (V_xx + V_xx^T) / 2: see the header
+#pragma unroll
+    for (int r = 0; r < N; ++r)
+#pragma unroll
+      for (int c = r + 1; c < N; ++c) Vxx[r * N + c] = Vxx[c * N + r] = 0.5 * (Vxx[r * N + c] + Vxx[c * N + r]);
 #pragma unroll
     for (int k = 0; k < N; ++k) Oe[(size_t)i * ns + k] = Vx[k];
     Oe[(size_t)i * ns + N] = 0.0;
@@ -377,13 +389,19 @@ __global__ void __launch_bounds__(64) k_ddp_riccati_wave(const SysDevice* __rest
       }
     }
     __syncthreads();
-    // V_xx = Q_xx - (Q_xu Qbar^-1) Q_xu^T
+    // Q_xx - (Q_xu Qbar^-1) Q_xu^T into sVA (last read two barriers ago), then V_xx = its symmetric part:
+    // element (c, r) comes from another lane, hence the barrier between the two
     for (int o = lane; o < N * N; o += 64) {
       const int r = o / N, c = o - r * N;
       double s = 0.0;
 #pragma unroll
       for (int k = 0; k < M; ++k) s += sQK[r * M + k] * sQxu[c * M + k];
-      sVxx[o] = sQxx[o] - s;
+      sVA[o] = sQxx[o] - s;
+    }
+    __syncthreads();
+    for (int o = lane; o < N * N; o += 64) {
+      const int r = o / N, c = o - r * N;
+      sVxx[o] = 0.5 * (sVA[o] + sVA[c * N + r]);
     }
     for (int k = lane; k <= N; k += 64) Oe[(size_t)i * ns + k] = k < N ? sVx[k] : 0.0;
     __syncthreads();

@@ -372,13 +372,16 @@ def _chain_augmented_derivative(conf, state, action, h=1e-20):
     return Fx, Fu
 
 
-def backward_pass(conf, states, controls, mu=1e-9, inverse="pinv"):
+def backward_pass(conf, states, controls, mu=1e-9, inverse="pinv", symmetrize=False):
     """TO.py:119-202. states [T, >= n] (s_0..s_{T-1}; a time column, if present, is ignored),
     controls [T-1, m]. Returns V_x [T, n+1] (the last, time, column stays 0).
     inverse="inv" evaluates Qbar_uu^-1 with np.linalg.inv instead of the reference's pinv: the two
     agree to rounding when Qbar_uu is well conditioned, and their difference measures how strongly
     the recursion amplifies rounding for that trajectory (Q_uu passes near zero where the reward's
-    curvature in u, -2 scale w6, is cancelled by dt^2 V_xx)."""
+    curvature in u, -2 scale w6, is cancelled by dt^2 V_xx).
+    symmetrize=True adds V_xx = (V_xx + V_xx^T) / 2 after each node, which the reference's formula
+    (the default) lacks: without it the antisymmetric rounding residue of A^T V_xx A grows
+    geometrically over a long episode (tests/ddp_mp_ref.py); the kernels symmetrise."""
     n, m = _n_m(conf)
     T = states.shape[0]
     X_bar = np.asarray(states, dtype=np.float64)[:, :n]
@@ -406,4 +409,6 @@ def backward_pass(conf, states, controls, mu=1e-9, inverse="pinv"):
         Qbar_uu_pinv = np.linalg.pinv(Qbar_uu) if inverse == "pinv" else np.linalg.inv(Qbar_uu)
         V_x[i, :-1] = Q_x - Q_xu @ Qbar_uu_pinv @ Q_u                                      # :192-193
         V_xx[i] = Q_xx - Q_xu @ Qbar_uu_pinv @ Q_xu.T
+        if symmetrize:
+            V_xx[i] = 0.5 * (V_xx[i] + V_xx[i].T)
     return V_x

@@ -19,12 +19,12 @@ def held_set(u, Q_u, lo, hi):
     return (at_lo & (Q_u < 0)) | (at_hi & (Q_u > 0)), at_lo | at_hi
 
 
-def backward_pass_box(conf, states, controls, lo, hi, mu=1e-9, inverse="pinv"):
+def backward_pass_box(conf, states, controls, lo, hi, mu=1e-9, inverse="pinv", symmetrize=False):
     """oracle.ddp.backward_pass under the bounds lo <= u <= hi ([m] each; +-inf: that side open).
     states [T, >= n], controls [T-1, m]. Returns (V_x [T, n+1] with the time column 0, held [T-1, m]
     bool, margin): margin is the smallest |Q_u[j]| / max|Q_u| of the node over the controls on a
     limit — how far the nearest held decision is from flipping (0: a control on a limit whose Q_u[j]
-    is 0; inf: no control on a limit)."""
+    is 0; inf: no control on a limit). symmetrize: as in oracle.ddp.backward_pass."""
     n, m = oddp._n_m(conf)
     T = states.shape[0]
     X_bar = np.asarray(states, dtype=np.float64)[:, :n]
@@ -69,6 +69,8 @@ def backward_pass_box(conf, states, controls, lo, hi, mu=1e-9, inverse="pinv"):
             Q_xf = Q_xu[:, free]
             V_x[i, :-1] = Q_x - Q_xf @ Qi @ Q_u[free]
             V_xx[i] = Q_xx - Q_xf @ Qi @ Q_xf.T
+        if symmetrize:
+            V_xx[i] = 0.5 * (V_xx[i] + V_xx[i].T)
     return V_x, held, margin
 
 

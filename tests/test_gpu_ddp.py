@@ -56,10 +56,14 @@ def test_ddp_backward_matches_oracle(system):
     got = out.cpu().numpy()
     n = conf.nb_state - 1
     for e in range(len(T)):
-        ref = oddp.backward_pass(conf, S[e, :T[e] + 1], U[e, :T[e]])
+        # These episodes run up to NSTEPS (the car's seed-21 batch: 418 steps). The kernels symmetrise
+        # V_xx per node, so the oracle does too: the reference's formula without it has no correct digit
+        # in float64 beyond ~60 steps (tests/test_ddp_long_cpu.py), and its own inv / pinv spread, the
+        # tolerance below, then allowed anything on the long episodes of this batch.
+        ref = oddp.backward_pass(conf, S[e, :T[e] + 1], U[e, :T[e]], symmetrize=True)
         # rounding amplification of this trajectory's recursion: the oracle against itself with
         # an equivalent inverse (see oracle/ddp.py); the GPU may differ by a multiple of it
-        alt = oddp.backward_pass(conf, S[e, :T[e] + 1], U[e, :T[e]], inverse="inv")
+        alt = oddp.backward_pass(conf, S[e, :T[e] + 1], U[e, :T[e]], inverse="inv", symmetrize=True)
         scale = np.abs(ref[:, :n]).max() + 1e-12
         tol = RTOL * scale + 100.0 * np.abs(alt[:, :n] - ref[:, :n]).max(axis=1, keepdims=True)
         assert (np.abs(got[e, :T[e] + 1, :n] - ref[:, :n]) <= tol).all(), (system, e)

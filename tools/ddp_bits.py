@@ -14,7 +14,12 @@ controls clamped to them (the share of controls on a limit and of episodes whose
 change are printed); cacto_env_jacobians on the 70 first nodes; cacto_to_backward_gains for
 {exact, psd} x {no bounds, conf bounds} x mu in {0, 1e-3}; cacto_to_solve on both paths for
 {exact, psd} x {no bounds, conf bounds} with max_iter = 5. --compare counts the arrays that differ
-by bit pattern over the rows each episode owns, over the arrays both files hold."""
+by bit pattern over the rows each episode owns, over the arrays both files hold.
+
+Against a build from before the label recursion symmetrised V_xx per node (ddp_kernels.hip's header) the
+dVdx arrays of cacto_ddp_backward and cacto_ddp_backward_box, and those of cacto_to_solve, which end with
+the same label pass, differ by design from the second step of an episode on (by rounding at these
+lengths); the jacobians, the gains and the solvers' trajectories must not."""
 import os
 import random
 import sys
